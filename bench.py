@@ -8,13 +8,20 @@ distribution, angle + BRIEF), undistort/rectify, feature grid, the Preprocess st
 and the brute-force kNN-2 Hamming matcher + ratio filter between the two descriptor sets.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, DIR/<name>.npy)
+  python bench.py ... --full                             (+ every other leg and check, see below)
 
 Prints ONE JSON line on rank 0.  `value` is whole-job frames/s (all ranks; weak scaling: every
 GPU processes its own batch, no data-path collective; one RCCL all_gather of a per-rank result
 block after the timed region).  `roofline` is for the dominant kernel (the FAST cell kernel),
-timed with HIP events recorded on the launch stream inside the timed region.  `cpu_baseline` is
-the CPU oracle (a restatement of the reference path — NOT the reference binary, which cannot be
-built here) timed on this box's host cores on a bounded sample of the same workload.
+timed with HIP events recorded on the launch stream inside the timed region.
+
+A plain run does only what the headline needs: inputs, warm-up, the K timed steps, the outputs
+(--dump-outputs) and the line.  --full adds the other legs (local and global BA, pose refinement,
+the per-frame front-end, the tracking chain, the Harris response, the KITTI shape), the measured
+copy bandwidth beside the roofline's peak, and `cpu_baseline`: the CPU oracle (a restatement of the
+reference path — NOT the reference binary, which cannot be built here) timed on this box's host
+cores on a bounded sample of the same workload, its results compared with the GPU's.
 """
 from __future__ import annotations
 
@@ -117,6 +124,67 @@ def snapshot_outputs(B, out_sets, kp64, kp64_g, desc_g, right_points, depth, n_s
             "g": kp64_g[:n].cpu().numpy().view(KP64_DTYPE).reshape(n, cap), "gd": desc_g[:n].cpu().numpy().view(np.uint64),
             "rp": right_points[:n].cpu().numpy(), "dp": depth[:n].cpu().numpy(), "ns": n_stereo[:n].cpu().numpy(),
             "knn": knn[:n].cpu().numpy().view(KNN2_DTYPE).reshape(n, cap), "pairs": pairs[:n].cpu().numpy(), "np": n_pairs[:n].cpu().numpy()}
+
+
+DUMP_FRAMES = 32     # frames of the batch whose per-keypoint outputs --dump-outputs writes (a fixed, seeded sample)
+DUMP_SEED = 20261016
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, B, kps, desc, nkp, kp64, kp64_g, desc_g, perm, cell_start, right_points, depth, n_stereo, knn, pairs, n_pairs):
+    """--dump-outputs: what the last timed step left in HBM, as its caller receives it, written as DIR/<name>.npy in float64 (exact
+    for every field: f32 / f64 coordinates, i32 counts and indices, descriptors as eight u32 words).  The counts cover the whole
+    batch ([0, B) left images, [B, 2B) right); the per-keypoint outputs cover a fixed, seeded sample of DUMP_FRAMES frames
+    (`sample_frames`), their valid rows only, concatenated in sample order -- so two builds compare output for output, whatever
+    their buffers hold past the counts."""
+    import torch
+
+    from snake_slam_amd.matcher import KNN2_DTYPE, KP64_DTYPE
+    from snake_slam_amd.orb import KEYPOINT_DTYPE
+
+    cap = kp64_g.shape[1]
+    S = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_FRAMES), replace=False))
+    idx = torch.from_numpy(S).to(kps.device)
+    both = torch.cat([idx, idx + B])
+    host = lambda t, rows: t.index_select(0, rows).cpu().numpy()  # noqa: E731
+    n_img = nkp.cpu().numpy().astype(np.int64)
+    n_l, n_r = n_img[S], n_img[S + B]
+    n_pr = n_pairs.cpu().numpy().astype(np.int64)[S]
+
+    def rows(a, counts):  # valid rows of each sampled frame, concatenated -> float64 [sum(counts), fields...]
+        return np.concatenate([a[i, :int(c)] for i, c in enumerate(counts)]).astype(np.float64)
+
+    def fields(rec, dtype, names):
+        v = rec.view(dtype).reshape(rec.shape[0], cap)
+        return np.stack([v[f] for f in names], -1)
+
+    s, kp64_f = len(S), list(KP64_DTYPE.names)
+    k = fields(host(kps, both), KEYPOINT_DTYPE, list(KEYPOINT_DTYPE.names))
+    kr = fields(host(kp64, both), KP64_DTYPE, kp64_f)
+    d = host(desc, both).view(np.uint32)
+    out = {
+        "sample_frames": S.astype(np.float64),
+        "keypoint_counts": n_img.astype(np.float64),
+        "stereo_match_counts": n_stereo.cpu().numpy().astype(np.float64),
+        "filtered_pair_counts": n_pairs.cpu().numpy().astype(np.float64),
+        "left_keypoints": rows(k[:s], n_l), "right_keypoints": rows(k[s:], n_r),                  # x, y, size, angle, response, octave
+        "left_descriptors": rows(d[:s], n_l), "right_descriptors": rows(d[s:], n_r),              # 8 x u32 per 256-bit descriptor
+        "rectified_left_keypoints": rows(kr[:s], n_l), "rectified_right_keypoints": rows(kr[s:], n_r),  # x, y, angle, octave
+        "grid_left_keypoints": rows(fields(host(kp64_g, idx), KP64_DTYPE, kp64_f), n_l),
+        "grid_left_descriptors": rows(host(desc_g, idx).view(np.uint32), n_l),
+        "grid_permutation": rows(host(perm, idx), n_l),
+        "grid_cell_start": host(cell_start, idx).astype(np.float64),
+        "right_points": rows(host(right_points, idx), n_l),
+        "depth": rows(host(depth, idx), n_l),
+        "knn2": rows(fields(host(knn, idx), KNN2_DTYPE, list(KNN2_DTYPE.names)), n_l),         # idx1, dist1, idx2, dist2
+        "filtered_pairs": rows(host(pairs, idx), n_pr),
+    }
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def compare_with_oracle(gpu, kept):
@@ -412,7 +480,7 @@ def kitti_leg(args):
     released the GPU's memory; a failure is reported in the line, it does not take the headline down."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "kitti", "--steps", str(args.kitti_steps), "--warmup", "2", "--batch", "512",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", "kitti", "--steps", str(args.kitti_steps), "--warmup", "2", "--batch", "512",
            "--ba-windows", "0", "--gba-keyframes", "0", "--pose-frames", "0", "--track-frames", "0", "--frame-calls", "0", "--kitti-steps", "0", "--harris-steps", "0",
            "--cpu-seconds", "3", "--check-frames", "16", "--distinct", "64"]
     try:
@@ -556,9 +624,20 @@ def main():
     ap.add_argument("--kitti-steps", type=int, default=20, help="steps of the KITTI leg of the default line (BASELINE.json configs[2]: 1241x376 stereo, 2000 "
                     "features, 7 levels; this script re-run with --workload kitti on 512 frames per step once the EuRoC legs are done, its line "
                     "embedded under \"kitti\"; 0 = skip; single GPU, euroc workload only)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the BA, global-BA, pose, per-frame, tracking, Harris and "
+                    "KITTI legs (their options above apply only here), the measured copy bandwidth and the CPU baseline with its checks "
+                    "against the oracle")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed to "
+                    "DIR/<name>.npy (float64; counts of the whole batch, per-keypoint outputs of a fixed, seeded sample of frames; batch mode)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and args.mode != "batch":
+        raise SystemExit("bench.py: --dump-outputs writes the batch mode's outputs (--mode batch)")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the outputs, the line
+        args.ba_windows = args.gba_keyframes = args.pose_frames = args.frame_calls = args.track_frames = 0
+        args.harris_steps = args.kitti_steps = 0
+        args.no_cpu_baseline = True
     spawn_ranks_if_needed(args)
     global W, H, ORB
     if args.workload == "kitti":  # reference configs/kitti.ini:30-34
@@ -694,6 +773,9 @@ def main():
     kps, desc, nkp = out_sets[(step_no[0] - 1) % n_sets]  # what the last step left in HBM (the legs below read it)
     stage_ms, n_calls = ext.stage_times() if not args.no_stage_events else ([0, 0, 0, 0, 0], 0)
     ext.set_profiling(False)
+    if args.dump_outputs and rank == 0:  # before any other leg touches the buffers
+        dump_outputs(args.dump_outputs, B, kps, desc, nkp, kp64, kp64_g, desc_g, perm, cell_start, right_points, depth, n_stereo, knn,
+                     pairs, n_pairs)
 
     elapsed = parallel.max_over_ranks(t1 - t0, dev)
     verify = not args.no_cpu_baseline and world == 1
@@ -1234,7 +1316,7 @@ def main():
                 except Exception:
                     traffic, valu = None, None
             peak_meas = None
-            if world == 1:
+            if world == 1 and args.full:
                 try:
                     peak_meas = measured_copy_bandwidth(dev)
                 except Exception as e:  # noqa: BLE001

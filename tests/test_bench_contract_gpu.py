@@ -4,6 +4,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -14,7 +15,7 @@ REQUIRED = {"metric": str, "value": float, "unit": str, "n_gpus": int, "steps": 
 
 
 def test_bench_prints_one_json_line():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--kitti-steps", "2", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--kitti-steps", "2", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16",
                         "--ba-windows", "8", "--pose-frames", "8", "--gba-keyframes", "0", "--no-cpu-baseline", "--frame-calls", "10"],
                        capture_output=True, text=True, cwd=str(ROOT), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -50,7 +51,7 @@ def test_line_carries_verified_cpu_baseline():
     """The default line's `cpu_baseline` is not only a timing: the oracle's results for the frames it processed are compared
     bit for bit with what the last timed steps left in HBM (both extractor output sets of the two-stream pipeline, the
     stereo / kNN-2 / filter outputs), and three BA windows with the oracle's solve.  Small batch, short CPU budget."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--kitti-steps", "0", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "24",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--kitti-steps", "0", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "24",
                         "--distinct", "6", "--ba-windows", "8", "--pose-frames", "0", "--gba-keyframes", "0", "--track-frames", "0",
                         "--cpu-seconds", "1.0"], capture_output=True, text=True, cwd=str(ROOT), timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -110,7 +111,7 @@ def test_two_ranks_rehearsal_on_one_gpu(mode):
     if mode == "sequence":
         cmd += ["--host-api"]
     if mode == "batch":
-        cmd += ["--batch", "16", "--ba-windows", "8", "--no-cpu-baseline"]
+        cmd += ["--full", "--batch", "16", "--ba-windows", "8", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(ROOT), timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -135,7 +136,7 @@ def test_one_rank_process_group_on_rccl():
 
     env = {k: v for k, v in os.environ.items() if k not in ("SNK_DIST_BACKEND", "SNK_BENCH_DEVICE")}
     env.update(SNK_DIST_FORCE="1", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29578")
-    for extra in (["--batch", "16", "--ba-windows", "8", "--track-frames", "0"], ["--mode", "sequence"], ["--mode", "sequence", "--host-api"]):
+    for extra in (["--full", "--batch", "16", "--ba-windows", "8", "--track-frames", "0"], ["--mode", "sequence"], ["--mode", "sequence", "--host-api"]):
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--kitti-steps", "0", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                             "--gba-keyframes", "0", "--pose-frames", "0"] + extra, capture_output=True, text=True, cwd=str(ROOT), timeout=900, env=env)
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -155,3 +156,41 @@ def test_lockstep_sequence_mode_line():
     t = d["trajectories"][0]
     assert t["sequences"] == 4 and t["frames_per_sequence"] == 6 and 0.6 * t["ground_truth_x"] < t["mean_final_x"] < 1.4 * t["ground_truth_x"]
     assert d["stereo_matches_per_frame"] > 100 and d["pose_inliers_per_frame"] > 30
+
+
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path, orc):
+    """Without --full the line carries the headline only, over exactly --steps timed steps; --dump-outputs writes what the last timed
+    step computed (float64, at most 64 MB), the same in two runs, and the dumped keypoints of a sampled frame are the oracle's."""
+    from snake_slam_amd import synth
+
+    def run(d):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--distinct", "8",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, cwd=str(ROOT), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    lines = [run(tmp_path / "a"), run(tmp_path / "b")]
+    for d in lines:
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["dtype"] == "u8" and d["higher_is_better"] is True
+        assert abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"], d
+        assert not {"ba", "pose_refine", "frontend_frame", "tracking", "harris", "kitti", "cpu_baseline"} & set(d), sorted(d)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(p.name for p in (tmp_path / "b").iterdir()) and "left_keypoints.npy" in files and "knn2.npy" in files
+    dumped = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for name, a in dumped.items():
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+    assert sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    counts = dumped["keypoint_counts"]
+    assert counts.shape == (32,) and abs(counts.mean() - lines[0]["keypoints_per_image"]) < 0.06
+    # first sampled frame, left image (frame b holds distinct pair b % 8) against the oracle
+    b = int(dumped["sample_frames"][0])
+    left, _ = synth.stereo_frame(b % 8, 752, 480)
+    want, wd = orc.orb_detect(orc.orb_params(1000, 1.2, 4, 20, 7), left)
+    n = int(counts[b])
+    assert n == len(want) > 50
+    got = dumped["left_keypoints"][:n]
+    for j, f in enumerate(("x", "y", "size", "angle", "response", "octave")):
+        assert np.array_equal(got[:, j], want[f].astype(np.float64)), f
+    assert np.array_equal(dumped["left_descriptors"][:n].astype(np.uint32), np.ascontiguousarray(wd).view(np.uint32).reshape(n, 8))

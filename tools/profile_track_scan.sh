@@ -5,7 +5,7 @@
 OUT=$(realpath -m "${1:-gpurun_out/track_scan}"); mkdir -p "$OUT"
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
 cd /tmp; export TMPDIR=/tmp
-B="python $ROOT/bench.py --ba-windows 0 --gba-keyframes 0 --pose-frames 0 --frame-calls 0 --kitti-steps 0 --no-cpu-baseline --steps 3 --warmup 1 --batch 256 --track-frames 256"
+B="python $ROOT/bench.py --full --ba-windows 0 --gba-keyframes 0 --pose-frames 0 --frame-calls 0 --kitti-steps 0 --no-cpu-baseline --steps 3 --warmup 1 --batch 256 --track-frames 256"
 timeout 200 $B --dump-track-inputs "$OUT/track_inputs.npz" > /dev/null 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ts -o t -- $B > /dev/null 2>&1
 grep -E "Name|frame_kernel|pose_kernel|resolve|gather" /tmp/ts/t_kernel_stats.csv > "$OUT/stats.csv"

@@ -9,8 +9,11 @@ if [ "${2:-}" != "notest" ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q -rf --tb=short 2>&1 | grep -v amdgpu.ids > gpurun_out/$TAG/pytest_gpu.log
   tail -3 gpurun_out/$TAG/pytest_gpu.log
 fi
-timeout 600 python bench.py 2>&1 | grep '"metric"' > gpurun_out/$TAG/bench_default.json
-timeout 600 python bench.py --workload kitti --ba-windows 0 --gba-keyframes 0 --pose-frames 0 --track-frames 0 --kitti-steps 0 2>&1 | grep '"metric"' > gpurun_out/$TAG/bench_kitti.json
+# the bench lines (--full: every leg and the CPU baseline) go to CHECKPOINT_DIR, checkpoints/<tag> by default
+CK=${CHECKPOINT_DIR:-$REPO/checkpoints/$TAG}
+mkdir -p "$CK"
+timeout 600 python bench.py --full 2>&1 | grep '"metric"' > "$CK/bench_default.json"
+timeout 600 python bench.py --full --workload kitti --ba-windows 0 --gba-keyframes 0 --pose-frames 0 --track-frames 0 --kitti-steps 0 2>&1 | grep '"metric"' > "$CK/bench_kitti.json"
 bash tools/profile_gpu.sh $TAG > gpurun_out/$TAG/profile_gpu.log 2>&1
 python tools/collect_traffic.py gpurun_out/prof_$TAG 2048 > gpurun_out/$TAG/collect_traffic.log 2>&1 && cp profiles/fast_kernel_traffic.json gpurun_out/$TAG/fast_kernel_traffic.json
 # the KITTI leg's own counters (round 6: no longer the EuRoC pass scaled by the image count): 512 stereo frames = 1024 images per launch
@@ -23,7 +26,7 @@ python tools/collect_pipeline_traffic.py gpurun_out/prof_$TAG gpurun_out/prof_ba
 (python tools/latency_frontend.py; python tools/frontend_latency_cpp.py; python tools/latency.py; python tools/lba_call_latency_cpp.py) 2>&1 | grep -v amdgpu.ids > gpurun_out/$TAG/latencies.log
 python -c "
 import json
-d=json.load(open('gpurun_out/$TAG/bench_default.json'))
+d=json.load(open('$CK/bench_default.json'))
 print('front-end', d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('stage_ms_per_step'))
 print('ba', d['ba']['value'], 'tracking', d['tracking']['value'])
 "

@@ -73,7 +73,7 @@ def main():
 
     # 3. the batch metric on all GPUs (weak scaling)
     if not a.skip_batch:
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "3"], env=env, capture_output=True, text=True,
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", str(n), "--steps", "20", "--warmup", "3"], env=env, capture_output=True, text=True,
                            timeout=3600, cwd=str(ROOT))
         lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
         assert r.returncode == 0 and lines, r.stderr[-3000:]

@@ -1,5 +1,5 @@
 """Candidate statistics of the fine / coarse projection matchers' window scans on bench.py's tracking inputs (CPU, numpy):
-    python bench.py ... --dump-track-inputs x.npz ;  python tools/track_scan_stats.py x.npz
+    python bench.py --full ... --dump-track-inputs x.npz ;  python tools/track_scan_stats.py x.npz
 Per wavefront of 64 consecutive local-map points: candidates per window (mean, max), grid columns per window, the trip count of the
 per-lane scan (sum over the column steps of the largest column among the 64 lanes) against the balanced one (total / 64)."""
 import sys
