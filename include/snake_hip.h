@@ -782,9 +782,26 @@ SNK_API int snk_ba_sync(snk_ba* h);
 /* Replaces BARecRel::create(scene) — LocalBundleAdjustment.cpp:359: analyse the structure, copy
  * the problem to the device.  set_problems loads `count` independent windows that are solved side
  * by side (one launch sequence for all).  The arrays are copied; they need not stay alive.
- * Limits: count <= 65535; n_img <= 32767 per problem (SNK_ERR_INVALID_ARG beyond). */
+ * Limits: count <= 65535; n_img <= 32767 per problem (SNK_ERR_INVALID_ARG beyond).
+ * A call that returns anything but SNK_OK leaves the handle with NO problem set: the previous one
+ * is gone as well (its device arrays may be partly overwritten), and solve, solve_async, reset,
+ * get_state, residuals, set_outliers and solve_local_scene fail with "no problem set" until a
+ * later set_problem(s) succeeds. */
 SNK_API int snk_ba_set_problem(snk_ba* h, const snk_ba_problem* problem);
 SNK_API int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count);
+
+/* Which form of the reduced-camera-system PCG the last successful set_problem(s) chose (read-only;
+ * tests and diagnostics).  *workgroups: the workgroups of the one-launch forms, 0 for the others.
+ * A refused cooperative launch during a solve turns the handle to SNK_BA_PCG_LAUNCHES. */
+enum
+{
+    SNK_BA_PCG_PER_PROBLEM  = 0, /* one workgroup per problem (S fits one workgroup's LDS) */
+    SNK_BA_PCG_LAUNCHES     = 1, /* multi-launch pcgl_* sequence (vectors in HBM) */
+    SNK_BA_PCG_PERSIST      = 2, /* one cooperative launch, two grid barriers per iteration */
+    SNK_BA_PCG_PERSIST1     = 3, /* one cooperative launch, one grid barrier, rows of S streamed */
+    SNK_BA_PCG_PERSIST_REG  = 4  /* one cooperative launch, one grid barrier, rows of S in registers */
+};
+SNK_API int snk_ba_pcg_form(const snk_ba* h, int* form, int* workgroups);
 
 /* Observations flagged here are ignored by solve / residuals, like StereoImagePoint::outlier
  * (LocalBundleAdjustment.cpp:382,391).  obs_outlier has n_obs entries in caller order; NULL clears. */

@@ -31,6 +31,10 @@ BA_RPC_DTYPE = np.dtype([("img1", "<i4"), ("img2", "<i4"), ("rel_pose", "<f8", 7
                          ("weight_translation", "<f8")])
 
 
+# snk_ba_pcg_form's values (include/snake_hip.h SNK_BA_PCG_*)
+PCG_FORMS = {0: "per_problem", 1: "launches", 2: "persist", 3: "persist1", 4: "persist_reg"}
+
+
 def lba_options(max_iterations=3, max_pcg_iterations=30, pcg_tol=1e-10, huber_mono=2.1, huber_stereo=2.3, lambda_init=0.0):
     """Defaults = reference LocalBundleAdjustment.cpp:47-64, SnakeGlobal.h:145-150."""
     return BaOptions(max_iterations, max_pcg_iterations, pcg_tol, huber_mono, huber_stereo, lambda_init)
@@ -89,6 +93,8 @@ class BARec:
         packed = [_pack(s) for s in scenes]
         arr = (BaProblem * len(packed))(*[p for p, _ in packed])
         t1 = time.perf_counter()
+        # a failed hand-over leaves the handle with no problem set (snake_hip.h): nothing of the previous scenes remains to be read
+        self._scenes = []
         _lib.check(self._lib.snk_ba_set_problems(self._h, arr, len(packed)), "snk_ba_set_problems")
         # what this binding adds (numpy -> snk_ba_problem structs) and what the C call took (bench.py reports them apart: a C++ host pays
         # only the second); the call returns with the uploads enqueued, snk_ba_sync waits for them
@@ -119,6 +125,12 @@ class BARec:
 
     def sync(self):
         _lib.check(self._lib.snk_ba_sync(self._h), "snk_ba_sync")
+
+    def pcg_form(self):
+        """(form, workgroups) of the reduced-system PCG the last hand-over chose: one of PCG_FORMS' keys (snk_ba_pcg_form)."""
+        f, w = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.snk_ba_pcg_form(self._h, C.byref(f), C.byref(w)), "snk_ba_pcg_form")
+        return PCG_FORMS[f.value], w.value
 
     def set_outliers(self, problem: int, mask) -> None:
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)

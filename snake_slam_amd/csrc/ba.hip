@@ -3032,6 +3032,12 @@ struct PcgLarge
     int timing;       // SNK_BA_PCG_TIMING=1 (diagnostic): workgroup 0 of pcgl_persist_reg adds its cycles per phase to ps[0..5]
 };
 constexpr int PERSIST_WGS_MAX = 1024;
+// the grid barrier's words (grid_barrier_xcd); pcgl_init zeroes all BAR_WORDS of them before every PCG
+constexpr int BAR_PER_XCD = PERSIST_WGS_MAX / 8;      // arrival flags of group x at bar[x * BAR_PER_XCD + (workgroup >> 3)]
+constexpr int BAR_XFLAG   = PERSIST_WGS_MAX;          // the eight group flags, one 32-byte run
+constexpr int BAR_GEN     = PERSIST_WGS_MAX + 32;     // the groups' generation words, 128 bytes apart
+constexpr int BAR_WORDS   = BAR_GEN + 8 * 32;
+static_assert(BAR_WORDS <= 2 * (PERSIST_WGS_MAX + 8), "the barrier's words live in the (PERSIST_WGS_MAX + 8) doubles behind wpap");
 static inline int snk_env_int(const char* name, int dflt)
 {
     const char* e = getenv(name);
@@ -3085,7 +3091,7 @@ __global__ __launch_bounds__(64) void pcgl_init(Arrays A, Opt O, PcgLarge W)
     rr = wave_sum64(rr);
     rz = wave_sum64(rz);
     if (pb == 0 && blockIdx.x == 0 && W.bar)
-        for (int i = threadIdx.x; i < PERSIST_WGS_MAX + 32 + 8 * 32 /* BAR_WORDS */; i += 64) W.bar[i] = 0u;  // the grid barrier's flags of pcgl_persist
+        for (int i = threadIdx.x; i < BAR_WORDS; i += 64) W.bar[i] = 0u;  // the grid barrier's flags of pcgl_persist
     if (threadIdx.x == 0)
     {
         W.prr[(size_t)pb * W.G + blockIdx.x] = rr;  // buffer 0
@@ -3253,11 +3259,6 @@ __global__ void pcgl_latch(Arrays A, Opt O, PcgLarge W, int k)
 // Scalars (r.r, r.z, p.Ap, alpha, beta, the stopping test) are re-derived by every workgroup from the partial sums in a fixed
 // order: deterministic, no floating-point atomics.  The barrier is an arrival counter in HBM: __syncthreads, one agent-scope
 // release increment per workgroup, a spin on an agent-scope acquire load, __syncthreads.
-constexpr int BAR_PER_XCD = PERSIST_WGS_MAX / 8;      // arrival flags of group x at bar[x * BAR_PER_XCD + (workgroup >> 3)]
-constexpr int BAR_XFLAG   = PERSIST_WGS_MAX;          // the eight group flags, one 32-byte run
-constexpr int BAR_GEN     = PERSIST_WGS_MAX + 32;     // the groups' generation words, 128 bytes apart
-constexpr int BAR_WORDS   = BAR_GEN + 8 * 32;
-static_assert(BAR_WORDS <= 2 * (PERSIST_WGS_MAX + 8), "the barrier's words live in the (PERSIST_WGS_MAX + 8) doubles behind wpap");
 
 __device__ __forceinline__ void grid_barrier_flat(unsigned* bar, unsigned n_wgs, unsigned& phase)
 {
@@ -4789,6 +4790,21 @@ int snk_ba_sync(snk_ba* h)
 int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
 {
     SNK_REQUIRE(h != nullptr, "ba is NULL");
+    // A call that fails leaves NO problem set, whichever of its many exits it takes (snake_hip.h): past the checks the early upload of a
+    // batch writes into the device arrays of the previous set and the host lists are cleared, so solve / get_state / residuals must then
+    // refuse ("no problem set") instead of running the old tables over half-replaced arrays -- and a refused argument or a failed HIP
+    // call ends the previous set as well, so that the caller never has to tell the exits apart.
+    h->count       = 0;
+    h->state_fresh = false;
+    struct NoSetOnFailure
+    {
+        snk_ba* h;
+        bool ok = false;
+        ~NoSetOnFailure()
+        {
+            if (!ok) h->count = 0, h->state_fresh = false;
+        }
+    } no_set_on_failure{h};
     SNK_REQUIRE(count >= 1 && count <= 65535 && problems != nullptr, "count must be 1..65535");
     for (int b = 0; b < count; ++b)  // the packed observation records hold the image index in 15 bits (SetObs)
         SNK_REQUIRE(problems[b].n_img <= SET_MAX_IMG, "a problem has more than 32767 images");
@@ -6177,12 +6193,27 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
                 sec_us[0] / 1000, sec_us[1] / 1000, sec_us[2] / 1000, sec_us[3] / 1000, sec_us[4] / 1000,
                 (sec_us[5] + sec_us[8] + sec_us[9]) / 1000, sec_us[8] / 1000, sec_us[9] / 1000, sec_us[5] / 1000, sec_us[6] / 1000, sec_us[7] / 1000);
     }
+    no_set_on_failure.ok = true;
     return SNK_OK;
 }
 
 int snk_ba_set_problem(snk_ba* h, const snk_ba_problem* problem)
 {
     return snk_ba_set_problems(h, problem, 1);
+}
+
+int snk_ba_pcg_form(const snk_ba* h, int* form, int* workgroups)
+{
+    SNK_REQUIRE(h != nullptr && form != nullptr && workgroups != nullptr, "bad arguments");
+    SNK_REQUIRE(h->count > 0, "no problem set");
+    const PcgLarge& W = h->pcgw;
+    if (!h->pcg_large)
+        *form = SNK_BA_PCG_PER_PROBLEM, *workgroups = 0;
+    else if (W.persist_wgs <= 0 || h->count != 1)
+        *form = SNK_BA_PCG_LAUNCHES, *workgroups = 0;
+    else
+        *form = W.persist_one == 2 ? SNK_BA_PCG_PERSIST_REG : W.persist_one == 1 ? SNK_BA_PCG_PERSIST1 : SNK_BA_PCG_PERSIST, *workgroups = W.persist_wgs;
+    return SNK_OK;
 }
 
 int snk_ba_set_outliers(snk_ba* h, int problem, const uint8_t* obs_outlier)

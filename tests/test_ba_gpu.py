@@ -1,7 +1,9 @@
 """GPU: HIP local BA vs the CPU oracle through the C ABI.  Tolerance (north_star): pose / point
 RMSE <= 1e-5 against the CPU restatement (fp64 on both sides; only summation orders differ)."""
-import numpy as np
+import functools
 import os
+
+import numpy as np
 
 import pytest
 
@@ -575,3 +577,133 @@ def test_hand_over_threads_end_with_the_handle(orc):
     if "SNK_BA_NO_HOST_POOL" not in os.environ:  # (the variants matrix runs this file with threads created and joined per pass as well)
         assert during > before, "a batch of 32 scenes is expected to use the threaded list builder"
     assert n_threads() <= before
+
+
+def _windows(n, seed):
+    """n small local-BA windows of ONE shape (6 keyframes, 100 points, 4 observations each): two batches made by this function with
+    different seeds have the same sizes and offsets everywhere and differ only in their values."""
+    return list(_windows64(seed)[:n])
+
+
+@functools.lru_cache(maxsize=None)
+def _windows64(seed):
+    from snake_slam_amd import synth
+
+    return tuple(synth.ba_scene(n_kf=6, n_pt=100, obs_per_pt=4, seed=seed + k)[0] for k in range(64))
+
+
+def _with_negative_weight(scenes):
+    """The batch with one relative pose constraint of weight_rotation -1 in its LAST problem (between two free keyframes):
+    snk_ba_set_problems refuses it late, after the early upload of a batch has written into the device arrays."""
+    from snake_slam_amd import synth
+
+    sc, gt = synth.ba_scene(n_kf=6, n_pt=100, obs_per_pt=4, seed=4711)
+    synth.ba_add_rpcs(sc, gt, seed=4712)
+    sc["rpc"] = sc["rpc"].copy()
+    sc["rpc"]["weight_rotation"][-1] = -1.0
+    return list(scenes[:-1]) + [sc]
+
+
+def _assert_no_problem_set(ba, cap_problems, cap_img, cap_pt, cap_obs):
+    """Every call that needs a problem set fails and names it.  The buffers are large enough for whatever a handle that still
+    (wrongly) holds the previous set would write into them."""
+    import ctypes as C
+
+    lib, h = ba._lib, ba._h
+    ci, cf = np.zeros(cap_problems), np.zeros(cap_problems)
+    pose, pt, chi = np.zeros((cap_img, 7)), np.zeros((cap_pt, 3)), np.zeros(cap_obs)
+    flags, it, n = np.zeros(cap_obs, np.uint8), C.c_int(0), C.c_int(0)
+    vp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+    calls = {
+        "solve": lambda: lib.snk_ba_solve(h, 2, vp(ci), vp(cf)),
+        "solve_async": lambda: lib.snk_ba_solve_async(h, 2),
+        "reset": lambda: lib.snk_ba_reset(h),
+        "get_state": lambda: lib.snk_ba_get_state(h, 0, vp(pose), vp(pt), C.byref(it)),
+        "residuals": lambda: lib.snk_ba_residuals(h, 0, vp(chi)),
+        "set_outliers": lambda: lib.snk_ba_set_outliers(h, 0, None),
+        "solve_local_scene": lambda: lib.snk_ba_solve_local_scene(h, 0, 4.0, 5.0, 1, vp(flags), C.byref(n), None, None, None, None),
+        "pcg_form": lambda: lib.snk_ba_pcg_form(h, C.byref(it), C.byref(n)),
+    }
+    for name, call in calls.items():
+        rc = call()
+        msg = lib.snk_last_error().decode(errors="replace")
+        assert rc != 0 and "no problem set" in msg, f"{name} after a failed hand-over: status {rc} ({msg!r})"
+    lib.snk_ba_sync(h)
+
+
+def _solve_all(ba, scenes, iterations):
+    ci, cf = ba.solve(iterations)
+    return [ci, cf] + [a for k in range(len(scenes)) for a in ba.state(k)[:2]]
+
+
+@pytest.mark.parametrize("case", ["3-windows", "20-windows", "64-windows", "global-343"])
+def test_failed_hand_over_leaves_no_problem_set(case):
+    """A hand-over that fails late (a negative constraint weight in the last problem of a batch) must not leave the previous problem
+    set behind: with 16 and more problems the observation arrays are uploaded chunk by chunk (one chunk below 64 problems, four from
+    64 on) into the device arrays of the PREVIOUS set before the constraints are checked, so the old tables would run over
+    half-replaced arrays.  After the failure every call that needs a problem set fails ("no problem set"), and the handle takes the
+    first batch again: its solution is bit-identical to a fresh handle's.  The global case puts a batch failure between two
+    hand-overs of a 343-keyframe scene (pcgl_persist_reg; its PCG buffers and persistent-launch state are reused)."""
+    from snake_slam_amd import synth
+    from snake_slam_amd.ba import BARec, gba_options, lba_options
+    from snake_slam_amd._lib import SnakeHipError
+
+    if case == "global-343":
+        a = [synth.ba_scene(n_kf=343, n_pt=12 * 343, obs_per_pt=6, seed=900 + 343, n_fixed=1)[0]]
+        b = _with_negative_weight(_windows(20, 5300))
+        opts, iters = gba_options(max_iterations=2, max_pcg_iterations=40), 2
+    else:
+        n = int(case.split("-")[0])
+        a, b = _windows(n, 5000), _with_negative_weight(_windows(n, 5200))
+        opts, iters = lba_options(), 3
+    cap = (max(len(a), len(b)), max(len(s["pose"]) for s in a + b), max(len(s["pt"]) for s in a + b),
+           max(len(s["obs_img"]) for s in a + b))
+    fresh = BARec(opts)
+    fresh.create(a)
+    want = _solve_all(fresh, a, iters)
+    fresh.close()
+
+    ba = BARec(opts)
+    ba.create(a)
+    got = _solve_all(ba, a, iters)
+    assert all(np.array_equal(x, y) for x, y in zip(got, want))
+    with pytest.raises(SnakeHipError, match="negative constraint weight"):
+        ba.create(b)
+    assert ba._scenes == []
+    _assert_no_problem_set(ba, *cap)
+    ba.create(a)
+    again = _solve_all(ba, a, iters)
+    ba.close()
+    for k, (x, y) in enumerate(zip(again, want)):
+        assert np.array_equal(x, y), f"output {k} after the failed hand-over differs from a fresh handle's"
+
+
+def test_refused_hand_over_arguments_leave_no_problem_set():
+    """The argument checks at the top of snk_ba_set_problems (no problems at all, a problem with more than 32767 images) end the previous
+    set as well: the header promises no problem set after ANY failed call.  The binding drops its scenes first, so BARec.solve -- which
+    sizes its cost arrays by the scenes it holds -- must be refused by the library, not run the old set into empty arrays."""
+    from snake_slam_amd.ba import BARec, lba_options
+    from snake_slam_amd._lib import SnakeHipError
+
+    a = _windows(3, 5000)
+    fresh = BARec(lba_options())
+    fresh.create(a)
+    want = _solve_all(fresh, a, 3)
+    fresh.close()
+    many = dict(a[0], pose=np.tile(a[0]["pose"][:1], (32768, 1)), img_const=np.ones(32768, np.uint8))
+    cap = (len(a), 32768, max(len(s["pt"]) for s in a), max(len(s["obs_img"]) for s in a))
+    ba = BARec(lba_options())
+    for bad, msg in (([], "count must be"), ([many], "more than 32767 images")):
+        ba.create(a)
+        _solve_all(ba, a, 3)
+        with pytest.raises(SnakeHipError, match=msg):
+            ba.create(bad)
+        assert ba._scenes == []
+        _assert_no_problem_set(ba, *cap)
+        with pytest.raises(SnakeHipError, match="no problem set"):
+            ba.solve(3)
+    ba.create(a)
+    again = _solve_all(ba, a, 3)
+    ba.close()
+    for k, (x, y) in enumerate(zip(again, want)):
+        assert np.array_equal(x, y), f"output {k} after the refused hand-overs differs from a fresh handle's"
