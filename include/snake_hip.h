@@ -790,6 +790,15 @@ SNK_API int snk_ba_sync(snk_ba* h);
 SNK_API int snk_ba_set_problem(snk_ba* h, const snk_ba_problem* problem);
 SNK_API int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count);
 
+/* Saiga's BAOptions::buildExplizitSchur: the reference's local BA asks for the explicit Schur complement
+ * (Snake/Optimizer/LocalBundleAdjustment.cpp:59), its global BA leaves it unset (Snake/Optimizer/GlobalBundleAdjustment.cpp:32-43)
+ * and gets the implicit form.  1 (the default): the reduced camera system S is formed as a dense n6 x n6 matrix.  0: S is never
+ * formed; every PCG iteration computes S p = U p + (constraint cross terms) - W V^-1 W^T p from the per-observation W blocks, so device
+ * memory grows with the observations instead of the square of the free keyframes (global BA on maps of thousands of keyframes).
+ * Takes effect at the next snk_ba_set_problem(s); in implicit mode set_problems with count > 1 fails with SNK_ERR_INVALID_ARG (a
+ * global BA is one scene) and leaves no problem set.  Any value but 0 or 1: SNK_ERR_INVALID_ARG, the handle is unchanged. */
+SNK_API int snk_ba_set_explicit_schur(snk_ba* h, int explicit_schur);
+
 /* Which form of the reduced-camera-system PCG the last successful set_problem(s) chose (read-only;
  * tests and diagnostics).  *workgroups: the workgroups of the one-launch forms, 0 for the others.
  * A refused cooperative launch during a solve turns the handle to SNK_BA_PCG_LAUNCHES. */
@@ -799,7 +808,9 @@ enum
     SNK_BA_PCG_LAUNCHES     = 1, /* multi-launch pcgl_* sequence (vectors in HBM) */
     SNK_BA_PCG_PERSIST      = 2, /* one cooperative launch, two grid barriers per iteration */
     SNK_BA_PCG_PERSIST1     = 3, /* one cooperative launch, one grid barrier, rows of S streamed */
-    SNK_BA_PCG_PERSIST_REG  = 4  /* one cooperative launch, one grid barrier, rows of S in registers */
+    SNK_BA_PCG_PERSIST_REG  = 4, /* one cooperative launch, one grid barrier, rows of S in registers */
+    SNK_BA_PCG_IMPLICIT     = 5, /* implicit Schur form (snk_ba_set_explicit_schur(h, 0)): one cooperative launch */
+    SNK_BA_PCG_IMPLICIT_LAUNCHES = 6  /* implicit Schur form, multi-launch (refused cooperative launch, recorded graphs) */
 };
 SNK_API int snk_ba_pcg_form(const snk_ba* h, int* form, int* workgroups);
 

@@ -104,6 +104,7 @@ SIGNATURES = {
     "snk_ba_create": (i32, [vp, i32, vp, C.POINTER(vp)]),
     "snk_ba_destroy": (i32, [vp]),
     "snk_ba_sync": (i32, [vp]),
+    "snk_ba_set_explicit_schur": (i32, [vp, i32]),
     "snk_ba_set_problem": (i32, [vp, vp]),
     "snk_ba_set_problems": (i32, [vp, vp, i32]),
     "snk_ba_set_outliers": (i32, [vp, i32, vp]),

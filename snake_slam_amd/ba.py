@@ -32,7 +32,7 @@ BA_RPC_DTYPE = np.dtype([("img1", "<i4"), ("img2", "<i4"), ("rel_pose", "<f8", 7
 
 
 # snk_ba_pcg_form's values (include/snake_hip.h SNK_BA_PCG_*)
-PCG_FORMS = {0: "per_problem", 1: "launches", 2: "persist", 3: "persist1", 4: "persist_reg"}
+PCG_FORMS = {0: "per_problem", 1: "launches", 2: "persist", 3: "persist1", 4: "persist_reg", 5: "implicit", 6: "implicit_launches"}
 
 
 def lba_options(max_iterations=3, max_pcg_iterations=30, pcg_tol=1e-10, huber_mono=2.1, huber_stereo=2.3, lambda_init=0.0):
@@ -65,7 +65,9 @@ def _pack(scene):
 
 
 class BARec:
-    def __init__(self, options: BaOptions | None = None, device: int = 0, stream: int | None = None):
+    def __init__(self, options: BaOptions | None = None, device: int = 0, stream: int | None = None, explicit_schur: bool = True):
+        """explicit_schur = Saiga's BAOptions::buildExplizitSchur (snk_ba_set_explicit_schur): the reference's local BA sets it
+        (LocalBundleAdjustment.cpp:59), its global BA does not (GlobalBundleAdjustment.cpp:32-43)."""
         self._lib = _lib.load()
         self.optimizationOptions = options or lba_options()
         h = C.c_void_p()
@@ -73,6 +75,8 @@ class BARec:
                    "snk_ba_create")
         self._h = h
         self._scenes = []
+        if not explicit_schur:
+            _lib.check(self._lib.snk_ba_set_explicit_schur(self._h, 0), "snk_ba_set_explicit_schur")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -681,6 +681,9 @@ class BARec
 {
    public:
     snk_ba_options optimizationOptions{3, 30, 1e-10, 2.1, 2.3, 0.0};  // LocalBundleAdjustment.cpp:47-64
+    // BAOptions::buildExplizitSchur: set by the local BA (LocalBundleAdjustment.cpp:59), left unset by the global BA
+    // (GlobalBundleAdjustment.cpp:32-43) -- false selects the implicit Schur form (snk_ba_set_explicit_schur); read by create()
+    bool buildExplizitSchur = true;
 
     explicit BARec(int device = 0) : device_(device) {}
     ~BARec() { snk_ba_destroy(h_); }
@@ -720,6 +723,7 @@ class BARec
         p.bf    = scene.bf;
         p.n_rpc = (int)scene.rel_pose_constraints.size();
         p.rpc   = scene.rel_pose_constraints.data();
+        check(snk_ba_set_explicit_schur(h_, buildExplizitSchur ? 1 : 0), "snk_ba_set_explicit_schur");
         check(snk_ba_set_problem(h_, &p), "snk_ba_set_problem");
     }
     OptimizationResults initAndSolve() { return solve(); }

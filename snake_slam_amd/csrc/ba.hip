@@ -28,6 +28,8 @@
 //   pcg_solve     one workgroup per problem : block-Jacobi PCG, vectors (and S when it fits) in LDS
 //   pcgl_*        multi-workgroup PCG for reduced systems beyond the LDS (global BA): vectors in HBM,
 //                 (row chunk x column part) matvec, fixed-order partial sums, 5 launches per iteration
+//   imp_*         implicit Schur form (snk_ba_set_explicit_schur(h, 0), one scene): S never formed; block-Jacobi PCG whose S p is a
+//                 point phase (y = V^-1 W^T p) and a camera phase (U p + constraint terms - W y) over the per-observation W
 //   update_wave / update_pass : back-substitution of the points / trial poses (SE3 exp)
 //   cost_wave     robust cost at the trial state (point_pass<1> as fallback); rpc_pass(trial) for constraints
 //   accept_pass   one workgroup per problem : fixed-order cost sums, accept / reject, lambda schedule
@@ -3030,6 +3032,8 @@ struct PcgLarge
     int persist_wgs;  // workgroups of the launch (all resident: cooperative launch)
     int persist_rows;  // pcgl_persist_reg: rows of S per workgroup (8 or 16)
     int timing;       // SNK_BA_PCG_TIMING=1 (diagnostic): workgroup 0 of pcgl_persist_reg adds its cycles per phase to ps[0..5]
+    double* y;        // implicit Schur form: [tot_pt][3] V^-1 W^T p of the point phase (ps[c] then holds p_c . (S p)_c)
+    int zero_rows;    // implicit Schur form: point_wave linearised (inactive observations have zero W rows, o_r is not written)
 };
 constexpr int PERSIST_WGS_MAX = 1024;
 // the grid barrier's words (grid_barrier_xcd); pcgl_init zeroes all BAR_WORDS of them before every PCG
@@ -3984,6 +3988,345 @@ __device__ inline void trial_pose(const Arrays& A, const Prob& pr, int i)
         se3_update(cur, A.x + pr.vec_off + c * 6, out);
 }
 
+// ---- the implicit Schur form (snk_ba_set_explicit_schur(h, 0): global BA on maps of thousands of keyframes) ----
+// S = U + (constraint cross blocks) - W V^-1 W^T is never formed.  Every PCG iteration computes S p from what the linearisation wrote:
+//   point phase   y_j = V_j^-1 sum_{o in j} W_o^T p_c(o)          thread per point, its observations in point order
+//   camera phase  q_c = U_c p_c + sum H12 p_other - sum_{o in c} W_o y_j(o)
+//                                                                  wavefront per camera, its observations in camera-list order
+// The block-Jacobi preconditioner is D_c = U_c - sum_{o in c} W_o V_j^-1 W_o^T, the diagonal block of S the dense forms read.
+// Only free cameras / free points / active observations (in front of the camera, not an outlier) contribute -- the terms the dense
+// Schur passes sum.  Which observations are active: point_wave writes zero W rows for the others (W.zero_rows = 1, schur_pass's
+// zero_rows) and no o_r; point_pass<0> leaves their W rows stale and marks them with o_r[3] = 0.  The algorithm is pcgl_*'s (x0 = 0,
+// pcgl_stop's stop rule, one counted iteration per completed update); both forms below run the same device functions in the same
+// order, so they are bit-identical to each other.
+// Every sum has a fixed order: per-thread loops, wavefront butterflies, and totals over partials in index order.  One problem.
+__device__ __forceinline__ bool imp_active(const Arrays& A, const PcgLarge& W, int go)
+{
+    return A.o_ptfree[go] && (W.zero_rows || A.o_r[(size_t)go * 4 + 3] != 0.0);
+}
+
+// D_c and its inverse (inv6_spd; its diagonal fallback is the oracle's for a block that is not positive definite).  One wavefront per camera.
+__global__ __launch_bounds__(64) void imp_precond(Arrays A, PcgLarge W)
+{
+    __shared__ double D[36];
+    const Prob pr  = A.prob[0];
+    const int c    = blockIdx.x, lane = threadIdx.x;
+    if (c >= pr.nfc) return;
+    const int j0 = A.cam_start[pr.camstart_off + c], j1 = A.cam_start[pr.camstart_off + c + 1];
+    double acc[21];
+#pragma unroll
+    for (int u = 0; u < 21; ++u) acc[u] = 0.0;
+    for (int j = j0 + lane; j < j1; j += 64)
+    {
+        const int go = pr.obs_off + A.cam_items[pr.citem_off + j];
+        if (!imp_active(A, W, go)) continue;
+        const double* Wo = A.o_W + (size_t)go * 18;
+        const double* Vp = A.Vinv + (size_t)(pr.pt_off + A.o_pt[go]) * 6;
+        double w[18], y[18];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) w[q] = Wo[q];
+        const double v0 = Vp[0], v1 = Vp[1], v2 = Vp[2], v3 = Vp[3], v4 = Vp[4], v5 = Vp[5];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+        {
+            y[a * 3]     = w[a * 3] * v0 + w[a * 3 + 1] * v1 + w[a * 3 + 2] * v2;
+            y[a * 3 + 1] = w[a * 3] * v1 + w[a * 3 + 1] * v3 + w[a * 3 + 2] * v4;
+            y[a * 3 + 2] = w[a * 3] * v2 + w[a * 3 + 1] * v4 + w[a * 3 + 2] * v5;
+        }
+        int u = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b, ++u) acc[u] += y[a * 3] * w[b * 3] + y[a * 3 + 1] * w[b * 3 + 1] + y[a * 3 + 2] * w[b * 3 + 2];
+    }
+#pragma unroll
+    for (int u = 0; u < 21; ++u) acc[u] = wave_sum64(acc[u]);
+    if (lane == 0)
+    {
+        const double* U = A.U + (size_t)(pr.cam_off + c) * 36;
+        int u = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b, ++u)
+            {
+                const double v = U[a * 6 + b] - acc[u];
+                D[a * 6 + b] = v;
+                D[b * 6 + a] = v;
+            }
+        inv6_spd(D, 6, W.Minv + (size_t)(pr.cam_off + c) * 36);
+    }
+}
+
+// pcgl_init with the preconditioner of imp_precond: r = rhs, x = 0, z = p = Minv r, partial r.r / r.z per 64 cameras
+__global__ __launch_bounds__(64) void imp_init(Arrays A, Opt O, PcgLarge W)
+{
+    const Prob pr = A.prob[0];
+    const int c   = blockIdx.x * 64 + threadIdx.x;
+    double rr = 0.0, rz = 0.0;
+    if (c < pr.nfc)
+    {
+        const double* Mi = W.Minv + (size_t)(pr.cam_off + c) * 36;
+        double rv[6];
+        for (int a = 0; a < 6; ++a)
+        {
+            rv[a] = A.rhs[pr.vec_off + c * 6 + a];
+            rr += rv[a] * rv[a];
+        }
+        for (int a = 0; a < 6; ++a)
+        {
+            double sacc = 0.0;
+            for (int b = 0; b < 6; ++b) sacc += Mi[a * 6 + b] * rv[b];
+            const int q = pr.vec_off + c * 6 + a;
+            W.r[q] = rv[a];
+            W.z[q] = sacc;
+            W.p[q] = sacc;
+            A.x[q] = 0.0;
+            rz += rv[a] * sacc;
+        }
+    }
+    rr = wave_sum64(rr);
+    rz = wave_sum64(rz);
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < BAR_WORDS; i += 64) W.bar[i] = 0u;  // the grid barrier's flags of imp_persist
+    if (threadIdx.x == 0)
+    {
+        W.prr[blockIdx.x] = rr;  // parity 0
+        W.prz[blockIdx.x] = rz;
+        if (blockIdx.x == 0)
+        {
+            W.scal[1] = 0.0;   // done
+            W.scal[0] = -1.0;  // stop2: latched by imp_latch of iteration 0
+        }
+    }
+}
+
+// point phase, point pt: y = V^-1 sum W^T p (constant points: no y, nobody reads it)
+__device__ __forceinline__ void imp_point_one(const Arrays& A, const PcgLarge& W, const Prob& pr, int pt)
+{
+    const int gp = pr.pt_off + pt;
+    if (A.pt_const[gp]) return;
+    const int s0 = A.pt_start[pr.ptstart_off + pt], s1 = A.pt_start[pr.ptstart_off + pt + 1];
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+    for (int s = s0; s < s1; ++s)
+    {
+        const int go = pr.obs_off + s;
+        const int c  = A.o_cam[go];
+        if (c < 0 || (!W.zero_rows && A.o_r[(size_t)go * 4 + 3] == 0.0)) continue;
+        const double* Wo = A.o_W + (size_t)go * 18;
+        const double* pc = W.p + pr.vec_off + c * 6;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+        {
+            const double pa = pc[a];
+            t0 += Wo[a * 3] * pa;
+            t1 += Wo[a * 3 + 1] * pa;
+            t2 += Wo[a * 3 + 2] * pa;
+        }
+    }
+    const double* Vp = A.Vinv + (size_t)gp * 6;
+    double* y        = W.y + (size_t)gp * 3;
+    y[0] = Vp[0] * t0 + Vp[1] * t1 + Vp[2] * t2;
+    y[1] = Vp[1] * t0 + Vp[3] * t1 + Vp[4] * t2;
+    y[2] = Vp[2] * t0 + Vp[4] * t1 + Vp[5] * t2;
+}
+
+// camera phase, camera c, one wavefront: Ap_c = U_c p_c + constraint cross terms - sum W y; ps[c] = p_c . Ap_c
+__device__ __forceinline__ void imp_cam_one(const Arrays& A, const PcgLarge& W, const Prob& pr, int c, int lane)
+{
+    const int j0 = A.cam_start[pr.camstart_off + c], j1 = A.cam_start[pr.camstart_off + c + 1];
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int j = j0 + lane; j < j1; j += 64)
+    {
+        const int go = pr.obs_off + A.cam_items[pr.citem_off + j];
+        if (!imp_active(A, W, go)) continue;
+        const double* Wo = A.o_W + (size_t)go * 18;
+        const double* y  = W.y + (size_t)(pr.pt_off + A.o_pt[go]) * 3;
+        const double y0 = y[0], y1 = y[1], y2 = y[2];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) t[a] += Wo[a * 3] * y0 + Wo[a * 3 + 1] * y1 + Wo[a * 3 + 2] * y2;
+    }
+    double ta = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+    {
+        const double s = wave_sum64(t[a]);
+        if (lane == a) ta = s;
+    }
+    double pq = 0.0;
+    if (lane < 6)
+    {
+        const int a      = lane;
+        const double* U  = A.U + (size_t)(pr.cam_off + c) * 36 + a * 6;
+        const double* pc = W.p + pr.vec_off + c * 6;
+        double v = 0.0;
+        for (int b = 0; b < 6; ++b) v += U[b] * pc[b];
+        if (pr.n_rpc > 0)  // S[c(img1), c(img2)] = H12, S[c(img2), c(img1)] = H12^T (schur_pass's blocks), in cam_rpc_items order
+        {
+            const int r0 = A.cam_rpc_start[pr.camrpc_off + c], r1 = A.cam_rpc_start[pr.camrpc_off + c + 1];
+            for (int q = r0; q < r1; ++q)
+            {
+                const int item  = A.cam_rpc_items[q];
+                const int k     = item >> 1, side = item & 1;
+                const RpcMeta& m = A.rpc_meta[pr.rpc_off + k];
+                const int other = side ? m.c1 : m.c2;
+                if (other < 0) continue;
+                const double* H  = A.rpc_out + (size_t)(pr.rpc_off + k) * RPC_STRIDE + 35;
+                const double* po = W.p + pr.vec_off + other * 6;
+                for (int b = 0; b < 6; ++b) v += (side ? H[b * 6 + a] : H[a * 6 + b]) * po[b];
+            }
+        }
+        v -= ta;
+        W.Ap[pr.vec_off + c * 6 + a] = v;
+        pq = pc[a] * v;
+    }
+    const double d = ((((__shfl(pq, 0) + __shfl(pq, 1)) + __shfl(pq, 2)) + __shfl(pq, 3)) + __shfl(pq, 4)) + __shfl(pq, 5);
+    if (lane == 0) W.ps[c] = d;
+}
+
+// p.Ap over every camera in index order (the same value in every lane and every wavefront that asks)
+__device__ __forceinline__ double imp_pap(const PcgLarge& W, const Prob& pr, int lane)
+{
+    return sum_partials_wave(W.ps, pr.nfc, lane);
+}
+
+// update, 64 cameras of block g: x += alpha p, r -= alpha Ap, z = Minv r; partial r.r / r.z of the next parity (pcgl_update's arithmetic)
+__device__ __forceinline__ void imp_update_blk(const Arrays& A, const PcgLarge& W, const Prob& pr, int k, int g, int lane, double pAp)
+{
+    const int g_used = (pr.nfc + 63) / 64;
+    const double rz    = sum_partials(W.prz + (size_t)(k & 1) * W.G, g_used);
+    const double alpha = rz / pAp;
+    const int c = g * 64 + lane;
+    double rr = 0.0, rzn = 0.0;
+    if (c < pr.nfc)
+    {
+        const double* Mi = W.Minv + (size_t)(pr.cam_off + c) * 36;
+        double rv[6];
+        for (int a = 0; a < 6; ++a)
+        {
+            const int q = pr.vec_off + c * 6 + a;
+            A.x[q] += alpha * W.p[q];
+            rv[a]  = W.r[q] - alpha * W.Ap[q];
+            W.r[q] = rv[a];
+            rr += rv[a] * rv[a];
+        }
+        for (int a = 0; a < 6; ++a)
+        {
+            double sacc = 0.0;
+            for (int b = 0; b < 6; ++b) sacc += Mi[a * 6 + b] * rv[b];
+            W.z[pr.vec_off + c * 6 + a] = sacc;
+            rzn += rv[a] * sacc;
+        }
+    }
+    rr  = wave_sum64(rr);
+    rzn = wave_sum64(rzn);
+    if (lane == 0)
+    {
+        W.prr[(size_t)((k + 1) & 1) * W.G + g] = rr;
+        W.prz[(size_t)((k + 1) & 1) * W.G + g] = rzn;
+    }
+}
+
+// direction, 64 cameras of block g: p = z + beta p
+__device__ __forceinline__ void imp_direction_blk(const PcgLarge& W, const Prob& pr, int k, int g, int lane)
+{
+    const int g_used = (pr.nfc + 63) / 64;
+    const double rz   = sum_partials(W.prz + (size_t)(k & 1) * W.G, g_used);
+    const double rzn  = sum_partials(W.prz + (size_t)((k + 1) & 1) * W.G, g_used);
+    const double beta = rzn / rz;
+    const int c       = g * 64 + lane;
+    if (c < pr.nfc)
+        for (int a = 0; a < 6; ++a)
+        {
+            const int q = pr.vec_off + c * 6 + a;
+            W.p[q]      = W.z[q] + beta * W.p[q];
+        }
+}
+
+// the multi-launch form: imp_point, imp_cam, imp_update, imp_direction, imp_latch per iteration (pcgl_stop: scal latched by imp_latch)
+__global__ __launch_bounds__(256) void imp_point(Arrays A, Opt O, PcgLarge W, int k)
+{
+    const Prob pr = A.prob[0];
+    if (pcgl_stop(W, pr, O, 0, k, (pr.nfc + 63) / 64)) return;
+    const int pt = blockIdx.x * 256 + threadIdx.x;
+    if (pt < pr.np) imp_point_one(A, W, pr, pt);
+}
+
+__global__ __launch_bounds__(64) void imp_cam(Arrays A, Opt O, PcgLarge W, int k)
+{
+    const Prob pr = A.prob[0];
+    if ((int)blockIdx.x >= pr.nfc || pcgl_stop(W, pr, O, 0, k, (pr.nfc + 63) / 64)) return;
+    imp_cam_one(A, W, pr, blockIdx.x, threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void imp_update(Arrays A, Opt O, PcgLarge W, int k)
+{
+    const Prob pr = A.prob[0];
+    if ((int)blockIdx.x >= (pr.nfc + 63) / 64 || pcgl_stop(W, pr, O, 0, k, (pr.nfc + 63) / 64)) return;
+    const double pAp = imp_pap(W, pr, threadIdx.x);
+    if (pAp <= 0.0) return;  // imp_latch latches the break
+    imp_update_blk(A, W, pr, k, blockIdx.x, threadIdx.x, pAp);
+}
+
+__global__ __launch_bounds__(64) void imp_direction(Arrays A, Opt O, PcgLarge W, int k)
+{
+    const Prob pr = A.prob[0];
+    if ((int)blockIdx.x >= (pr.nfc + 63) / 64 || pcgl_stop(W, pr, O, 0, k, (pr.nfc + 63) / 64)) return;
+    if (imp_pap(W, pr, threadIdx.x) <= 0.0) return;
+    imp_direction_blk(W, pr, k, blockIdx.x, threadIdx.x);
+}
+
+// one wavefront: latches stop2 (iteration 0), convergence and the p.Ap <= 0 break; counts the iteration
+__global__ __launch_bounds__(64) void imp_latch(Arrays A, Opt O, PcgLarge W, int k)
+{
+    const Prob pr = A.prob[0];
+    if (pr.n6 == 0 || W.scal[1] != 0.0) return;
+    const int g_used   = (pr.nfc + 63) / 64;
+    const double rn2   = sum_partials(W.prr + (size_t)(k & 1) * W.G, g_used);
+    const double stop2 = k == 0 ? O.pcg_tol * O.pcg_tol * rn2 : W.scal[0];
+    const bool stop    = rn2 <= stop2;
+    const double pAp   = stop ? 1.0 : imp_pap(W, pr, threadIdx.x);
+    if (threadIdx.x != 0) return;
+    if (k == 0) W.scal[0] = stop2;
+    if (stop || pAp <= 0.0)
+        W.scal[1] = 1.0;
+    else
+        A.state[0].pcg_iters += 1;
+}
+
+// the one-launch form (cooperative: all workgroups resident): the phases of an iteration separated by grid barriers, every
+// workgroup re-deriving the stop decisions from the same partial sums (pcgl_persist's scheme); a wavefront stands for one
+// 64-thread block of the multi-launch kernels
+constexpr int IMP_THREADS = 256;
+__global__ __launch_bounds__(IMP_THREADS) void imp_persist(Arrays A, Opt O, PcgLarge W)
+{
+    const Prob pr  = A.prob[0];
+    const int lane = threadIdx.x & 63;
+    const int gw   = blockIdx.x * (IMP_THREADS / 64) + (threadIdx.x >> 6), nw = gridDim.x * (IMP_THREADS / 64);
+    const int g_used = (pr.nfc + 63) / 64;
+    unsigned phase   = 0;
+    int iters        = 0;
+    double stop2     = 0.0;
+    for (int k = 0; k < O.max_pcg; ++k)
+    {
+        const double rn2 = sum_partials(W.prr + (size_t)(k & 1) * W.G, g_used);
+        if (k == 0) stop2 = O.pcg_tol * O.pcg_tol * rn2;
+        if (pr.n6 == 0 || rn2 <= stop2) break;
+        for (int pt = blockIdx.x * IMP_THREADS + threadIdx.x; pt < pr.np; pt += gridDim.x * IMP_THREADS) imp_point_one(A, W, pr, pt);
+        grid_barrier_xcd(W.bar, gridDim.x, phase);
+        for (int c = gw; c < pr.nfc; c += nw) imp_cam_one(A, W, pr, c, lane);
+        grid_barrier_xcd(W.bar, gridDim.x, phase);
+        const double pAp = imp_pap(W, pr, lane);
+        if (pAp <= 0.0) break;
+        for (int g = gw; g < g_used; g += nw) imp_update_blk(A, W, pr, k, g, lane, pAp);
+        grid_barrier_xcd(W.bar, gridDim.x, phase);
+        for (int g = gw; g < g_used; g += nw) imp_direction_blk(W, pr, k, g, lane);
+        grid_barrier_xcd(W.bar, gridDim.x, phase);
+        ++iters;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) A.state[0].pcg_iters += iters;
+}
+
 // update_wave's workgroups behind the point work items (blockIdx.x >= wave_blocks): the trial poses, 256 images each
 __device__ inline void trial_poses_block(const Arrays& A, int pb, int block)
 {
@@ -4356,6 +4699,8 @@ struct snk_ba : HandleBase
     bool point_wave_ok = false;  // every problem has a point_wave work list (no point with > 64 observations)
     PcgLarge pcgw{};     // work arrays of the multi-workgroup PCG (only when the reduced system exceeds the LDS)
     bool pcg_large = false;
+    int explicit_schur = 1;  // snk_ba_set_explicit_schur: the form the next hand-over builds
+    bool implicit = false;   // the current problem set runs the implicit Schur form (imp_*): no S, no camera-pair lists
     Arrays arr{};
     std::vector<int> orig_off, orig_n;
     std::map<int, hipGraphExec_t> graphs;  // LM launch sequence captured per iteration count
@@ -4806,6 +5151,10 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         }
     } no_set_on_failure{h};
     SNK_REQUIRE(count >= 1 && count <= 65535 && problems != nullptr, "count must be 1..65535");
+    // implicit Schur form (snk_ba_set_explicit_schur): one scene; nothing below sized (free cameras)^2 is built or allocated
+    const bool imp = h->explicit_schur == 0;
+    SNK_REQUIRE(!imp || count == 1, "the implicit Schur form takes one problem (snk_ba_set_explicit_schur)");
+    h->implicit = imp;
     for (int b = 0; b < count; ++b)  // the packed observation records hold the image index in 15 bits (SetObs)
         SNK_REQUIRE(problems[b].n_img <= SET_MAX_IMG, "a problem has more than 32767 images");
     SNK_HIP_CHECK(hipSetDevice(h->device));
@@ -4860,8 +5209,8 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
             t_blk += nfc * nfc + 1;
             sets_likely |= problems[b].n_pt >= 8000;
         }
-        cblkstart.reserve(t_blk);
-        if (sets_likely) setpts.reserve(t_pt), cblkitems.reserve(2 * t_obs), ccitems.reserve(t_obs);
+        if (!imp) cblkstart.reserve(t_blk);
+        if (sets_likely && !imp) setpts.reserve(t_pt), cblkitems.reserve(2 * t_obs), ccitems.reserve(t_obs);
     }
     h->orig_off.assign((size_t)count, 0);
     h->orig_n.assign((size_t)count, 0);
@@ -5297,7 +5646,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         // point-major Schur pass: points grouped by camera set, work items of <= SET_CHUNK points, per-block lists of
         // the partial sums they produce
         {
-            const size_t nb = (size_t)nfc * nfc;
+            const size_t nb = imp ? 0 : (size_t)nfc * nfc;
             // camera set -> group: a hash of the signature finds the candidate, the stored signature confirms it (a std::map keyed by
             // the vectors themselves was 60 ns per point, a third of a batch hand-over's list time)
             std::unordered_multimap<unsigned long long, int> gid;
@@ -5322,7 +5671,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
             // (0.8 MB of records alone) was a quarter of the 0.9 ms a scene hand-over cost.  Built for batches and for big
             // single scenes (global BA); forced when the threshold is lowered by the environment (tests).
             static const bool sets_forced = getenv("SNK_BA_SCHUR_SET_MIN_ITEMS") != nullptr;
-            bool ok = nfc > 0 && (count >= 8 || P.n_pt >= 8000 || sets_forced);
+            bool ok = !imp && nfc > 0 && (count >= 8 || P.n_pt >= 8000 || sets_forced);
             // points that produce no Schur products (constant points, points seen by constant cameras only) still need their
             // linearisation (cost, V, b_p): they form groups of their own, keyed by their run length, with no pairs
             std::vector<int> plain_key;
@@ -5555,7 +5904,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         if (nfc > BE_MAX_CAMS) dev_entries_ok = false;
         ent_bound[(size_t)b] = B.ent_bound;
         pr.blkstart_off = blkstart_total;
-        blkstart_total += nfc * nfc + 1;
+        if (!imp) blkstart_total += nfc * nfc + 1;
         mark(3);
         mark(4);
         // point-major Schur pass (built in pass 3 with problem-local offsets): append, relocating by the running totals
@@ -5625,13 +5974,14 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
             const int item_base = (int)camrpcitems.size();
             std::vector<int> items((size_t)cs[(size_t)nfc]), fill(cs.begin(), cs.end() - 1);
             // the per-block chains are only read for problems that HAVE constraints: the others advance the offset and write nothing
-            std::vector<int> brpc(mine.empty() ? 0 : (size_t)nfc * nfc, 0), nxt(mine.size(), 0);
+            // (implicit form: no per-block chains -- its camera phase walks the per-camera lists)
+            std::vector<int> brpc(mine.empty() || imp ? 0 : (size_t)nfc * nfc, 0), nxt(mine.size(), 0);
             for (int k = 0; k < (int)mine.size(); ++k)
             {
                 const RpcMeta& m = mine[(size_t)k];
                 if (m.c1 >= 0) items[(size_t)fill[(size_t)m.c1]++] = k * 2;
                 if (m.c2 >= 0) items[(size_t)fill[(size_t)m.c2]++] = k * 2 + 1;
-                if (m.c1 >= 0 && m.c2 >= 0)
+                if (m.c1 >= 0 && m.c2 >= 0 && !imp)
                 {
                     // the upper block (lo, hi) holds J(lo)^T J(hi): H12 when img1 is `lo`, its transpose otherwise
                     const int lo = std::min(m.c1, m.c2), hi = std::max(m.c1, m.c2);
@@ -5642,12 +5992,12 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
             }
             for (int c = 0; c <= nfc; ++c) camrpcstart.push_back(item_base + cs[(size_t)c]);
             camrpcitems.insert(camrpcitems.end(), items.begin(), items.end());
-            if (!mine.empty())
+            if (!mine.empty() && !imp)
             {
                 blkrpc.resize(blkrpc_logical, 0);  // zeros for the problems without constraints in front of this one
                 blkrpc.insert(blkrpc.end(), brpc.begin(), brpc.end());
             }
-            blkrpc_logical += (size_t)nfc * nfc;
+            if (!imp) blkrpc_logical += (size_t)nfc * nfc;
             rpcnext.insert(rpcnext.end(), nxt.begin(), nxt.end());
             rpcmeta.insert(rpcmeta.end(), mine.begin(), mine.end());
         }
@@ -5658,7 +6008,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         cam_off += nfc;
         orig_off += P.n_obs;
         vec_off += pr.n6;
-        s_off += (long long)pr.n6 * pr.n6;
+        if (!imp) s_off += (long long)pr.n6 * pr.n6;
         max_np  = std::max(max_np, P.n_pt);
         max_ni  = std::max(max_ni, P.n_img);
         max_nfc = std::max(max_nfc, nfc);
@@ -5715,7 +6065,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
     const size_t pcg_lds = (size_t)max_n6 * 9 * 8 + (size_t)max_nfc * 36 * 8;
     // S (and the vectors) of the largest problem fit one workgroup's LDS -> one workgroup per problem;
     // otherwise the multi-workgroup PCG (measured: 120 keyframes 38 ms -> 9 ms, 600 keyframes 21 ms)
-    h->pcg_large = pcg_lds + (size_t)max_n6 * max_n6 * 8 > 158 * 1024;
+    h->pcg_large = !imp && pcg_lds + (size_t)max_n6 * max_n6 * 8 > 158 * 1024;
     h->probs.assign(probs.begin(), probs.end());
     h->count = count;
     h->tot_img = img_off; h->tot_pt = pt_off; h->tot_obs = obs_off; h->tot_cam = cam_off; h->tot_orig = orig_off;
@@ -5727,7 +6077,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
 
     // block entries: on the device when every problem qualifies, by the host builder otherwise
     static const bool host_entries = getenv("SNK_BA_HOST_ENTRIES") != nullptr;  // A/B and tests
-    bool dev_entries = dev_entries_ok && !host_entries;
+    bool dev_entries = dev_entries_ok && !host_entries && !imp;
     if (dev_entries)
     {
         // The device builder counts into nfc x chunks x nfc ints per problem -- quadratic in the free cameras.  A global BA with
@@ -5754,7 +6104,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
             max_be_waves = std::max(max_be_waves, pr.nfc * pr.be_nch);
         }
     }
-    else
+    else if (!imp)
     {
         long long bound = 0;
         for (int b = 0; b < count; ++b) bound += ent_bound[(size_t)b];
@@ -5955,6 +6305,49 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
             (void)hipGetLastError();
         }
     }
+    else if (imp)
+    {
+        // the implicit form's PCG (imp_*): the vectors, the preconditioner blocks, the point phase's y, per-camera p.Ap, the
+        // partial sums of 64 cameras each and the grid barrier's words -- O(observations + keyframes), nothing (free cameras)^2
+        PcgLarge& W = h->pcgw;
+        W         = PcgLarge{};
+        W.G       = std::max(1, ceil_div(max_nfc, 64));
+        W.B       = 1;
+        W.parts   = 1;
+        W.tot_vec = vec_off;
+        const size_t nv = (size_t)std::max(vec_off, 1), ng = (size_t)W.G;
+        const size_t doubles = 4 * nv + (size_t)std::max(cam_off, 1) * 36 + (size_t)std::max(cam_off, 1) + 5 * ng + 4 + npt * 3 +
+                               (size_t)PERSIST_WGS_MAX + 8;
+        RS(d_pcgw, doubles * 8);
+        double* w = h->d_pcgw.as<double>();
+        W.r = w;     w += nv;
+        W.z = w;     w += nv;
+        W.p = w;     w += nv;
+        W.Ap = w;    w += nv;
+        W.Minv = w;  w += (size_t)std::max(cam_off, 1) * 36;
+        W.ps = w;    w += (size_t)std::max(cam_off, 1);
+        W.prr = w;   w += 2 * ng;
+        W.prz = w;   w += 2 * ng;
+        W.ppap = w;  w += ng;
+        W.scal = w;  w += 4;
+        W.y = w;     w += npt * 3;
+        W.bar = reinterpret_cast<unsigned*>(w);  // (PERSIST_WGS_MAX + 8) doubles = 2064 words >= BAR_WORDS
+        // one cooperative launch when every workgroup can be resident (SNK_BA_PCGL_LAUNCHES=1 or a refused launch: the multi-launch form);
+        // enough workgroups for a point per thread or a camera per wavefront, at most one per compute unit (the barrier's cost grows with them)
+        W.persist_wgs = 0;
+        static const bool launches_env = getenv("SNK_BA_PCGL_LAUNCHES") != nullptr;
+        hipDeviceProp_t prop;
+        int coop = 0, resident = 0;
+        if (!launches_env && max_nfc > 0 && hipGetDeviceProperties(&prop, h->device) == hipSuccess &&
+            hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, h->device) == hipSuccess && coop &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, reinterpret_cast<const void*>(imp_persist), IMP_THREADS, 0) == hipSuccess && resident >= 1)
+        {
+            const int want = std::max(16, std::max(ceil_div(max_np, IMP_THREADS), ceil_div(max_nfc, IMP_THREADS / 64)));
+            const int wgs  = std::min(PERSIST_WGS_MAX, snk_env_int("SNK_BA_PERSIST_WGS", std::min(prop.multiProcessorCount, want)));
+            W.persist_wgs  = std::min(wgs, resident * prop.multiProcessorCount);
+        }
+        (void)hipGetLastError();
+    }
 #undef RS
 #undef UP
     // ... and the buffers that start as zeros are entries of the same table (source NULL): nine fill launches of ~5 us each
@@ -6090,7 +6483,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
     // batches that will run the point-major kernels never read the block entries (SNK_BA_CHECK_LISTS=1 builds and checks them anyway)
     static const bool check_lists_be = getenv("SNK_BA_CHECK_LISTS") != nullptr;
     const bool skip_entries = dev_entries && count >= 16 && ba_sets_will_run(h) && !check_lists_be;
-    h->blk_built = !skip_entries;
+    h->blk_built = !skip_entries && !imp;
     if (dev_entries && !skip_entries)
     {
         if (max_be_waves > 0)
@@ -6197,6 +6590,14 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
     return SNK_OK;
 }
 
+int snk_ba_set_explicit_schur(snk_ba* h, int explicit_schur)
+{
+    SNK_REQUIRE(h != nullptr, "ba is NULL");
+    SNK_REQUIRE(explicit_schur == 0 || explicit_schur == 1, "explicit_schur must be 0 or 1");
+    h->explicit_schur = explicit_schur;  // read by the next snk_ba_set_problem(s)
+    return SNK_OK;
+}
+
 int snk_ba_set_problem(snk_ba* h, const snk_ba_problem* problem)
 {
     return snk_ba_set_problems(h, problem, 1);
@@ -6207,7 +6608,14 @@ int snk_ba_pcg_form(const snk_ba* h, int* form, int* workgroups)
     SNK_REQUIRE(h != nullptr && form != nullptr && workgroups != nullptr, "bad arguments");
     SNK_REQUIRE(h->count > 0, "no problem set");
     const PcgLarge& W = h->pcgw;
-    if (!h->pcg_large)
+    if (h->implicit)
+    {
+        if (W.persist_wgs > 0)
+            *form = SNK_BA_PCG_IMPLICIT, *workgroups = W.persist_wgs;
+        else
+            *form = SNK_BA_PCG_IMPLICIT_LAUNCHES, *workgroups = 0;
+    }
+    else if (!h->pcg_large)
         *form = SNK_BA_PCG_PER_PROBLEM, *workgroups = 0;
     else if (W.persist_wgs <= 0 || h->count != 1)
         *form = SNK_BA_PCG_LAUNCHES, *workgroups = 0;
@@ -6299,8 +6707,8 @@ static int enqueue_lm(snk_ba* h, int iterations, Launcher& L, bool only_marked =
         static const bool no_mfma  = getenv("SNK_BA_NO_SCHUR_MFMA") != nullptr;   // A/B: the vector-ALU form (schur_set)
         static const bool no_fused = getenv("SNK_BA_NO_SCHUR_FUSED") != nullptr;  // A/B: point_wave + schur_mfma through W in HBM
         // (the whole batch decides, not the range of a chain: the hand-over left out the block entries on the same answer)
-        const bool use_set = ba_sets_will_run(h);
-        if (!use_set && !h->blk_built)
+        const bool use_set = !h->implicit && ba_sets_will_run(h);
+        if (!use_set && !h->blk_built && !h->implicit)
         {
             set_error("bundle adjustment: the block-major pass was chosen but the hand-over did not build its lists (internal)");
             return SNK_ERR_HIP;
@@ -6344,6 +6752,9 @@ static int enqueue_lm(snk_ba* h, int iterations, Launcher& L, bool only_marked =
             }
             else
                 LAUNCH(cam_pass<256>, dim3(h->max_nfc, B), dim3(256), 0, A, O, 0, B);
+            if (h->implicit)
+                ;  // no S: the implicit PCG below works from W, V^-1 and U
+            else
             {
                 const int nbx = ceil_div(h->max_nfc * h->max_nfc, 4);  // schur_pass: a block per wavefront
                 const int nbs = ceil_div(h->max_nfc * h->max_nfc, 4 * SUM_NB);  // schur_sum: SUM_NB blocks per wavefront
@@ -6377,7 +6788,44 @@ static int enqueue_lm(snk_ba* h, int iterations, Launcher& L, bool only_marked =
                 }
             }
             static const bool pcg_in_lds = getenv("SNK_BA_PCG_LDS") != nullptr;  // A/B: S in LDS (pcg_solve<true>) also for local-BA sizes
-            if (!h->pcg_large && h->max_n6 <= 128 && !O.pcg_general && !pcg_in_lds)
+            if (h->implicit)
+            {
+                PcgLarge W  = h->pcgw;
+                W.zero_rows = h->point_wave_ok && !no_wave ? 1 : 0;
+                LAUNCH(imp_precond, dim3(h->max_nfc), dim3(64), 0, A, W);
+                LAUNCH(imp_init, dim3(W.G), dim3(64), 0, A, O, W);
+                bool persisted = false;
+                if (W.persist_wgs > 0 && L.graph == nullptr && L.err == hipSuccess)
+                {
+                    static const bool fail_hook = getenv("SNK_BA_PERSIST_FAIL") != nullptr;  // tests: the runtime refuses the cooperative launch
+                    L.cooperative = true;
+                    if (fail_hook)
+                        L.cooperative = false, L.err = hipErrorCooperativeLaunchTooLarge;
+                    else
+                        LAUNCH(imp_persist, dim3(W.persist_wgs), dim3(IMP_THREADS), 0, A, O, W);
+                    persisted = L.err == hipSuccess;
+                    if (!persisted)
+                    {
+                        // refused (see the dense forms below): nothing ran, imp_init's state is where the launch sequence starts from too
+                        if (getenv("SNK_DEBUG")) fprintf(stderr, "snake_hip: cooperative implicit PCG launch refused (%s); multi-launch PCG\n", hipGetErrorString(L.err));
+                        (void)hipGetLastError();
+                        L.err               = hipSuccess;
+                        h->pcgw.persist_wgs = 0;
+                    }
+                }
+                static const bool debug = getenv("SNK_DEBUG") != nullptr;  // tests: which form an LM iteration enqueued (or recorded)
+                if (debug) fprintf(stderr, "snake_hip: implicit PCG %s\n", persisted ? "cooperative" : L.graph ? "multi-launch (graph)" : "multi-launch");
+                if (!persisted)
+                    for (int k = 0; k < O.max_pcg; ++k)
+                    {
+                        LAUNCH(imp_point, dim3(std::max(1, ceil_div(h->max_np, 256))), dim3(256), 0, A, O, W, k);
+                        LAUNCH(imp_cam, dim3(h->max_nfc), dim3(64), 0, A, O, W, k);
+                        LAUNCH(imp_update, dim3(W.G), dim3(64), 0, A, O, W, k);
+                        LAUNCH(imp_direction, dim3(W.G), dim3(64), 0, A, O, W, k);
+                        LAUNCH(imp_latch, dim3(1), dim3(64), 0, A, O, W, k);
+                    }
+            }
+            else if (!h->pcg_large && h->max_n6 <= 128 && !O.pcg_general && !pcg_in_lds)
                 LAUNCH(pcg_small, dim3(B), dim3(PCG_THREADS), ((size_t)h->max_n6 * 9 + (size_t)h->max_nfc * 72) * 8 + 8192, A, O);
             else if (!h->pcg_large)
                 if (s_in_lds)
@@ -6480,9 +6928,10 @@ int snk_ba_solve_async(snk_ba* h, int iterations)
     static const bool graph_first = getenv("SNK_BA_GRAPH_FIRST") != nullptr;
     Launcher direct;
     direct.st = h->stream;
-    // a cooperative launch is not a graph node: scenes solved by the one-launch PCG (global BA) always take plain launches -- seven per
-    // LM iteration there, against milliseconds of work
-    if (no_graph || iterations == 0 || (h->pcg_large && h->pcgw.persist_wgs > 0 && h->count == 1)) return enqueue_lm(h, iterations, direct);
+    // a cooperative launch is not a graph node: scenes solved by a one-launch PCG (global BA, dense or implicit) always take plain
+    // launches -- seven per LM iteration there, against milliseconds of work
+    if (no_graph || iterations == 0 || ((h->pcg_large || h->implicit) && h->pcgw.persist_wgs > 0 && h->count == 1))
+        return enqueue_lm(h, iterations, direct);
     auto it = h->graphs.find(iterations);
     if (it == h->graphs.end())
     {
