@@ -27,7 +27,8 @@ HIP_FLAGS = [
 ]
 # Per-source additions (appended, so they win).  ba.hip: bundle adjustment is specified by a tolerance (1e-5 RMSE, only
 # summation orders ever differed from the oracle's) and its kernels are bound by fp64 issue slots -- a * b + c as one
-# v_fma_f64 halves them.  Everything that must match the oracle bit for bit keeps -ffp-contract=off.
+# v_fma_f64 halves them.  ba_handover.hip holds the kernels of the scene hand-over, which were part of ba.hip: the same flag, so that they
+# compile as they did there.  Everything that must match the oracle bit for bit keeps -ffp-contract=off.
 # pose.hip (round 4): pose refinement is specified by a tolerance too (<= 1e-9 on the pose against the oracle; the sums already differ
 # from the oracle's by their order), its kernel is 62 % VALU-issue bound in fp64 multiply-add chains.  The flag covers the whole file: the
 # glue kernels backproject_kernel (world points of the next frame) and gather_matches_kernel's weights are fp64 multiply-add chains too and
@@ -38,7 +39,7 @@ HIP_FLAGS = [
 # literals; the machine-level loop-invariant code motion hoists ~60 of their v_mov pairs in front of the iteration loops, the kernel
 # sits at 254 registers and the allocator then SPILLS three of those constants to scratch (28-36 bytes per lane, reloaded in the loop
 # where a v_mov would do).  Without the pass: 180 registers, no scratch (tests/test_kernel_resources.py holds that).
-HIP_FLAGS_PER_SOURCE = {"ba.hip": ["-ffp-contract=fast"], "pose.hip": ["-mllvm", "-disable-machine-licm"]}  # pose.hip: contraction by pragma inside the file
+HIP_FLAGS_PER_SOURCE = {"ba.hip": ["-ffp-contract=fast"], "ba_handover.hip": ["-ffp-contract=fast"], "pose.hip": ["-mllvm", "-disable-machine-licm"]}  # pose.hip: contraction by pragma inside the file
 
 
 def _newer(target: Path, deps) -> bool:

@@ -34,20 +34,17 @@
 //   cost_wave     robust cost at the trial state (point_pass<1> as fallback); rpc_pass(trial) for constraints
 //   accept_pass   one workgroup per problem : fixed-order cost sums, accept / reject, lambda schedule
 //   point_pass<2> chi-square per caller observation (snk_ba_residuals)
-#include "common.hpp"
+//
+// The scene hand-over (snk_ba_set_problems: the caller's scenes -> the device lists these kernels walk, and the kernels that derive
+// lists on the device) is ba_handover.hip; ba_types.hpp holds what the two files share.  This file keeps the one decision of a
+// hand-over that is solver policy: the PCG form and its work arrays (ba_plan_pcg, beside the kernels whose occupancy it asks for).
+#include "ba_types.hpp"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
-#include <chrono>
 #include <map>
-#include <unordered_map>
 #include <tuple>
 #include <utility>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 // This file is compiled with -ffp-contract=fast (snake_slam_amd/build.py): BA is specified by a tolerance, its kernels
@@ -70,98 +67,9 @@
 
 namespace snk
 {
+using namespace ba;
 namespace
 {
-struct Prob
-{
-    int ni, np, no;     // images, points, valid observations (sorted by point)
-    int nfc, n6;        // free cameras, 6 * nfc
-    int img_off, pt_off, obs_off, cam_off;
-    int ptstart_off, camstart_off, citem_off, blkstart_off, ent_off;
-    int vec_off;        // n6-vectors (rhs, x)
-    long long s_off;    // S (n6 * n6 doubles)
-    int orig_off;       // first caller-order observation of this problem
-    int n_wv;           // wavefront work items of point_wave (whole points, <= 64 observations each); 0: not available
-    int wv_off;
-    int n_rpc;          // valid relative pose constraints (IMU scenes)
-    int rpc_off;        // into rpc_meta / rpc_out
-    int camrpc_off;     // into cam_rpc_start (nfc + 1 entries per problem)
-    int n_set;          // work items of schur_set (0: not available for this problem)
-    int set_off;        // into set_items
-    int cblk_off;       // into cblk_start (nfc * nfc + 1 entries per problem)
-    int ccam_off;       // into cc_start (nfc + 1 entries per problem): the per-camera lists of cam_part partial sums
-    int be_nch;         // device-built block entries: 64-item chunks of the longest camera list
-    int becnt_off;      // ... and this problem's [nfc][be_nch][nfc] counters
-    double K[4];
-    double bf;
-};
-
-struct Opt
-{
-    int max_pcg;
-    int pcg_general;  // SNK_BA_PCG_GENERAL=1: the 256-thread PCG loop for every size (A/B against the replicated one)
-    double pcg_tol, huber_mono, huber_stereo, lambda_init;
-    double chi2_mono, chi2_stereo;  // point_pass<3> (the chi-square pass of SolveLocalScene): thresholds of the squared residual
-};
-
-struct State  // per problem, device resident
-{
-    double cost, cost_new, lambda, vfac, cost_initial;
-    int accepted, iter, pcg_iters;
-    int marked;  // observations the chi-square pass after this solve marked (point_pass<3>); begin_solve resets it
-    double first_cost_initial, first_cost;  // the costs at the time of that pass (a conditional extra iteration overwrites the others)
-};
-
-struct RpcMeta
-{
-    int img1, img2;  // image index inside the problem
-    int c1, c2;      // free-camera index or -1
-    double rel[7];
-    double w_rot, w_trans;
-};
-constexpr int RPC_STRIDE = 72;
-
-// What cam_pass needs of an observation that never changes during a solve, stored in the order of the camera lists
-// so that a camera's workgroup streams it: 40 bytes (round 5; 48 before: cam_pass and update_cost run at the speed their records
-// stream at, so the index fields are packed -- the point index and "the point is an unknown" share a word, the image is the
-// camera's and is looked up once per camera).
-struct CamObs
-{
-    double u, v, depth, weight;
-    int ptw;   // point index | "the point is an unknown" << 31
-    int orig;  // caller-order index (global)
-};
-
-// One wavefront's share of the point-major Schur pass: <= SET_CHUNK points that are all observed by the same cameras
-// in the same order (same "camera set"), so that lane q owns pair slot q = rows (ra, rb) of a point's run for all of
-// them and the 6 x 6 sum of block (camera(ra), camera(rb)) stays in its registers.
-struct SetItem
-{
-    int pts_off, n_pts;    // into set_pts; n_pts <= SET_CHUNK <= 64 (one list entry per lane)
-    int pair_off, npairs;  // into set_pairs: ra | rb << 8, camera(ra) < camera(rb) or ra == rb
-    int part_off;          // first of its npairs partial sums in s_part (36 doubles each)
-    int run;               // observations per point of this set
-    int nfree;             // free-camera observations per point (k)
-    int aux_off;           // into set_pairs: k run positions ordered by camera index, then the k x k table "pair slot of (i, j)", i <= j
-    int rec_off;           // into set_obs: n_pts x run static observation records in (point of the item, observation) order
-    int cpart_off;         // first of its nfree per-camera partial sums in cam_part (schur_fused<3, true>; 33 doubles each)
-};
-
-// camera sums of schur_fused<3, true>: 33 terms per (work item, free camera), in passes of eight: 0..7, 8..15, 16..23,
-// 24..26 (from J_c and r) and 27..32 (W V^-1 b_p)
-constexpr int CS_TERMS = 33, CS_PASSES = 5;
-
-// Static part of an observation in the order schur_fused walks it (item, point of the item, observation of the point): a lane's
-// record is at rec_off + group * run + lane, so the first round of loads of a group is three coalesced 16-byte loads.
-// In memory 40 bytes (round 5; 48 before): image, free-camera index and the "unknown" flag share a word.  SET_MAX_IMG bounds the images of a
-// problem for which the packed form exists (snk_ba_set_problems refuses more).
-constexpr int SET_MAX_IMG = 32767;
-struct SetObs
-{
-    double u, v, depth, weight;
-    int orig;  // caller-order index (global)
-    int pk;    // image inside the problem (15 bits) | point is an unknown << 15 | (free-camera index + 1) << 16
-};
 struct SetRec  // the same in a lane's registers (the index word stays packed: two registers fewer per record set than four ints)
 {
     double u, v, depth, weight;
@@ -169,65 +77,6 @@ struct SetRec  // the same in a lane's registers (the index word stays packed: t
     __device__ __forceinline__ int img() const { return pk & 0x7FFF; }           // image inside the problem
     __device__ __forceinline__ int cam() const { return (int)((unsigned)pk >> 16) - 1; }  // free-camera index or -1
     __device__ __forceinline__ bool ptfree() const { return (pk & 0x8000) != 0; }  // the point is an unknown
-};
-__host__ __device__ inline int set_pack(int img, int cam, int ptfree) { return img | (ptfree ? 1 << 15 : 0) | ((cam + 1) << 16); }
-
-struct Arrays
-{
-    const Prob* prob;
-    State* state;
-    double* pose;  // [img][7]
-    double* pose_new;
-    double* pt;  // [pt][3]
-    double* pt_new;
-    const unsigned char* pt_const;
-    const int* cam_idx;  // [img] free-camera index or -1
-    const int* pt_start;
-    // observations sorted by point
-    const int* o_img;
-    const int* o_cam;               // free-camera index of the observation's image, or -1
-    const unsigned char* o_ptfree;  // 1 when the observation's point is an unknown
-    const double2* o_uv;
-    const double* o_depth;
-    const double* o_weight;
-    const int* o_orig;             // caller-order index (global over problems)
-    const int* o_pt;               // point index (inside the problem) of the observation
-    const int* wv_pt;              // [n_wv + 1] per problem: first point of every point_wave work item
-    // relative pose constraints
-    const RpcMeta* rpc_meta;       // [rpc]
-    double* rpc_out;               // [rpc][RPC_STRIDE]: cost, trial cost, g1[6], g2[6], H11 upper[21], H12[36]
-    const int* cam_rpc_start;      // [nfc + 1] per problem
-    const int* cam_rpc_items;      // rpc index (inside the problem) * 2 + side (0: the camera is img1, 1: img2)
-    const int* blk_rpc;            // [nfc * nfc] per problem (at blkstart_off - problem index): 0 or 1 + (rpc * 2 + transposed)
-    const int* rpc_next;           // [rpc] chain of further constraints on the same camera pair, same encoding
-    const unsigned char* outlier;  // caller order
-    double* o_r;   // [obs][4]  scaled residual, [3] = dim (0: inactive in this iteration)
-    double* o_W;   // [obs][18]
-    double* ptv;   // [pt][6]   point position of the linearisation | V^-1 b_p (cam_pass rebuilds J_c, r, Y b_p from them)
-    const CamObs* cs_obs;  // static observation records in camera order (indexed like cam_items)
-    double* Vinv;  // [pt][6]
-    double* bp;    // [pt][3]
-    double* cost_pt;
-    double* cost_pt_new;
-    double* U;  // [cam][36] damped
-    const int* cam_start;
-    const int* cam_items;
-    const int* blk_start;
-    const int4* blk_ent;  // (observation of c1, observation of c2, point, 0), observation indices relative to the problem
-    const SetItem* set_items;
-    const int2* set_pts;  // (point, first observation of the point) inside the problem
-    const int* set_pairs;
-    const SetObs* set_obs;
-    const int* cblk_start;  // per problem, per block: its partial sums in cblk_items (fixed order)
-    const int* cblk_items;  // index into s_part
-    double* s_part;         // [partial][36]
-    const int* cc_start;    // per problem, per free camera: its per-item partial sums in cc_items (fixed order)
-    const int* cc_items;    // index into cam_part
-    double* cam_part;       // [partial][33]: b_c (6) | U upper (21) | Y b_p (6) of one camera over one work item's points
-    double* S;
-    double* rhs;
-    double* x;
-    double* chi2;  // caller order
 };
 
 #ifndef SNK_BA_IEEE_DIV
@@ -1339,14 +1188,6 @@ __global__ __launch_bounds__(64) void cam_sum(Arrays A)
 // (ra, rb) it owns, and because all points of a work item share one camera set (SetItem) the lane's 36 sums stay in
 // registers across the item.  The item's sums go to s_part; schur_sum adds the partial sums of a block in a fixed
 // order and writes S.  The next two points' rows are in flight (two register sets) while one is multiplied.
-constexpr int SET_CHUNK   = 50;  // points per work item (a set's points are cut into equal items of at most this many)
-// Big batches (>= 256 problems, every set with <= 8 free cameras, default kernels): items of up to 128 points.  Every item
-// writes one 288-byte partial sum per camera pair whatever its size: with 100 points per camera set (the benchmark window) one
-// item per set instead of two halves what schur_fused writes and schur_sum reads back (425 MB per LM iteration of 1024 windows).
-// Only schur_fused / update_cost walk such items (two list registers); the alternative paths keep <= 64.
-constexpr int SET_CHUNK_BIG = 104;
-constexpr int SET_MAX_RUN = 14;  // observations of a point (rows staged per point)
-constexpr int SET_MAX_K   = 10;  // free-camera observations of a point: 55 pairs <= 64 lanes
 constexpr int SET_SLOT    = SET_MAX_RUN * 144 + 48;  // LDS bytes of one staged point (2064)
 constexpr int SET_QUADS   = (SET_SLOT / 16 + 63) / 64;  // load instructions per point (3)
 
@@ -3008,33 +2849,6 @@ __global__ __launch_bounds__(PCG_THREADS, 2) void pcg_small(Arrays A, Opt O)
 // per-workgroup partial sums combined in fixed order by every workgroup that needs them (deterministic,
 // no atomics).  One PCG iteration = 4 launches (matvec, combine, update, direction); convergence is
 // re-derived from the partial sums by every workgroup, the last launch of an iteration latches it.
-struct PcgLarge
-{
-    double* r;     // [tot_vec]
-    double* z;
-    double* p;
-    double* Ap;
-    double* Minv;  // [tot_cam][36]
-    double* ps;    // [parts][tot_vec]
-    double* prr;   // [2][B][G] partial r.r   (double-buffered by iteration parity)
-    double* prz;   // [2][B][G] partial r.z
-    double* ppap;  // [B][G]    partial p.Ap
-    double* scal;  // [B][4]    stop2, done, -, -
-    int G, parts, tot_vec, B;
-    // the one-launch form (pcgl_persist, one problem): p double-buffered, per-workgroup partial sums, the grid barrier's counter
-    double* p2;       // [tot_vec]  the other direction buffer
-    double* wrr;      // [2][PERSIST_WGS]  partial r.r  (by iteration parity)
-    double* wrz;      // [2][PERSIST_WGS]  partial r.z
-    double* wpap;     // [PERSIST_WGS]     partial p.Ap
-    unsigned* bar;    // [BAR_WORDS] the grid barrier's phase flags: per workgroup, per group of eight, per group generation (zeroed by pcgl_init)
-    int bar_flat;     // SNK_BA_FLAT_BARRIER=1: every workgroup polls every flag (the round-5 barrier)
-    int persist_one;  // pcgl_persist1 (one grid barrier per PCG iteration; r, z, p private in LDS) instead of pcgl_persist
-    int persist_wgs;  // workgroups of the launch (all resident: cooperative launch)
-    int persist_rows;  // pcgl_persist_reg: rows of S per workgroup (8 or 16)
-    int timing;       // SNK_BA_PCG_TIMING=1 (diagnostic): workgroup 0 of pcgl_persist_reg adds its cycles per phase to ps[0..5]
-    double* y;        // implicit Schur form: [tot_pt][3] V^-1 W^T p of the point phase (ps[c] then holds p_c . (S p)_c)
-    int zero_rows;    // implicit Schur form: point_wave linearised (inactive observations have zero W rows, o_r is not written)
-};
 constexpr int PERSIST_WGS_MAX = 1024;
 // the grid barrier's words (grid_barrier_xcd); pcgl_init zeroes all BAR_WORDS of them before every PCG
 constexpr int BAR_PER_XCD = PERSIST_WGS_MAX / 8;      // arrival flags of group x at bar[x * BAR_PER_XCD + (workgroup >> 3)]
@@ -3042,11 +2856,6 @@ constexpr int BAR_XFLAG   = PERSIST_WGS_MAX;          // the eight group flags, 
 constexpr int BAR_GEN     = PERSIST_WGS_MAX + 32;     // the groups' generation words, 128 bytes apart
 constexpr int BAR_WORDS   = BAR_GEN + 8 * 32;
 static_assert(BAR_WORDS <= 2 * (PERSIST_WGS_MAX + 8), "the barrier's words live in the (PERSIST_WGS_MAX + 8) doubles behind wpap");
-static inline int snk_env_int(const char* name, int dflt)
-{
-    const char* e = getenv(name);
-    return e && atoi(e) > 0 ? atoi(e) : dflt;
-}
 
 __device__ __forceinline__ double wave_sum64(double v)
 {
@@ -4535,185 +4344,8 @@ __global__ void begin_solve(State* st, int n, double lambda_init, int only_marke
     if (!only_marked) st[i].marked = 0;
 }
 }  // namespace
-}  // namespace snk
 
-using namespace snk;
-
-// The lists a scene hand-over builds on the host live in PINNED vectors that belong to the handle and keep their capacity from call to
-// call: hipMemcpyAsync from pageable memory stages and synchronises (33 uploads cost 0.23 ms per local-BA scene), from pinned memory
-// it is an enqueue; and a new scene per keyframe no longer allocates and first-touches a megabyte of host memory.
-template <typename T>
-struct PinnedAlloc
-{
-    using value_type = T;
-    PinnedAlloc() = default;
-    template <typename U>
-    PinnedAlloc(const PinnedAlloc<U>&) {}
-    T* allocate(size_t n)
-    {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) throw std::bad_alloc();
-        return static_cast<T*>(p);
-    }
-    void deallocate(T* p, size_t) { (void)hipHostFree(p); }
-    // resize() default-initialises (no zero fill): every list is written in full right after it is sized, and zeroing hundreds of
-    // megabytes of pinned memory first was host time of a batch hand-over; resize(n, value) still fills
-    template <typename U>
-    void construct(U* p) noexcept
-    {
-        ::new (static_cast<void*>(p)) U;
-    }
-    template <typename U, typename... Args>
-    void construct(U* p, Args&&... args)
-    {
-        ::new (static_cast<void*>(p)) U(std::forward<Args>(args)...);
-    }
-    template <typename U>
-    bool operator==(const PinnedAlloc<U>&) const { return true; }
-    template <typename U>
-    bool operator!=(const PinnedAlloc<U>&) const { return false; }
-};
-template <typename T>
-using pvec = std::vector<T, PinnedAlloc<T>>;
-
-struct BaLists
-{
-    pvec<Prob> probs;
-    pvec<double> pose, pt, ouv2, odepth, oweight;
-    pvec<unsigned char> ptc, optfree;
-    pvec<SetItem> setitems;
-    pvec<int2> setpts;
-    pvec<int> setpairs, cblkstart, cblkitems, ccstart, ccitems;
-    pvec<int> camidx, ptstart, oimg, ocam, oorig, camstart, camitems, blkstart, optidx, wvpt, rpcnext, camrpcstart, camrpcitems, blkrpc;
-    pvec<RpcMeta> rpcmeta;
-    pvec<int4> blkent;
-    pvec<State> states;
-    void clear()
-    {
-        probs.clear(), pose.clear(), pt.clear(), ouv2.clear(), odepth.clear(), oweight.clear(), ptc.clear(), optfree.clear();
-        setitems.clear(), setpts.clear(), setpairs.clear(), cblkstart.clear(), cblkitems.clear();
-        camidx.clear(), ptstart.clear(), oimg.clear(), ocam.clear(), oorig.clear(), camstart.clear(), camitems.clear();
-        blkstart.clear(), optidx.clear(), wvpt.clear(), rpcnext.clear(), camrpcstart.clear(), camrpcitems.clear(), blkrpc.clear();
-        rpcmeta.clear(), blkent.clear(), ccstart.clear(), ccitems.clear();
-    }
-};
-
-// The host threads of a batch hand-over, kept by the handle (round 6, late).  snk_ba_set_problems runs seven threaded passes over the
-// problems of a batch; with std::thread created and joined per pass that was 7 x 31 creations (~20 us each, issued one after the
-// other) inside a 22 ms hand-over.  Workers park on a condition variable between passes and end with the handle.
-constexpr int BA_FILL_CHUNKS = 4;   // chunks of problems the fill pass of a batch hand-over runs (and uploads) in
-struct HostPool
-{
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv, cv_done;
-    const std::function<void()>* job = nullptr;
-    unsigned gen = 0;
-    int n_run = 0, n_left = 0;
-    bool stop = false;
-    void worker(int idx)
-    {
-        unsigned seen = 0;
-        for (;;)
-        {
-            const std::function<void()>* j = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv.wait(lk, [&] { return stop || gen != seen; });
-                if (stop) return;
-                seen = gen;
-                if (idx < n_run) j = job;
-            }
-            if (j)
-            {
-                (*j)();  // the passes catch their own exceptions
-                std::lock_guard<std::mutex> lk(m);
-                if (--n_left == 0) cv_done.notify_one();
-            }
-        }
-    }
-    // runs `work` on up to `helpers` pool threads and on the caller; returns when all of them are done
-    void run(int helpers, const std::function<void()>& work)
-    {
-        try
-        {
-            while ((int)th.size() < helpers) th.emplace_back(&HostPool::worker, this, (int)th.size());
-        }
-        catch (...)
-        {
-        }  // thread creation failed: the threads that exist (and the caller) do the work
-        const int n = std::min(helpers, (int)th.size());
-        if (n > 0)
-        {
-            std::lock_guard<std::mutex> lk(m);
-            job    = &work;
-            n_run  = n;
-            n_left = n;
-            ++gen;
-        }
-        if (n > 0) cv.notify_all();
-        work();
-        if (n > 0)
-        {
-            std::unique_lock<std::mutex> lk(m);
-            cv_done.wait(lk, [&] { return n_left == 0; });
-            job = nullptr;
-        }
-    }
-    ~HostPool()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            stop = true;
-        }
-        cv.notify_all();
-        for (auto& t : th) t.join();
-    }
-};
-
-struct snk_ba : HandleBase
-{
-    BaLists lists;
-    HostPool pool;    // host threads of the batch hand-over
-    HostBuf h_stage;  // pinned staging of the small per-call transfers (outlier masks)
-    DevBuf d_becnt;   // per (camera, 64-item chunk, camera) counters of the device-built block entries
-    DevBuf d_probcond;  // the problem table of a conditional extra iteration (select_marked)
-    DevBuf d_campart, d_ccstart, d_ccitems;  // per (work item, free camera) sums of schur_fused<3, true> and the per-camera lists of them
-    bool state_fresh = false;                // the device state is the uploaded initial one (no solve since the hand-over)
-    bool blk_built = true;                   // the camera-pair block entries of the current problem set exist on the device (see ba_sets_will_run)
-    bool cam_sums_ok = false;                // every observation of a free camera belongs to a work item with pairs (no constant point seen by a free camera)
-    snk_ba_options opt{};
-    int count = 0;
-    std::vector<Prob> probs;
-    int tot_img = 0, tot_pt = 0, tot_obs = 0, tot_cam = 0, tot_orig = 0, tot_vec = 0;
-    long long tot_s = 0;
-    int max_np = 0, max_nfc = 0, max_n6 = 0, max_ni = 0, max_set_items = 0;
-    bool set_ok = false, set_small = false;
-    int set_k_max = 0, set_run_max = 0;
-    DevBuf d_setitems, d_setpts, d_setpairs, d_setobs, d_cblkstart, d_cblkitems, d_spart;
-    DevBuf d_prob, d_state, d_pose, d_pose_new, d_pose0, d_pt, d_pt_new, d_pt0, d_ptc, d_camidx, d_ptstart, d_oimg, d_ocam,
-        d_optfree, d_ouv, d_odepth, d_oweight, d_oorig, d_outlier, d_csobs, d_r, d_W, d_ptv, d_Vinv, d_bp, d_cost,
-        d_cost_new, d_U, d_camstart, d_camitems, d_blkstart, d_blkent, d_S, d_rhs, d_x, d_chi2, d_pcgw, d_optidx, d_wvpt, d_rpcmeta, d_rpcnext, d_camrpcstart, d_camrpcitems, d_blkrpc, d_rpcout;
-    int max_rpc = 0;
-    int max_wv = 0;
-    bool point_wave_ok = false;  // every problem has a point_wave work list (no point with > 64 observations)
-    PcgLarge pcgw{};     // work arrays of the multi-workgroup PCG (only when the reduced system exceeds the LDS)
-    bool pcg_large = false;
-    int explicit_schur = 1;  // snk_ba_set_explicit_schur: the form the next hand-over builds
-    bool implicit = false;   // the current problem set runs the implicit Schur form (imp_*): no S, no camera-pair lists
-    Arrays arr{};
-    std::vector<int> orig_off, orig_n;
-    std::map<int, hipGraphExec_t> graphs;  // LM launch sequence captured per iteration count
-    std::map<int, int> plain_runs;         // solves issued with plain launches since set_problems, per iteration count
-    void drop_graphs()
-    {
-        for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-        graphs.clear();
-        plain_runs.clear();
-    }
-};
-
-namespace
+namespace ba
 {
 Opt make_opt(const snk_ba_options& o)
 {
@@ -4728,237 +4360,10 @@ Opt make_opt(const snk_ba_options& o)
     d.chi2_mono = d.chi2_stereo = 0.0;
     return d;
 }
+}  // namespace ba
 
-// The hand-over's lists reach the device with ONE kernel that reads the pinned host vectors over the bus (hipHostMalloc memory is
-// device-visible) and writes the device arrays: 33 separate copies cost ~6 us each on the copy engine whatever their size.
-constexpr int COPY_TAB_MAX = 48;
-struct CopyTab
+namespace
 {
-    const void* src[COPY_TAB_MAX];
-    void* dst[COPY_TAB_MAX];
-    unsigned bytes[COPY_TAB_MAX];
-    int n;
-};
-// ---- scene lists built on the device -------------------------------------------------------------------------------------------
-// The static per-camera observation records (what cam_pass streams) are a gather of the sorted observation arrays through the
-// camera lists: 40 bytes per observation that neither the host loop nor the bus has to touch.
-// Batches (round 6): three of the sorted observation arrays and the camera lists are functions of arrays that are on the device anyway --
-// 13 of the 53 bytes per observation a hand-over used to carry over the bus (210 MB of a 1024-window batch's 1.07 GB).
-//   o_pt[s]     = the point whose run [pt_start[p], pt_start[p + 1]) holds s (binary search),
-//   o_cam[s]    = cam_idx[o_img[s]],   o_ptfree[s] = !pt_const[o_pt[s]]
-__global__ __launch_bounds__(256) void derive_obs_fields(Arrays A, int* __restrict__ o_pt, int* __restrict__ o_cam, unsigned char* __restrict__ o_ptfree)
-{
-    const Prob pr = A.prob[blockIdx.y];
-    const int s   = blockIdx.x * 256 + threadIdx.x;
-    if (s >= pr.no) return;
-    const int* ps = A.pt_start + pr.ptstart_off;
-    int lo = 0, hi = pr.np;  // ps[lo] <= s < ps[hi]
-    while (hi - lo > 1)
-    {
-        const int mid = (lo + hi) >> 1;
-        if (ps[mid] <= s) lo = mid;
-        else hi = mid;
-    }
-    const int go  = pr.obs_off + s;
-    o_pt[go]      = lo;
-    o_cam[go]     = A.cam_idx[pr.img_off + A.o_img[go]];
-    o_ptfree[go]  = A.pt_const[pr.pt_off + lo] ? 0 : 1;
-}
-// cam_items of camera c = the observations s with o_cam[s] == c in ascending s (the host builder's order): one wavefront per (camera,
-// problem) walks the observations 64 at a time and compacts by ballot.  cam_start comes from the host (nfc + 1 ints per problem).
-__global__ __launch_bounds__(64) void derive_cam_items(Arrays A, const int* __restrict__ o_cam, int* __restrict__ cam_items)
-{
-    const Prob pr = A.prob[blockIdx.y];
-    const int c   = blockIdx.x;
-    if (c >= pr.nfc) return;
-    const int lane = threadIdx.x;
-    int at = pr.citem_off + A.cam_start[pr.camstart_off + c];
-    for (int s0 = 0; s0 < pr.no; s0 += 64)
-    {
-        const int s    = s0 + lane;
-        const bool hit = s < pr.no && o_cam[pr.obs_off + s] == c;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-        if (hit) cam_items[at + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = s;
-        at += __popcll(m);
-    }
-}
-
-__global__ __launch_bounds__(256) void gather_cam_records(Arrays A, CamObs* __restrict__ out)
-{
-    const Prob pr = A.prob[blockIdx.y];
-    const int n   = A.cam_start[pr.camstart_off + pr.nfc];
-    const int k   = blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    const int go = pr.obs_off + A.cam_items[pr.citem_off + k];
-    const double2 uv = A.o_uv[go];
-    CamObs rec;
-    rec.u = uv.x; rec.v = uv.y; rec.depth = A.o_depth[go]; rec.weight = A.o_weight[go];
-    rec.ptw = A.o_pt[go] | (A.o_ptfree[go] ? (int)0x80000000u : 0); rec.orig = A.o_orig[go];
-    out[pr.citem_off + k] = rec;
-}
-
-// The static observation records in the order schur_fused / update_cost walk them (work item, point of the item, observation of
-// the point) are a gather as well: 48 bytes per observation that the host loop wrote one by one and the bus carried (786 KB per
-// benchmark window -- half of a batch's upload).  One workgroup per work item.
-__global__ __launch_bounds__(256) void gather_set_records(Arrays A, SetObs* __restrict__ out)
-{
-    const Prob pr = A.prob[blockIdx.y];
-    if ((int)blockIdx.x >= pr.n_set) return;
-    const SetItem si = A.set_items[pr.set_off + blockIdx.x];
-    const int n      = si.n_pts * si.run;
-    for (int idx = threadIdx.x; idx < n; idx += 256)
-    {
-        const int q = idx / si.run, a = idx - q * si.run;
-        const int go = pr.obs_off + A.set_pts[si.pts_off + q].y + a;
-        const double2 uv = A.o_uv[go];
-        SetObs rec;
-        rec.u = uv.x; rec.v = uv.y; rec.depth = A.o_depth[go]; rec.weight = A.o_weight[go];
-        rec.orig = A.o_orig[go]; rec.pk = set_pack(A.o_img[go], A.o_cam[go], A.o_ptfree[go]);
-        out[(size_t)si.rec_off + idx] = rec;
-    }
-}
-
-// The camera-pair block entries of schur_pass -- for every upper block (c1, c2) the co-observations (observation of c1,
-// observation of c2, point) in ascending order -- built by three launches instead of a host loop over every pair of every
-// point (half of a scene hand-over's host time, and 1.1 MB over the bus for a 20 x 2000 x 8 window).  Requirements (checked
-// on the host, which keeps its own builder for the other scenes): <= BE_MAX_CAMS free cameras, no camera twice on a point.
-// One wavefront per (camera c1, 64 items of its list): lane = one observation a of c1; the free cameras >= c1 in its point's
-// run are a bit mask (BE_WORDS x 64 bits in registers); ballot(c2 in mask) ranks the lane inside the chunk for block (c1, c2).
-// Order inside a block = list order of c1 = ascending observation index = ascending point: the host builder's order.
-constexpr int BE_WORDS = 8, BE_MAX_CAMS = 64 * BE_WORDS;
-__device__ inline void block_entry_item(const Arrays& A, const Prob& pr, int c1, int chunk, int lane, int& a, int& p, int& r0, int& r1,
-                                        unsigned long long (&mask)[BE_WORDS])
-{
-    const int s0 = A.cam_start[pr.camstart_off + c1], s1 = A.cam_start[pr.camstart_off + c1 + 1];
-    const int k  = s0 + chunk * 64 + lane;
-    a = -1, p = 0, r0 = 0, r1 = 0;
-#pragma unroll
-    for (int w = 0; w < BE_WORDS; ++w) mask[w] = 0ull;
-    if (k >= s1) return;
-    const int s  = A.cam_items[pr.citem_off + k];
-    const int go = pr.obs_off + s;
-    if (!A.o_ptfree[go]) return;  // constant points produce no Schur products
-    a  = s;
-    p  = A.o_pt[go];
-    r0 = A.pt_start[pr.ptstart_off + p], r1 = A.pt_start[pr.ptstart_off + p + 1];
-    for (int c = r0; c < r1; ++c)
-    {
-        const int cc = A.o_cam[pr.obs_off + c];
-        if (cc < c1) continue;
-        const unsigned long long bit = 1ull << (cc & 63);
-#pragma unroll
-        for (int w = 0; w < BE_WORDS; ++w)
-            if (w == (cc >> 6)) mask[w] |= bit;
-    }
-}
-
-__global__ __launch_bounds__(64) void block_entries_count(Arrays A, int* __restrict__ cnt)
-{
-    const Prob pr = A.prob[blockIdx.y];
-    const int w0  = blockIdx.x;
-    if (pr.be_nch <= 0 || w0 >= pr.nfc * pr.be_nch) return;
-    const int c1 = w0 / pr.be_nch, chunk = w0 - c1 * pr.be_nch, lane = threadIdx.x;
-    int a, p, r0, r1;
-    unsigned long long mask[BE_WORDS];
-    block_entry_item(A, pr, c1, chunk, lane, a, p, r0, r1, mask);
-    int* out = cnt + pr.becnt_off + (size_t)(c1 * pr.be_nch + chunk) * pr.nfc;
-#pragma unroll
-    for (int w = 0; w < BE_WORDS; ++w)
-    {
-        if (w * 64 >= pr.nfc) break;  // uniform
-        int mine = 0;
-        if (__builtin_amdgcn_ballot_w64(mask[w] != 0ull) != 0ull)  // uniform: most words of a big scene are empty
-            for (int b = 0; b < 64; ++b)
-            {
-                const unsigned long long m = __builtin_amdgcn_ballot_w64((mask[w] >> b) & 1ull);
-                if (lane == b) mine = __popcll(m);
-            }
-        if (w * 64 + lane < pr.nfc) out[w * 64 + lane] = mine;  // (cameras below c1 are in no mask: zeros)
-    }
-}
-
-// per problem: chunk counts -> chunk bases (in place), block totals -> blk_start (exclusive scan over the nfc * nfc blocks)
-constexpr int BE_SCAN_THREADS = 1024;
-__global__ __launch_bounds__(BE_SCAN_THREADS) void block_entries_scan(Arrays A, int* __restrict__ cnt, int* __restrict__ blk_start)
-{
-    __shared__ int s_wave[BE_SCAN_THREADS / 64];
-    __shared__ int s_run;
-    const Prob pr = A.prob[blockIdx.x];
-    const int nb = pr.nfc * pr.nfc, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_run = 0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += BE_SCAN_THREADS)
-    {
-        const int blk = base + tid;
-        int tot = 0;
-        if (blk < nb && pr.be_nch > 0)
-        {
-            const int c1 = blk / pr.nfc, c2 = blk - c1 * pr.nfc;
-            if (c2 >= c1)  // the lower blocks have no entries (and their counters were never written)
-                for (int ch = 0; ch < pr.be_nch; ++ch)
-                {
-                    int* q = cnt + pr.becnt_off + (size_t)(c1 * pr.be_nch + ch) * pr.nfc + c2;
-                    const int v = *q;
-                    *q = tot;
-                    tot += v;
-                }
-        }
-        // inclusive scan: inside the wavefront by shuffles, then the wavefront totals
-        int incl = tot;
-        incl = wave_scan_incl_dpp(incl);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        const int run = s_run;
-        if (blk < nb) blk_start[pr.blkstart_off + blk] = run + before + incl - tot;
-        __syncthreads();
-        if (tid == BE_SCAN_THREADS - 1) s_run = run + before + incl;
-        __syncthreads();
-    }
-    if (tid == 0) blk_start[pr.blkstart_off + nb] = s_run;
-}
-
-__global__ __launch_bounds__(64) void block_entries_fill(Arrays A, const int* __restrict__ cnt, int4* __restrict__ blk_ent)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char be_smem[];
-    const Prob pr = A.prob[blockIdx.y];
-    const int w0  = blockIdx.x;
-    if (pr.be_nch <= 0 || w0 >= pr.nfc * pr.be_nch) return;
-    unsigned long long* s_ball = reinterpret_cast<unsigned long long*>(be_smem);  // [words * 64] ballots per camera c2
-    const int nwords = (pr.nfc + 63) >> 6;
-    int* s_base = reinterpret_cast<int*>(s_ball + nwords * 64);                     // [words * 64] first entry of (c1, chunk, c2)
-    const int c1 = w0 / pr.be_nch, chunk = w0 - c1 * pr.be_nch, lane = threadIdx.x;
-    int a, p, r0, r1;
-    unsigned long long mask[BE_WORDS];
-    block_entry_item(A, pr, c1, chunk, lane, a, p, r0, r1, mask);
-    const int* cin = cnt + pr.becnt_off + (size_t)(c1 * pr.be_nch + chunk) * pr.nfc;
-#pragma unroll
-    for (int w = 0; w < BE_WORDS; ++w)
-    {
-        if (w * 64 >= pr.nfc) break;  // uniform
-        unsigned long long mine = 0ull;
-        if (__builtin_amdgcn_ballot_w64(mask[w] != 0ull) != 0ull)
-            for (int b = 0; b < 64; ++b)
-            {
-                const unsigned long long m = __builtin_amdgcn_ballot_w64((mask[w] >> b) & 1ull);
-                if (lane == b) mine = m;
-            }
-        const int c2 = w * 64 + lane;
-        s_ball[c2] = mine;
-        s_base[c2] = c2 >= c1 && c2 < pr.nfc ? A.blk_start[pr.blkstart_off + c1 * pr.nfc + c2] + cin[c2] : 0;
-    }
-    __syncthreads();
-    if (a < 0) return;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int c = r0; c < r1; ++c)
-    {
-        const int cc = A.o_cam[pr.obs_off + c];
-        if (cc < c1) continue;
-        blk_ent[(size_t)pr.ent_off + s_base[cc] + __popcll(s_ball[cc] & below)] = make_int4(a, c, p, 0);
-    }
-}
-
 // The extra iteration of SolveLocalScene runs only for scenes whose chi-square pass marked something
 // (LocalBundleAdjustment.cpp:399).  Instead of reading the count back and deciding on the host, the iteration is enqueued
 // behind the pass with THIS table of problems: an unmarked problem appears with every size zero, so each kernel of the
@@ -4982,43 +4387,10 @@ __global__ __launch_bounds__(64) void select_marked(const Prob* __restrict__ pro
     }
     out[i] = p;
 }
-
-__global__ __launch_bounds__(256) void copy_table_kernel(CopyTab T)
-{
-    const int e = blockIdx.y;
-    const unsigned nb = T.bytes[e], nq = nb >> 4;
-    const uint4* s4 = static_cast<const uint4*>(T.src[e]);  // both sides are at least 256-byte aligned (hipHostMalloc / hipMalloc)
-    uint4* d4       = static_cast<uint4*>(T.dst[e]);
-    if (s4 == nullptr)  // a buffer that starts as zeros
-    {
-        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nq; i += gridDim.x * 256u) d4[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (blockIdx.x == 0)
-            for (unsigned i = (nq << 4) + threadIdx.x; i < nb; i += 256u) static_cast<unsigned char*>(T.dst[e])[i] = 0;
-        return;
-    }
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nq; i += gridDim.x * 256u) d4[i] = s4[i];
-    if (blockIdx.x == 0)
-    {
-        const unsigned char* sb = static_cast<const unsigned char*>(T.src[e]);
-        unsigned char* db       = static_cast<unsigned char*>(T.dst[e]);
-        for (unsigned i = (nq << 4) + threadIdx.x; i < nb; i += 256u) db[i] = sb[i];
-    }
-}
-template <typename V>
-int upload(DevBuf& b, const V& v, CopyTab& tab)
-{
-    using T = typename V::value_type;
-    int rc  = b.reserve(std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (rc != SNK_OK) return rc;
-    if (v.empty()) return SNK_OK;
-    SNK_REQUIRE(tab.n < COPY_TAB_MAX && v.size() * sizeof(T) < (1ull << 32), "scene list too large for the upload table");
-    tab.src[tab.n]   = v.data();
-    tab.dst[tab.n]   = b.p;
-    tab.bytes[tab.n] = (unsigned)(v.size() * sizeof(T));
-    ++tab.n;
-    return SNK_OK;
-}
 }  // namespace
+}  // namespace snk
+
+using namespace snk;
 
 // One launch sequence, two ways to issue it: plain launches on the handle's stream, or kernel nodes appended to an
 // explicitly built hipGraph (a linear chain).  No stream capture anywhere: capture is process-visible state that any
@@ -5070,11 +4442,15 @@ struct Launcher
 };
 #define LAUNCH(...) L(__LINE__, __VA_ARGS__)
 
+namespace snk
+{
+namespace ba
+{
 // Will the LM sequence of this problem set run the point-major kernels (schur_fused / schur_mfma + update_cost over the camera-set work
 // items)?  Decided by the hand-over's results and by switches that are read once per process: the hand-over asks too, because the
 // camera-pair block entries are only read by the block-major pass (schur_pass) -- building them for a 1024-window batch that never
 // runs it was 1.4 ms of device time behind every hand-over (block_entries_count 0.40 + block_entries_fill 1.03 ms, round 6 trace).
-static bool ba_sets_will_run(const snk_ba* h)
+bool ba_sets_will_run(const snk_ba* h)
 {
     static const bool no_wave       = getenv("SNK_BA_NO_POINT_WAVE") != nullptr;
     static const bool no_set        = getenv("SNK_BA_NO_SCHUR_SET") != nullptr;
@@ -5082,1144 +4458,18 @@ static bool ba_sets_will_run(const snk_ba* h)
     return h->max_nfc > 0 && h->point_wave_ok && !no_wave && h->set_ok && !no_set && (long long)h->max_set_items * h->count >= set_min;
 }
 
-extern "C" {
-
-int snk_ba_create(const snk_ba_options* options, int device, void* stream, snk_ba** out)
+// The PCG form of a problem set and its work arrays (the hand-over calls this once the set's totals are in the handle; it lives here,
+// beside the kernels whose occupancy it asks the runtime for).
+int ba_plan_pcg(snk_ba* h)
 {
-    SNK_REQUIRE(out != nullptr, "out is NULL");
-    *out = nullptr;
-    SNK_REQUIRE(options != nullptr, "options is NULL");
-    SNK_REQUIRE(options->max_iterations >= 0 && options->max_pcg_iterations >= 0, "negative iteration count");
-    SNK_REQUIRE(options->huber_mono > 0.0 && options->huber_stereo > 0.0, "Huber thresholds must be > 0");
-    snk_ba* h = new snk_ba();
-    h->opt    = *options;
-    int rc    = h->init(device, stream);
-    if (rc != SNK_OK)
-    {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return SNK_OK;
-}
-
-int snk_ba_destroy(snk_ba* h)
-{
-    if (!h) return SNK_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);  // an upload of a hand-over (it reads the handle's pinned lists) or a solve may still be in flight
-    // every device buffer of the handle (the struct's DevBuf members)
-    DevBuf* all[] = {&h->d_setitems, &h->d_setpts, &h->d_setpairs, &h->d_setobs, &h->d_cblkstart, &h->d_cblkitems, &h->d_spart,
-                     &h->d_prob, &h->d_state, &h->d_pose, &h->d_pose_new, &h->d_pose0, &h->d_pt, &h->d_pt_new,
-                     &h->d_pt0, &h->d_ptc, &h->d_camidx, &h->d_ptstart, &h->d_oimg, &h->d_ocam, &h->d_optfree,
-                     &h->d_ouv, &h->d_odepth, &h->d_oweight, &h->d_oorig, &h->d_outlier, &h->d_csobs, &h->d_r,
-                     &h->d_W, &h->d_ptv, &h->d_Vinv, &h->d_bp, &h->d_cost, &h->d_cost_new, &h->d_U, &h->d_camstart,
-                     &h->d_camitems, &h->d_blkstart, &h->d_blkent, &h->d_S, &h->d_rhs, &h->d_x, &h->d_chi2,
-                     &h->d_pcgw, &h->d_optidx, &h->d_wvpt, &h->d_rpcmeta, &h->d_rpcnext, &h->d_camrpcstart,
-                     &h->d_camrpcitems, &h->d_blkrpc, &h->d_rpcout, &h->d_becnt, &h->d_probcond, &h->d_campart, &h->d_ccstart, &h->d_ccitems};
-    for (DevBuf* b : all) b->release();
-    h->h_stage.release();
-    h->drop_graphs();
-    h->fini();
-    delete h;
-    return SNK_OK;
-}
-
-int snk_ba_sync(snk_ba* h)
-{
-    SNK_REQUIRE(h != nullptr, "ba is NULL");
-    SNK_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return SNK_OK;
-}
-
-int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
-{
-    SNK_REQUIRE(h != nullptr, "ba is NULL");
-    // A call that fails leaves NO problem set, whichever of its many exits it takes (snake_hip.h): past the checks the early upload of a
-    // batch writes into the device arrays of the previous set and the host lists are cleared, so solve / get_state / residuals must then
-    // refuse ("no problem set") instead of running the old tables over half-replaced arrays -- and a refused argument or a failed HIP
-    // call ends the previous set as well, so that the caller never has to tell the exits apart.
-    h->count       = 0;
-    h->state_fresh = false;
-    struct NoSetOnFailure
-    {
-        snk_ba* h;
-        bool ok = false;
-        ~NoSetOnFailure()
-        {
-            if (!ok) h->count = 0, h->state_fresh = false;
-        }
-    } no_set_on_failure{h};
-    SNK_REQUIRE(count >= 1 && count <= 65535 && problems != nullptr, "count must be 1..65535");
-    // implicit Schur form (snk_ba_set_explicit_schur): one scene; nothing below sized (free cameras)^2 is built or allocated
-    const bool imp = h->explicit_schur == 0;
-    SNK_REQUIRE(!imp || count == 1, "the implicit Schur form takes one problem (snk_ba_set_explicit_schur)");
-    h->implicit = imp;
-    for (int b = 0; b < count; ++b)  // the packed observation records hold the image index in 15 bits (SetObs)
-        SNK_REQUIRE(problems[b].n_img <= SET_MAX_IMG, "a problem has more than 32767 images");
-    SNK_HIP_CHECK(hipSetDevice(h->device));
-    SNK_HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->drop_graphs();
-    const auto t_begin = std::chrono::steady_clock::now();
-
-    BaLists& LS = h->lists;  // pinned, capacity kept from the previous scene
-    LS.clear();
-    auto& probs = LS.probs;
-    probs.resize((size_t)count);
-    auto &pose = LS.pose, &pt = LS.pt, &ouv2 = LS.ouv2, &odepth = LS.odepth, &oweight = LS.oweight;
-    auto &ptc = LS.ptc, &optfree = LS.optfree;
-    auto& setitems = LS.setitems;
-    auto& setpts   = LS.setpts;
-    auto &setpairs = LS.setpairs, &cblkstart = LS.cblkstart, &cblkitems = LS.cblkitems, &ccstart = LS.ccstart, &ccitems = LS.ccitems;
-    int n_partials = 0, max_set_items = 0, max_set_pairs = 0, max_set_run = 0, max_set_k = 0;
-    int n_cparts = 0;          // per (work item, free camera) partial sums of the camera pass
-    long long n_setrec = 0;    // static observation records of the work items
-    bool cam_sums_ok = true;   // no constant point is seen by a free camera (its observations are in no work item with pairs)
-    bool set_ok = true;  // every problem can run the point-major Schur pass
-    auto &camidx = LS.camidx, &ptstart = LS.ptstart, &oimg = LS.oimg, &ocam = LS.ocam, &oorig = LS.oorig, &camstart = LS.camstart,
-         &camitems = LS.camitems, &blkstart = LS.blkstart, &optidx = LS.optidx, &wvpt = LS.wvpt, &rpcnext = LS.rpcnext,
-         &camrpcstart = LS.camrpcstart, &camrpcitems = LS.camrpcitems, &blkrpc = LS.blkrpc;
-    auto& rpcmeta = LS.rpcmeta;
-    int max_rpc = 0;
-    int max_wv = 0;
-    bool wave_ok = true;
-    auto& blkent = LS.blkent;
-    {
-        // the big lists are sized by the totals of the call: growing a pinned vector re-pins and copies it every time it doubles
-        size_t t_img = 0, t_pt = 0, t_obs = 0;
-        for (int b = 0; b < count; ++b)
-        {
-            t_img += (size_t)std::max(problems[b].n_img, 0);
-            t_pt += (size_t)std::max(problems[b].n_pt, 0);
-            t_obs += (size_t)std::max(problems[b].n_obs, 0);
-        }
-        pose.reserve(7 * t_img), pt.reserve(3 * t_pt), ptc.reserve(t_pt), camidx.reserve(t_img), ptstart.reserve(t_pt + (size_t)count);
-        ouv2.reserve(2 * t_obs), odepth.reserve(t_obs), oweight.reserve(t_obs), optfree.reserve(t_obs), oimg.reserve(t_obs);
-        ocam.reserve(t_obs), oorig.reserve(t_obs), optidx.reserve(t_obs), camitems.reserve(t_obs);
-        // ... and so are the lists of the point-major pass when they will be built (batches, big scenes): on a 300-keyframe
-        // scene the doubling of setobs / cblkstart / cblkitems through fresh pinned allocations was 17 of the 26 ms of a
-        // first hand-over (the same scene again on the handle, capacities kept: 8 ms)
-        size_t t_blk = 0;
-        bool sets_likely = count >= 8 || getenv("SNK_BA_SCHUR_SET_MIN_ITEMS") != nullptr;
-        for (int b = 0; b < count; ++b)
-        {
-            size_t nfc = 0;
-            if (problems[b].img_const)
-                for (int i = 0; i < problems[b].n_img; ++i) nfc += problems[b].img_const[i] ? 0 : 1;
-            t_blk += nfc * nfc + 1;
-            sets_likely |= problems[b].n_pt >= 8000;
-        }
-        if (!imp) cblkstart.reserve(t_blk);
-        if (sets_likely && !imp) setpts.reserve(t_pt), cblkitems.reserve(2 * t_obs), ccitems.reserve(t_obs);
-    }
-    h->orig_off.assign((size_t)count, 0);
-    h->orig_n.assign((size_t)count, 0);
-    int img_off = 0, pt_off = 0, obs_off = 0, cam_off = 0, orig_off = 0, vec_off = 0;
-    long long s_off = 0;
-    int max_np = 0, max_nfc = 0, max_n6 = 0, max_ni = 0;
-
-    // work items of up to 128 points: see SET_CHUNK_BIG.  Needs the default point-major kernels (the A/B switches that select
-    // the others are read here as well) and at most 8 free observations per point in EVERY problem (else the batch runs
-    // point_wave + schur_mfma<4>), which is known only after a look at all of them.
-    // (decided behind the sizing pass below, which counts the free observations per point on the host threads: as a serial loop over
-    // every observation of the batch in front of everything else it was ~20 of a 1024-window hand-over's 53 ms of list time, round 6)
-    bool big_items = false;
-    static const bool alt_paths = getenv("SNK_BA_NO_SCHUR_FUSED") || getenv("SNK_BA_NO_SCHUR_MFMA") || getenv("SNK_BA_NO_UPDATE_COST") ||
-                                  getenv("SNK_BA_FUSED_K10") || getenv("SNK_BA_NO_SCHUR_SET") || getenv("SNK_BA_NO_POINT_WAVE") ||
-                                  getenv("SNK_BA_NO_BIG_ITEMS");
-    const bool want_big_items = count >= 256 && !alt_paths;
-    size_t blkrpc_logical = 0;   // entries of blk_rpc up to the current problem (materialised only for problems with constraints)
-    bool dev_entries_ok = true;  // every problem can have its block entries built on the device
-    std::vector<long long> ent_bound((size_t)count, 0);
-    int blkstart_total = 0, max_citems = 0;
-    // camera-pair blocks on the host: co-observations of every ordered pair (dense block grid, empty blocks allowed).  The
-    // builder for scenes the device kernels do not take (more than 512 free cameras, one camera twice on a point), and their checker.
-    auto host_block_entries = [&](int b, pvec<int>& blkstart, pvec<int4>& blkent)
-    {
-        const snk_ba_problem& P = problems[b];
-        const Prob& pr          = probs[(size_t)b];
-        const int nfc           = pr.nfc;
-        const int* pstart       = ptstart.data() + pr.ptstart_off;
-        const int* s_cam        = ocam.data() + pr.obs_off;
-        {
-            const size_t nb = (size_t)nfc * nfc;
-            std::vector<int> bs(nb + 1, 0);
-            for (int p = 0; p < P.n_pt; ++p)
-            {
-                if (P.pt_const[p]) continue;
-                for (int a = pstart[(size_t)p]; a < pstart[(size_t)p + 1]; ++a)
-                {
-                    if (s_cam[(size_t)a] < 0) continue;
-                    for (int c = pstart[(size_t)p]; c < pstart[(size_t)p + 1]; ++c)  // upper blocks only: schur_pass never reads the others
-                        if (s_cam[(size_t)c] >= s_cam[(size_t)a]) bs[(size_t)s_cam[(size_t)a] * nfc + s_cam[(size_t)c] + 1]++;
-                }
-            }
-            for (size_t k = 0; k < nb; ++k) bs[k + 1] += bs[k];
-            const size_t ent_at = blkent.size();
-            blkent.resize(ent_at + (size_t)bs[nb]);  // filled in place (no second copy of a megabyte of entries)
-            int4* ent = blkent.data() + ent_at;
-            std::vector<int> fill(bs.begin(), bs.end() - 1);
-            for (int p = 0; p < P.n_pt; ++p)
-            {
-                if (P.pt_const[p]) continue;
-                for (int a = pstart[(size_t)p]; a < pstart[(size_t)p + 1]; ++a)
-                {
-                    if (s_cam[(size_t)a] < 0) continue;
-                    for (int c = pstart[(size_t)p]; c < pstart[(size_t)p + 1]; ++c)
-                        if (s_cam[(size_t)c] >= s_cam[(size_t)a])
-                        {
-                            int4 e;
-                            e.x = a;
-                            e.y = c;
-                            e.z = p;
-                            e.w = 0;
-                            ent[(size_t)fill[(size_t)s_cam[(size_t)a] * nfc + s_cam[(size_t)c]]++] = e;
-                        }
-                }
-            }
-            blkstart.insert(blkstart.end(), bs.begin(), bs.end());
-        }
-    };
-    static const bool prof_sections = getenv("SNK_BA_PROFILE_CREATE") != nullptr;
-    long long sec_us[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto sec_t = std::chrono::steady_clock::now();
-    auto mark = [&](int k)
-    {
-        if (!prof_sections) return;
-        const auto now = std::chrono::steady_clock::now();
-        sec_us[k] += (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(now - sec_t).count();
-        sec_t = now;
-    };
-    // ---- sizing pass + fill pass over the problems, on several host threads for batches (round 4) ----
-    // The values, the free-camera indices, the counting sort by point and the eight sorted observation arrays of a problem depend on nothing
-    // but that problem, and they were half of a batch hand-over's list time on ONE core (1024 windows: 117 of 227 ms).  Pass 1 counts
-    // (valid observations, free cameras) per problem, a prefix sum gives every problem its place in the shared lists, pass 2 writes the
-    // places directly -- disjoint ranges, no locks.  The per-problem loop below then only READS these lists.  Same contents as the serial
-    // builder (the loop's old code, run per problem): SNK_BA_CHECK_LISTS and the bit-identity tests of the variants suite cover it.
-    for (int b = 0; b < count; ++b)
-    {
-        const snk_ba_problem& P = problems[b];
-        SNK_REQUIRE(P.n_img >= 0 && P.n_pt >= 0 && P.n_obs >= 0, "negative problem size");
-        SNK_REQUIRE(P.n_img == 0 || (P.pose && P.img_const), "NULL pose arrays");
-        SNK_REQUIRE(P.n_pt == 0 || (P.pt && P.pt_const), "NULL point arrays");
-        SNK_REQUIRE(P.n_obs == 0 || (P.obs_img && P.obs_pt && P.obs_uv && P.obs_depth && P.obs_weight), "NULL observation arrays");
-        SNK_REQUIRE(P.n_rpc >= 0 && (P.n_rpc == 0 || P.rpc != nullptr), "bad relative pose constraints");
-    }
-    struct PreProb
-    {
-        int nfc, no;
-        size_t img_at, pt_at, ps_at, obs_at;
-        int orig_at;
-        char dup;  // one camera twice on a point (device-built block entries are then off)
-        char k_over8;  // a point with more than eight free observations (work items of up to 128 points are then off)
-    };
-    std::vector<PreProb> pre((size_t)count);
-    static const int host_threads_env = getenv("SNK_BA_HOST_THREADS") ? atoi(getenv("SNK_BA_HOST_THREADS")) : 0;
-    int n_threads = 1;
-    if (count >= 16)
-    {
-        // up to 32 threads (round 6; 16 before): on the 256-thread hosts of the MI355X boxes a 1024-window hand-over builds its lists in 35
-        // instead of 53 ms with 32, no faster with 64 (profiles/r06/r06i_ba_handover_threads_before.txt)
-        n_threads = host_threads_env > 0 ? host_threads_env : (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
-        n_threads = std::min(n_threads, count / 8);
-    }
-    else if (host_threads_env > 0 && count >= 2)
-        n_threads = std::min(host_threads_env, count);  // tests force the threaded form on small batches
-    std::atomic<bool> worker_failed{false};
-    int pf_lo = 0, pf_hi = count;  // the problems a parallel_for covers (the fill pass of a batch runs in chunks, see below)
-    auto parallel_for = [&](auto&& body)
-    {
-        const int lo = pf_lo, hi = pf_hi;
-        if (n_threads <= 1)
-        {
-            for (int b = lo; b < hi; ++b) body(b);
-            return;
-        }
-        std::atomic<int> next{lo};
-        // an exception in a worker (the vectors it grows: std::bad_alloc) must not reach std::terminate: it is caught, the remaining
-        // work is abandoned and the caller turns worker_failed into an error code after the pass
-        const std::function<void()> work = [&]()
-        {
-            try
-            {
-                for (;;)
-                {
-                    const int b0 = next.fetch_add(8);
-                    if (b0 >= hi || worker_failed.load(std::memory_order_relaxed)) return;
-                    for (int b = b0; b < std::min(b0 + 8, hi); ++b) body(b);
-                }
-            }
-            catch (...)
-            {
-                worker_failed.store(true);
-            }
-        };
-        static const bool no_pool = getenv("SNK_BA_NO_HOST_POOL") != nullptr;  // A/B: threads created and joined per pass (rounds 4-6)
-        if (!no_pool)
-        {
-            h->pool.run(n_threads - 1, work);
-            return;
-        }
-        std::vector<std::thread> pool;
-        try
-        {
-            for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
-        }
-        catch (...)
-        {
-            worker_failed.store(true);  // thread creation failed: the threads that exist finish, this thread does the rest
-        }
-        work();
-        for (auto& t : pool) t.join();
-    };
-    parallel_for([&](int b)
-    {
-        const snk_ba_problem& P = problems[b];
-        PreProb& q = pre[(size_t)b];
-        q.nfc = 0;
-        for (int i = 0; i < P.n_img; ++i) q.nfc += P.img_const[i] ? 0 : 1;
-        int no = 0;
-        for (int o = 0; o < P.n_obs; ++o)
-        {
-            const int i = P.obs_img[o], p = P.obs_pt[o];
-            if (i < 0 || i >= P.n_img || p < 0 || p >= P.n_pt) continue;
-            if (P.img_const[i] && P.pt_const[p]) continue;  // reference LocalBundleAdjustment.cpp:286
-            ++no;
-        }
-        q.no  = no;
-        q.dup = 0;
-        q.k_over8 = 0;
-        if (want_big_items && P.n_pt > 0 && P.n_obs > 0)
-        {
-            // work items of up to 128 points need at most 8 free observations per point in EVERY problem
-            std::vector<unsigned char> kfree((size_t)P.n_pt, 0);
-            for (int o = 0; o < P.n_obs; ++o)
-            {
-                const int i = P.obs_img[o], p = P.obs_pt[o];
-                if (i < 0 || i >= P.n_img || p < 0 || p >= P.n_pt || P.img_const[i]) continue;
-                if (++kfree[(size_t)p] > 8) q.k_over8 = 1;
-            }
-        }
-    });
-    if (want_big_items)
-    {
-        big_items = true;
-        for (int b = 0; b < count; ++b) big_items = big_items && !pre[(size_t)b].k_over8;
-    }
-    if (worker_failed.load())
-    {
-        set_error("snk_ba_set_problems: a list-building thread failed (out of host memory?)");
-        return SNK_ERR_HIP;
-    }
-    {
-        size_t a_img = 0, a_pt = 0, a_ps = 0, a_obs = 0;
-        long long a_orig = 0;
-        for (int b = 0; b < count; ++b)
-        {
-            PreProb& q = pre[(size_t)b];
-            q.img_at = a_img, q.pt_at = a_pt, q.ps_at = a_ps, q.obs_at = a_obs, q.orig_at = (int)a_orig;
-            a_img += (size_t)problems[b].n_img, a_pt += (size_t)problems[b].n_pt, a_ps += (size_t)problems[b].n_pt + 1, a_obs += (size_t)q.no;
-            a_orig += problems[b].n_obs;
-            SNK_REQUIRE(a_orig < (1ll << 31) && a_obs < ((size_t)1 << 31), "scene list too large (observations)");
-        }
-        pose.resize(7 * a_img), pt.resize(3 * a_pt), ptc.resize(a_pt), camidx.resize(a_img), ptstart.resize(a_ps);
-        oimg.resize(a_obs), ocam.resize(a_obs), optfree.resize(a_obs), ouv2.resize(2 * a_obs), odepth.resize(a_obs), oweight.resize(a_obs);
-        oorig.resize(a_obs), optidx.resize(a_obs);
-    }
-    auto fill_pass = [&](int b)
-    {
-        const snk_ba_problem& P = problems[b];
-        PreProb& q = pre[(size_t)b];
-        // values
-        if (P.n_img) memcpy(pose.data() + 7 * q.img_at, &P.pose[0][0], (size_t)P.n_img * 7 * sizeof(double));
-        if (P.n_pt) memcpy(pt.data() + 3 * q.pt_at, &P.pt[0][0], (size_t)P.n_pt * 3 * sizeof(double));
-        for (int p = 0; p < P.n_pt; ++p) ptc[q.pt_at + (size_t)p] = P.pt_const[p] ? 1 : 0;
-        // free cameras
-        int* cidx = camidx.data() + q.img_at;
-        int nfc   = 0;
-        for (int i = 0; i < P.n_img; ++i) cidx[i] = P.img_const[i] ? -1 : nfc++;
-        // valid observations, counting sort by point (stable: caller order inside a point)
-        int* pstart = ptstart.data() + q.ps_at;
-        for (int p = 0; p <= P.n_pt; ++p) pstart[p] = 0;
-        std::vector<char> valid((size_t)P.n_obs, 0);
-        for (int o = 0; o < P.n_obs; ++o)
-        {
-            const int i = P.obs_img[o], p = P.obs_pt[o];
-            if (i < 0 || i >= P.n_img || p < 0 || p >= P.n_pt) continue;
-            if (P.img_const[i] && P.pt_const[p]) continue;
-            valid[(size_t)o] = 1;
-            pstart[p + 1]++;
-        }
-        for (int p = 0; p < P.n_pt; ++p) pstart[p + 1] += pstart[p];
-        // the sorted observation arrays, written in ONE pass over the caller's order: position = next free slot of the point
-        const size_t obs_at = q.obs_at;
-        int* q_img = oimg.data() + obs_at, *q_cam = ocam.data() + obs_at, *q_orig = oorig.data() + obs_at, *q_pt = optidx.data() + obs_at;
-        unsigned char* q_free = optfree.data() + obs_at;
-        double *q_uv = ouv2.data() + 2 * obs_at, *q_d = odepth.data() + obs_at, *q_w = oweight.data() + obs_at;
-        // free cameras seen so far per point (device-built block entries: no camera twice on a point)
-        const int seen_words = nfc <= BE_MAX_CAMS ? (nfc + 63) >> 6 : 0;
-        std::vector<unsigned long long> seen((size_t)P.n_pt * (size_t)seen_words, 0ull);
-        std::vector<int> fill(pstart, pstart + P.n_pt);
-        for (int o = 0; o < P.n_obs; ++o)
-        {
-            if (!valid[(size_t)o]) continue;
-            const int i = P.obs_img[o], p = P.obs_pt[o];
-            const int sl = fill[(size_t)p]++;
-            const int c  = cidx[i];
-            if (c >= 0 && seen_words)
-            {
-                const unsigned long long bit = 1ull << (c & 63);
-                unsigned long long& word     = seen[(size_t)p * (size_t)seen_words + (size_t)(c >> 6)];
-                if (word & bit) q.dup = 1;
-                word |= bit;
-            }
-            q_img[sl]  = i;
-            q_cam[sl]  = c;
-            q_free[sl] = P.pt_const[p] ? 0 : 1;
-            q_uv[2 * sl]     = P.obs_uv[o][0];
-            q_uv[2 * sl + 1] = P.obs_uv[o][1];
-            q_d[sl]    = P.obs_depth[o];
-            q_w[sl]    = P.obs_weight[o];
-            q_orig[sl] = q.orig_at + o;
-            q_pt[sl]   = p;
-        }
-    };
-    // ---- batches: the observation arrays (0.65 of a batch's GB) go over the bus WHILE the lists are built (round 6): the fill pass runs in
-    // four chunks of problems, every chunk's ranges of the arrays are sent as soon as they are written (the upload of a 1024-window batch is
-    // ~15 ms of PCIe time that used to start when the last list was done), and pass 3 and the merge below build the rest meanwhile.
-    // Everything sent here is final: the fill pass writes it in place and nothing below touches it.  o_cam, o_ptfree, o_pt and cam_items
-    // are derived on the device (derive_obs_fields, derive_cam_items): reserved, not sent.
-    const bool early_upload = count >= 16;
-    static const int chunks_env = getenv("SNK_BA_FILL_CHUNKS") ? atoi(getenv("SNK_BA_FILL_CHUNKS")) : 0;  // A/B
-    const int n_chunks      = early_upload && count >= 64 ? (chunks_env > 0 ? std::min(chunks_env, count / 16) : BA_FILL_CHUNKS) : 1;
-    if (early_upload)
-    {
-        int rcE;
-#define RSE(buf, vec, T) if ((rcE = h->buf.reserve(std::max<size_t>((vec).size(), 1) * sizeof(T))) != SNK_OK) return rcE
-        RSE(d_pose, pose, double); RSE(d_pt, pt, double); RSE(d_ptc, ptc, unsigned char); RSE(d_camidx, camidx, int); RSE(d_ptstart, ptstart, int);
-        RSE(d_oimg, oimg, int); RSE(d_ouv, ouv2, double); RSE(d_odepth, odepth, double); RSE(d_oweight, oweight, double); RSE(d_oorig, oorig, int);
-        RSE(d_ocam, ocam, int); RSE(d_optfree, optfree, unsigned char); RSE(d_optidx, optidx, int);
-#undef RSE
-    }
-    for (int ck = 0; ck < n_chunks; ++ck)
-    {
-        const int b0 = (int)((long long)count * ck / n_chunks), b1 = (int)((long long)count * (ck + 1) / n_chunks);
-        pf_lo = b0, pf_hi = b1;
-        parallel_for(fill_pass);
-        pf_lo = 0, pf_hi = count;
-        if (worker_failed.load())
-        {
-            set_error("snk_ba_set_problems: a list-building thread failed (out of host memory?)");
-            return SNK_ERR_HIP;
-        }
-        if (!early_upload) continue;
-        // this chunk's ranges of the arrays.  Range ends are rounded outwards to 16 bytes (the copy kernel moves 16-byte words): the few
-        // bytes of a neighbouring chunk that go along are either final already or sent again, later on the same stream, by their own chunk
-        CopyTab tabE;
-        tabE.n = 0;
-        auto part = [&](DevBuf& buf, const void* host, size_t elem, size_t e0, size_t e1, size_t total)
-        {
-            const size_t x0 = (e0 * elem) & ~(size_t)15, x1 = e1 >= total ? total * elem : std::min(total * elem, (e1 * elem + 15) & ~(size_t)15);
-            if (x1 <= x0 || tabE.n >= COPY_TAB_MAX) return;
-            tabE.src[tabE.n]   = static_cast<const char*>(host) + x0;
-            tabE.dst[tabE.n]   = static_cast<char*>(buf.p) + x0;
-            tabE.bytes[tabE.n] = (unsigned)(x1 - x0);
-            ++tabE.n;
-        };
-        const size_t i0 = pre[(size_t)b0].img_at, p0 = pre[(size_t)b0].pt_at, s0 = pre[(size_t)b0].ps_at, o0 = pre[(size_t)b0].obs_at;
-        const bool last = b1 >= count;
-        const size_t i1 = last ? camidx.size() : pre[(size_t)b1].img_at, p1 = last ? ptc.size() : pre[(size_t)b1].pt_at,
-                     s1 = last ? ptstart.size() : pre[(size_t)b1].ps_at, o1 = last ? oimg.size() : pre[(size_t)b1].obs_at;
-        SNK_REQUIRE((o1 - o0 + 1) * 16 < (1ull << 32) && (p1 - p0 + 1) * 24 < (1ull << 32) && (i1 - i0 + 1) * 56 < (1ull << 32),
-                    "scene list too large for the upload table");
-        part(h->d_pose, pose.data(), 56, i0, i1, camidx.size());
-        part(h->d_camidx, camidx.data(), 4, i0, i1, camidx.size());
-        part(h->d_pt, pt.data(), 24, p0, p1, ptc.size());
-        part(h->d_ptc, ptc.data(), 1, p0, p1, ptc.size());
-        part(h->d_ptstart, ptstart.data(), 4, s0, s1, ptstart.size());
-        part(h->d_oimg, oimg.data(), 4, o0, o1, oimg.size());
-        part(h->d_ouv, ouv2.data(), 16, o0, o1, oimg.size());
-        part(h->d_odepth, odepth.data(), 8, o0, o1, oimg.size());
-        part(h->d_oweight, oweight.data(), 8, o0, o1, oimg.size());
-        part(h->d_oorig, oorig.data(), 4, o0, o1, oimg.size());
-        if (tabE.n > 0)
-        {
-            unsigned big = 0;
-            for (int e = 0; e < tabE.n; ++e) big = std::max(big, tabE.bytes[e]);
-            const int gxe = (int)std::min(256u, std::max(16u, big >> 16));
-            hipLaunchKernelGGL(copy_table_kernel, dim3(gxe, tabE.n), dim3(256), 0, h->stream, tabE);
-            SNK_LAUNCH_CHECK();
-        }
-    }
-    mark(0);
-    mark(1);
-    // ---- pass 3: the camera lists and the point-major lists of every problem, built with PROBLEM-LOCAL offsets on the host threads; the
-    // per-problem loop below appends them to the shared lists and relocates the offsets (positions in setpts / setpairs / cblkitems / ccitems,
-    // partial-sum, camera-partial and record indices) by the running totals -- the same lists the serial builder wrote ----
-    struct Built
-    {
-        std::vector<int> camstart, camitems;
-        int be_nch          = 0;
-        long long ent_bound = 0;
-        bool ok = false, cam_sums_bad = false;
-        std::vector<SetItem> items;
-        std::vector<int2> ipts;
-        std::vector<int> ipairs;
-        int parts = 0, cparts = 0;
-        long long recs = 0;
-        int max_pairs = 0, max_run = 0, max_k = 0;
-        std::vector<int> cblkstart, cblkitems, ccstart, ccitems;
-        std::vector<int> wv;  // point_wave work items (first point of each, then n_pt); empty: a point has more than 64 observations
-        bool wv_ok = false;
-    };
-    // where the per-problem loop below puts a problem's lists in the shared ones: the loop only takes the decisions and does the
-    // arithmetic of the running totals; the element copies (with their relocations) run on the host threads afterwards (round 6: the
-    // loop's push_back relocations were ~6 of a 1024-window hand-over's 23 ms of list time)
-    struct MergeAt
-    {
-        size_t wvpt, camstart, camitems, ccstart, ccitems, setitems, setpts, setpairs, cblkstart, cblkitems;
-        int base_parts, base_cparts;
-        long long base_rec;
-        bool set;
-    };
-    std::vector<MergeAt> at((size_t)count);
-    size_t n_wvpt = 0, n_camstart = 0, n_camitems = 0, n_ccstart = 0, n_ccitems = 0, n_setitems = 0, n_setpts = 0, n_setpairs = 0, n_cblkstart = 0,
-           n_cblkitems = 0;
-    std::vector<Built> built((size_t)count);
-    parallel_for([&](int b)
-    {
-        const snk_ba_problem& P = problems[b];
-        const PreProb& pq       = pre[(size_t)b];
-        Built& B                = built[(size_t)b];
-        const int nfc = pq.nfc, no = pq.no;
-        const int* const pstart = ptstart.data() + pq.ps_at;
-        const int* const s_cam  = ocam.data() + pq.obs_at;
-        // camera lists
-        {
-            std::vector<int> cs((size_t)nfc + 1, 0);
-            for (int s = 0; s < no; ++s)
-                if (s_cam[(size_t)s] >= 0) cs[(size_t)s_cam[(size_t)s] + 1]++;
-            for (int c = 0; c < nfc; ++c) cs[(size_t)c + 1] += cs[(size_t)c];
-            std::vector<int> items((size_t)cs[(size_t)nfc]);
-            std::vector<int> fill(cs.begin(), cs.end() - 1);
-            for (int s = 0; s < no; ++s)
-                if (s_cam[(size_t)s] >= 0) items[(size_t)fill[(size_t)s_cam[(size_t)s]]++] = s;
-            B.camstart.assign(cs.begin(), cs.end());
-            B.camitems.swap(items);
-            
-            int longest = 0;
-            for (int c = 0; c < nfc; ++c) longest = std::max(longest, cs[(size_t)c + 1] - cs[(size_t)c]);
-            B.be_nch = ceil_div(longest, 64);
-            // (the same list as static records -- what cam_pass streams -- is gathered on the device: gather_cam_records)
-        }
-        {
-            // room for the block entries when the device builds them: every pair of a point's run is the most there can be
-            long long bound = 0;
-            for (int p = 0; p < P.n_pt; ++p)
-            {
-                const long long run = pstart[(size_t)p + 1] - pstart[(size_t)p];
-                bound += run * run;
-            }
-            B.ent_bound = bound;
-        }
-        // point_wave work items: consecutive whole points with <= 64 observations in total
-        {
-            bool ok = true;
-            std::vector<int>& wv = B.wv;
-            int p = 0;
-            while (p < P.n_pt && ok)
-            {
-                wv.push_back(p);
-                int n = 0, q = p;
-                while (q < P.n_pt && q - p < 64 && n + (pstart[(size_t)q + 1] - pstart[(size_t)q]) <= 64)
-                {
-                    n += pstart[(size_t)q + 1] - pstart[(size_t)q];
-                    ++q;
-                }
-                if (q == p) ok = false;  // a point with more than 64 observations: point_pass handles the problem
-                p = q;
-            }
-            if (ok) wv.push_back(P.n_pt);
-            else wv.clear();
-            B.wv_ok = ok;
-        }
-        // point-major Schur pass: points grouped by camera set, work items of <= SET_CHUNK points, per-block lists of
-        // the partial sums they produce
-        {
-            const size_t nb = imp ? 0 : (size_t)nfc * nfc;
-            // camera set -> group: a hash of the signature finds the candidate, the stored signature confirms it (a std::map keyed by
-            // the vectors themselves was 60 ns per point, a third of a batch hand-over's list time)
-            std::unordered_multimap<unsigned long long, int> gid;
-            std::vector<std::vector<int>> gpts;
-            std::vector<std::vector<int>> gsig;
-            auto find_group = [&](const std::vector<int>& key) -> int
-            {
-                unsigned long long hsh = 1469598103934665603ull;
-                for (int v : key) hsh = (hsh ^ (unsigned long long)(unsigned)v) * 1099511628211ull;
-                auto range = gid.equal_range(hsh);
-                for (auto it = range.first; it != range.second; ++it)
-                    if (gsig[(size_t)it->second] == key) return it->second;
-                gid.emplace(hsh, (int)gpts.size());
-                gpts.emplace_back();
-                gsig.push_back(key);
-                return (int)gpts.size() - 1;
-            };
-            std::vector<int> sig;
-            // The point-major kernels (schur_fused / schur_mfma / update_cost) are only chosen when the launch has enough work
-            // items (max_set_items * count >= SNK_BA_SCHUR_SET_MIN_ITEMS, default 256): for the reference's per-keyframe
-            // call -- ONE window of a few thousand points -- their lists are never used, and building + uploading them
-            // (0.8 MB of records alone) was a quarter of the 0.9 ms a scene hand-over cost.  Built for batches and for big
-            // single scenes (global BA); forced when the threshold is lowered by the environment (tests).
-            static const bool sets_forced = getenv("SNK_BA_SCHUR_SET_MIN_ITEMS") != nullptr;
-            bool ok = !imp && nfc > 0 && (count >= 8 || P.n_pt >= 8000 || sets_forced);
-            // points that produce no Schur products (constant points, points seen by constant cameras only) still need their
-            // linearisation (cost, V, b_p): they form groups of their own, keyed by their run length, with no pairs
-            std::vector<int> plain_key;
-            auto plain_group = [&](int p, int run)
-            {
-                // (a signature of `run` times -1 cannot be a set with free cameras: the plain group of that run length)
-                plain_key.assign((size_t)run, -1);
-                gpts[(size_t)find_group(plain_key)].push_back(p);
-            };
-            for (int p = 0; p < P.n_pt && ok; ++p)
-            {
-                const int a0 = pstart[(size_t)p], a1 = pstart[(size_t)p + 1];
-                if (a1 - a0 > SET_MAX_RUN) ok = false;
-                if (a1 == a0) continue;  // a point without observations: nothing to linearise (update_wave keeps it in place)
-                if (P.pt_const[p])
-                {
-                    for (int a = a0; a < a1; ++a)
-                        if (s_cam[(size_t)a] >= 0) B.cam_sums_bad = true;
-                    plain_group(p, a1 - a0);
-                    continue;
-                }
-                sig.clear();
-                int k = 0;
-                for (int a = a0; a < a1; ++a)
-                {
-                    const int c = s_cam[(size_t)a];
-                    sig.push_back(c);
-                    if (c < 0) continue;
-                    ++k;
-                    for (int b = a0; b < a; ++b)
-                        if (s_cam[(size_t)b] == c) ok = false;  // one camera twice on a point: block-major pass only
-                }
-                if (k == 0)
-                {
-                    plain_group(p, a1 - a0);
-                    continue;
-                }
-                if (k > SET_MAX_K || a1 - a0 > SET_MAX_RUN) ok = false;
-                gpts[(size_t)find_group(sig)].push_back(p);
-            }
-            std::vector<std::vector<int>> contrib(nb);
-            std::vector<std::vector<int>> ccontrib((size_t)nfc);  // per free camera: its partial sums in cam_part
-            int cparts = 0;
-            long long recs = 0;  // static observation records of the work items (gathered on the device: gather_set_records)
-            std::vector<SetItem> items;
-            std::vector<int2> ipts;
-            std::vector<int> ipairs;
-            int parts = 0;
-            if (ok)
-            {
-                // groups in order of their first point (std::map order would do as well: any fixed order)
-                for (size_t g = 0; g < gpts.size(); ++g)
-                {
-                    const std::vector<int>& sig = gsig[g];
-                    const int pair_off = (int)((size_t)0 + ipairs.size());
-                    std::vector<int> blocks;
-                    for (size_t i = 0; i < sig.size(); ++i)
-                        for (size_t j = i; j < sig.size(); ++j)
-                        {
-                            if (sig[i] < 0 || sig[j] < 0) continue;
-                            const bool sw = sig[i] > sig[j];
-                            const int ra = (int)(sw ? j : i), rb = (int)(sw ? i : j);
-                            ipairs.push_back(ra | (rb << 8));
-                            blocks.push_back(sig[(size_t)ra] * nfc + sig[(size_t)rb]);
-                        }
-                    const int npairs = (int)blocks.size();
-                    // matrix-core form (schur_mfma): the point's free rows ordered by camera index, so that every pair
-                    // (ra, rb) -- camera(ra) < camera(rb) -- lies in the upper triangle of Y W^T, and the slot of each
-                    const int aux_off = (int)((size_t)0 + ipairs.size());
-                    std::vector<int> fcams;  // the set's free cameras in ascending order (= the order of the k run positions)
-                    {
-                        std::vector<int> fpos;
-                        for (size_t i = 0; i < sig.size(); ++i)
-                            if (sig[i] >= 0) fpos.push_back((int)i);
-                        std::sort(fpos.begin(), fpos.end(), [&](int a, int b) { return sig[(size_t)a] < sig[(size_t)b]; });
-                        const int kf = (int)fpos.size();
-                        for (int v : fpos) ipairs.push_back(v);
-                        for (int v : fpos) fcams.push_back(sig[(size_t)v]);
-                        for (int i = 0; i < kf; ++i)
-                            for (int j = 0; j < kf; ++j)
-                            {
-                                int slot = -1;
-                                if (i <= j)
-                                    for (int q = 0; q < npairs; ++q)
-                                        if (ipairs[(size_t)(pair_off - (int)(size_t)0) + (size_t)q] == (fpos[(size_t)i] | (fpos[(size_t)j] << 8))) slot = q;
-                                ipairs.push_back(slot);
-                            }
-                        B.max_k = std::max(B.max_k, kf);
-                    }
-                    const size_t chunk    = big_items ? SET_CHUNK_BIG : SET_CHUNK;
-                    const size_t n_in_set = gpts[g].size(), n_cuts = (n_in_set + chunk - 1) / chunk;
-                    size_t cut = (n_in_set + n_cuts - 1) / n_cuts;  // equal items: a launch ends with its longest item
-                    {
-                        // schur_fused linearises 64 / run points at a time: whole groups of that many per item where possible
-                        const size_t grp = std::min<size_t>(64 / std::max<size_t>(sig.size(), 1), 16);  // SF_GMAX
-                        cut = std::min<size_t>((cut + grp - 1) / grp * grp, big_items ? 128 : 64);
-                    }
-                    for (size_t q0 = 0; q0 < n_in_set; q0 += cut)
-                    {
-                        SetItem si;
-                        si.pts_off  = (int)((size_t)0 + ipts.size());
-                        si.n_pts    = (int)std::min<size_t>(cut, n_in_set - q0);
-                        si.pair_off = pair_off;
-                        si.npairs   = npairs;
-                        si.part_off = parts;
-                        si.run      = (int)sig.size();
-                        si.aux_off  = aux_off;
-                        si.nfree    = 0;
-                        si.rec_off  = (int)recs;
-                        for (int v : sig) si.nfree += v >= 0 ? 1 : 0;
-                        si.cpart_off = cparts;
-                        for (int f = 0; f < si.nfree; ++f) ccontrib[(size_t)fcams[(size_t)f]].push_back(cparts + f);
-                        cparts += si.nfree;
-                        for (int q = 0; q < si.n_pts; ++q)
-                        {
-                            const int pp = gpts[g][q0 + (size_t)q];
-                            ipts.push_back(make_int2(pp, pstart[(size_t)pp]));
-                        }
-                        recs += (long long)si.n_pts * si.run;
-                        if (recs >= (1ll << 31)) ok = false;  // (would not be addressable by rec_off: the block-major pass then)
-                        for (int q = 0; q < npairs; ++q) contrib[(size_t)blocks[(size_t)q]].push_back(parts + q);
-                        parts += npairs;
-                        items.push_back(si);
-                        B.max_pairs = std::max(B.max_pairs, npairs);
-                        B.max_run   = std::max(B.max_run, si.run);
-                    }
-                }
-            }
-            {
-                int crun = 0;
-                for (int c = 0; c < nfc; ++c)
-                {
-                    B.ccstart.push_back(crun);
-                    if (ok)
-                    {
-                        B.ccitems.insert(B.ccitems.end(), ccontrib[(size_t)c].begin(), ccontrib[(size_t)c].end());
-                        crun += (int)ccontrib[(size_t)c].size();
-                    }
-                }
-                B.ccstart.push_back(crun);
-            }
-            B.ok = ok;
-            if (ok)
-            {
-                B.items.swap(items);
-                B.ipts.swap(ipts);
-                B.ipairs.swap(ipairs);
-                B.parts  = parts;
-                B.cparts = cparts;
-                B.recs   = recs;
-            }
-            int run = 0;
-            B.cblkstart.resize(nb + 1);
-            int* cb = B.cblkstart.data();
-            for (size_t k = 0; k < nb; ++k)
-            {
-                cb[k] = run;
-                if (ok && !contrib[k].empty())
-                {
-                    B.cblkitems.insert(B.cblkitems.end(), contrib[k].begin(), contrib[k].end());
-                    run += (int)contrib[k].size();
-                }
-            }
-            cb[nb] = run;
-        }
-    });
-    if (worker_failed.load())
-    {
-        set_error("snk_ba_set_problems: a list-building thread failed (out of host memory?)");
-        return SNK_ERR_HIP;
-    }
-    mark(3);
-    for (int b = 0; b < count; ++b)
-    {
-        const snk_ba_problem& P = problems[b];
-        mark(7);
-        SNK_REQUIRE(P.n_img >= 0 && P.n_pt >= 0 && P.n_obs >= 0, "negative problem size");
-        SNK_REQUIRE(P.n_img == 0 || (P.pose && P.img_const), "NULL pose arrays");
-        SNK_REQUIRE(P.n_pt == 0 || (P.pt && P.pt_const), "NULL point arrays");
-        SNK_REQUIRE(P.n_obs == 0 || (P.obs_img && P.obs_pt && P.obs_uv && P.obs_depth && P.obs_weight), "NULL observation arrays");
-        SNK_REQUIRE(P.n_rpc >= 0 && (P.n_rpc == 0 || P.rpc != nullptr), "bad relative pose constraints");
-        Prob& pr = probs[(size_t)b];
-        memset(&pr, 0, sizeof(pr));
-        pr.ni = P.n_img;
-        pr.np = P.n_pt;
-        for (int k = 0; k < 4; ++k) pr.K[k] = P.K[k];
-        pr.bf       = P.bf;
-        pr.img_off  = img_off;
-        pr.pt_off   = pt_off;
-        pr.obs_off  = obs_off;
-        pr.cam_off  = cam_off;
-        pr.orig_off = orig_off;
-        pr.vec_off  = vec_off;
-        pr.s_off    = s_off;
-        h->orig_off[(size_t)b] = orig_off;
-        h->orig_n[(size_t)b]   = P.n_obs;
-        // values, free-camera indices, counting sort and the sorted observation arrays: written by the fill pass above
-        const PreProb& pq = pre[(size_t)b];
-        const int nfc     = pq.nfc;
-        const int* const cidx = camidx.data() + pq.img_at;
-        pr.nfc = nfc;
-        pr.n6  = 6 * nfc;
-        const int no = pq.no;
-        pr.no        = no;
-        pr.ptstart_off = (int)pq.ps_at;
-        if (pq.dup) dev_entries_ok = false;
-        const Built& B = built[(size_t)b];
-        MergeAt& M     = at[(size_t)b];
-        // point_wave work items (built in pass 3)
-        pr.wv_off = (int)n_wvpt;
-        pr.n_wv   = 0;
-        M.wvpt    = n_wvpt;
-        if (B.wv_ok)
-        {
-            pr.n_wv = (int)B.wv.size() - 1;
-            n_wvpt += B.wv.size();
-            max_wv = std::max(max_wv, pr.n_wv);
-        }
-        else
-            wave_ok = false;
-        mark(2);
-        // camera lists (built in pass 3; positions and items are problem-local: appended as they are)
-        pr.camstart_off = (int)n_camstart;
-        pr.citem_off    = (int)n_camitems;
-        M.camstart = n_camstart, M.camitems = n_camitems;
-        n_camstart += B.camstart.size();
-        n_camitems += B.camitems.size();
-        max_citems = std::max(max_citems, (int)B.camitems.size());
-        pr.be_nch  = B.be_nch;
-        if (nfc > BE_MAX_CAMS) dev_entries_ok = false;
-        ent_bound[(size_t)b] = B.ent_bound;
-        pr.blkstart_off = blkstart_total;
-        if (!imp) blkstart_total += nfc * nfc + 1;
-        mark(3);
-        mark(4);
-        // point-major Schur pass (built in pass 3 with problem-local offsets): append, relocating by the running totals
-        pr.set_off  = (int)n_setitems;
-        pr.cblk_off = (int)n_cblkstart;
-        pr.n_set    = 0;
-        {
-            if (B.cam_sums_bad) cam_sums_ok = false;
-            max_set_k     = std::max(max_set_k, B.max_k);
-            max_set_pairs = std::max(max_set_pairs, B.max_pairs);
-            max_set_run   = std::max(max_set_run, B.max_run);
-            pr.ccam_off = (int)n_ccstart;
-            M.ccstart = n_ccstart, M.ccitems = n_ccitems;  // ccstart entries + base_cc (= M.ccitems), ccitems entries + base_cparts
-            n_ccstart += B.ccstart.size();
-            n_ccitems += B.ccitems.size();
-            M.base_parts = n_partials, M.base_cparts = n_cparts, M.base_rec = n_setrec;
-            // the batch's record / partial-sum counters are 32-bit on the device: a batch that would overflow them keeps the block-major pass
-            // (what the serial builder of round 3 did), it is not an error
-            const bool set_fits = n_setrec + B.recs < (1ll << 31) && (long long)n_partials + B.parts < (1ll << 31);
-            M.set = B.ok && set_fits;
-            M.setitems = n_setitems, M.setpts = n_setpts, M.setpairs = n_setpairs;
-            if (M.set)
-            {
-                n_setitems += B.items.size();
-                n_setpts += B.ipts.size();
-                n_setpairs += B.ipairs.size();
-                pr.n_set      = (int)B.items.size();
-                max_set_items = std::max(max_set_items, pr.n_set);
-            }
-            else
-                set_ok = false;
-            M.cblkstart = n_cblkstart, M.cblkitems = n_cblkitems;  // cblkstart entries + base_cb (= M.cblkitems), cblkitems entries + base_parts
-            n_cblkstart += B.cblkstart.size();
-            n_cblkitems += B.cblkitems.size();
-            if (M.set)
-            {
-                n_partials += B.parts;
-                n_cparts += B.cparts;
-                n_setrec += B.recs;
-            }
-        }
-        mark(5);
-        // relative pose constraints (IMU scenes): valid ones, per-camera incidence, per-block chains
-        {
-            pr.rpc_off    = (int)rpcmeta.size();
-            pr.camrpc_off = (int)camrpcstart.size();
-            std::vector<int> cs((size_t)nfc + 1, 0);
-            std::vector<RpcMeta> mine;
-            for (int k = 0; k < P.n_rpc; ++k)
-            {
-                const snk_ba_rpc& q = P.rpc[k];
-                if (q.img1 < 0 || q.img2 < 0 || q.img1 >= P.n_img || q.img2 >= P.n_img || q.img1 == q.img2) continue;
-                if (P.img_const[q.img1] && P.img_const[q.img2]) continue;
-                SNK_REQUIRE(q.weight_rotation >= 0.0 && q.weight_translation >= 0.0, "negative constraint weight");
-                RpcMeta m;
-                m.img1 = q.img1; m.img2 = q.img2;
-                m.c1 = cidx[(size_t)q.img1]; m.c2 = cidx[(size_t)q.img2];
-                for (int t = 0; t < 7; ++t) m.rel[t] = q.rel_pose[t];
-                m.w_rot = q.weight_rotation; m.w_trans = q.weight_translation;
-                mine.push_back(m);
-                if (m.c1 >= 0) cs[(size_t)m.c1 + 1]++;
-                if (m.c2 >= 0) cs[(size_t)m.c2 + 1]++;
-            }
-            pr.n_rpc = (int)mine.size();
-            max_rpc  = std::max(max_rpc, pr.n_rpc);
-            for (int c = 0; c < nfc; ++c) cs[(size_t)c + 1] += cs[(size_t)c];
-            const int item_base = (int)camrpcitems.size();
-            std::vector<int> items((size_t)cs[(size_t)nfc]), fill(cs.begin(), cs.end() - 1);
-            // the per-block chains are only read for problems that HAVE constraints: the others advance the offset and write nothing
-            // (implicit form: no per-block chains -- its camera phase walks the per-camera lists)
-            std::vector<int> brpc(mine.empty() || imp ? 0 : (size_t)nfc * nfc, 0), nxt(mine.size(), 0);
-            for (int k = 0; k < (int)mine.size(); ++k)
-            {
-                const RpcMeta& m = mine[(size_t)k];
-                if (m.c1 >= 0) items[(size_t)fill[(size_t)m.c1]++] = k * 2;
-                if (m.c2 >= 0) items[(size_t)fill[(size_t)m.c2]++] = k * 2 + 1;
-                if (m.c1 >= 0 && m.c2 >= 0 && !imp)
-                {
-                    // the upper block (lo, hi) holds J(lo)^T J(hi): H12 when img1 is `lo`, its transpose otherwise
-                    const int lo = std::min(m.c1, m.c2), hi = std::max(m.c1, m.c2);
-                    const int code = 1 + (k * 2 + (m.c1 == lo ? 0 : 1));
-                    nxt[(size_t)k]                 = brpc[(size_t)lo * nfc + hi];
-                    brpc[(size_t)lo * nfc + hi] = code;
-                }
-            }
-            for (int c = 0; c <= nfc; ++c) camrpcstart.push_back(item_base + cs[(size_t)c]);
-            camrpcitems.insert(camrpcitems.end(), items.begin(), items.end());
-            if (!mine.empty() && !imp)
-            {
-                blkrpc.resize(blkrpc_logical, 0);  // zeros for the problems without constraints in front of this one
-                blkrpc.insert(blkrpc.end(), brpc.begin(), brpc.end());
-            }
-            if (!imp) blkrpc_logical += (size_t)nfc * nfc;
-            rpcnext.insert(rpcnext.end(), nxt.begin(), nxt.end());
-            rpcmeta.insert(rpcmeta.end(), mine.begin(), mine.end());
-        }
-        mark(6);
-        img_off += P.n_img;
-        pt_off += P.n_pt;
-        obs_off += no;
-        cam_off += nfc;
-        orig_off += P.n_obs;
-        vec_off += pr.n6;
-        if (!imp) s_off += (long long)pr.n6 * pr.n6;
-        max_np  = std::max(max_np, P.n_pt);
-        max_ni  = std::max(max_ni, P.n_img);
-        max_nfc = std::max(max_nfc, nfc);
-        max_n6  = std::max(max_n6, pr.n6);
-    }
-    // ---- the element copies the loop above left out: every problem's lists into its ranges of the shared lists, relocated, on the host
-    // threads (disjoint ranges, no locks) ----
-    wvpt.resize(n_wvpt), camstart.resize(n_camstart), camitems.resize(n_camitems), ccstart.resize(n_ccstart), ccitems.resize(n_ccitems);
-    setitems.resize(n_setitems), setpts.resize(n_setpts), setpairs.resize(n_setpairs), cblkstart.resize(n_cblkstart), cblkitems.resize(n_cblkitems);
-    parallel_for([&](int b)
-    {
-        const Built& B   = built[(size_t)b];
-        const MergeAt& M = at[(size_t)b];
-        auto put = [](auto& dst, size_t pos, const auto& src)
-        {
-            if (!src.empty()) memcpy(dst.data() + pos, src.data(), src.size() * sizeof(src[0]));
-        };
-        if (B.wv_ok) put(wvpt, M.wvpt, B.wv);
-        put(camstart, M.camstart, B.camstart);
-        put(camitems, M.camitems, B.camitems);
-        {
-            int* d = ccstart.data() + M.ccstart;
-            for (size_t k = 0; k < B.ccstart.size(); ++k) d[k] = B.ccstart[k] + (int)M.ccitems;
-            d = ccitems.data() + M.ccitems;
-            for (size_t k = 0; k < B.ccitems.size(); ++k) d[k] = B.ccitems[k] + M.base_cparts;
-            d = cblkstart.data() + M.cblkstart;
-            for (size_t k = 0; k < B.cblkstart.size(); ++k) d[k] = B.cblkstart[k] + (int)M.cblkitems;
-            d = cblkitems.data() + M.cblkitems;
-            for (size_t k = 0; k < B.cblkitems.size(); ++k) d[k] = B.cblkitems[k] + M.base_parts;
-        }
-        if (M.set)
-        {
-            SetItem* d = setitems.data() + M.setitems;
-            for (size_t k = 0; k < B.items.size(); ++k)
-            {
-                SetItem si = B.items[k];
-                si.pts_off += (int)M.setpts;
-                si.pair_off += (int)M.setpairs;
-                si.aux_off += (int)M.setpairs;
-                si.part_off += M.base_parts;
-                si.cpart_off += M.base_cparts;
-                si.rec_off += (int)M.base_rec;
-                d[k] = si;
-            }
-            put(setpts, M.setpts, B.ipts);
-            put(setpairs, M.setpairs, B.ipairs);
-        }
-    });
-    if (worker_failed.load())
-    {
-        set_error("snk_ba_set_problems: a list-building thread failed (out of host memory?)");
-        return SNK_ERR_HIP;
-    }
+    const int count = h->count, max_n6 = h->max_n6, max_nfc = h->max_nfc, max_np = h->max_np, vec_off = h->tot_vec, cam_off = h->tot_cam;
+    const bool imp   = h->implicit;
+    const size_t npt = (size_t)std::max(h->tot_pt, 1);
+    int rc;
     const size_t pcg_lds = (size_t)max_n6 * 9 * 8 + (size_t)max_nfc * 36 * 8;
     // S (and the vectors) of the largest problem fit one workgroup's LDS -> one workgroup per problem;
     // otherwise the multi-workgroup PCG (measured: 120 keyframes 38 ms -> 9 ms, 600 keyframes 21 ms)
     h->pcg_large = !imp && pcg_lds + (size_t)max_n6 * max_n6 * 8 > 158 * 1024;
-    h->probs.assign(probs.begin(), probs.end());
-    h->count = count;
-    h->tot_img = img_off; h->tot_pt = pt_off; h->tot_obs = obs_off; h->tot_cam = cam_off; h->tot_orig = orig_off;
-    h->tot_vec = vec_off; h->tot_s = s_off;
-    h->max_np = max_np; h->max_nfc = max_nfc; h->max_n6 = max_n6; h->max_ni = max_ni;
-    h->max_wv = max_wv;
-    h->max_rpc = max_rpc;
-    h->point_wave_ok = wave_ok && max_wv > 0;
-
-    // block entries: on the device when every problem qualifies, by the host builder otherwise
-    static const bool host_entries = getenv("SNK_BA_HOST_ENTRIES") != nullptr;  // A/B and tests
-    bool dev_entries = dev_entries_ok && !host_entries && !imp;
-    if (dev_entries)
-    {
-        // The device builder counts into nfc x chunks x nfc ints per problem -- quadratic in the free cameras.  A global BA with
-        // ~500 free cameras and one long camera list needs hundreds of megabytes of counters the host builder never allocates:
-        // beyond a modest budget (64 MB; a batch of 1024 local windows needs 1.6 MB) the host builder takes over.
-        long long cnt = 0;
-        for (int b = 0; b < count; ++b) cnt += (long long)probs[(size_t)b].nfc * probs[(size_t)b].be_nch * probs[(size_t)b].nfc;
-        static const long long budget = getenv("SNK_BA_BECNT_BUDGET") ? atoll(getenv("SNK_BA_BECNT_BUDGET")) : (64ll << 20);  // bytes; tests force the fallback
-        if (cnt * (long long)sizeof(int) > budget) dev_entries = false;
-    }
-    long long ent_total = 0, becnt_total = 0;
-    int max_be_waves = 0;
-    if (dev_entries)
-    {
-        for (int b = 0; b < count; ++b)
-        {
-            Prob& pr = probs[(size_t)b];
-            SNK_REQUIRE(ent_total + ent_bound[(size_t)b] < (1ll << 31), "scene list too large (block entries)");
-            pr.ent_off   = (int)ent_total;
-            pr.becnt_off = (int)becnt_total;
-            ent_total += ent_bound[(size_t)b];
-            becnt_total += (long long)pr.nfc * pr.be_nch * pr.nfc;
-            SNK_REQUIRE(becnt_total < (1ll << 31), "scene list too large (block entry counters)");
-            max_be_waves = std::max(max_be_waves, pr.nfc * pr.be_nch);
-        }
-    }
-    else if (!imp)
-    {
-        long long bound = 0;
-        for (int b = 0; b < count; ++b) bound += ent_bound[(size_t)b];
-        LS.blkent.reserve((size_t)bound);  // one pinned allocation instead of a doubling chain
-        LS.blkstart.reserve((size_t)blkstart_total);
-        for (int b = 0; b < count; ++b)
-        {
-            probs[(size_t)b].be_nch  = 0;
-            probs[(size_t)b].ent_off = (int)blkent.size();
-            host_block_entries(b, LS.blkstart, LS.blkent);
-        }
-    }
-    h->probs.assign(probs.begin(), probs.end());  // again: with the block-entry offsets
-    mark(4);
-    int rc;
-    hipStream_t st = h->stream;
-    const auto t_lists = std::chrono::steady_clock::now();
-    CopyTab tab;
-    tab.n = 0;
-#define UP(buf, vec) if ((rc = upload(h->buf, vec, tab)) != SNK_OK) return rc
-    UP(d_prob, probs);
-    // batches: the second and third copies of the poses / points (the reset state, the trial points) are device-to-device copies behind
-    // the upload instead of two more trips over the bus (round 6: 100 MB of a 1024-window hand-over's 1.1 GB); a single window keeps the
-    // one launch
-    const bool dup_on_device = count >= 16;
-    CopyTab tab2;
-    tab2.n = 0;
-    auto dup = [&](DevBuf& dst, const DevBuf& src, size_t bytes) -> int
-    {
-        int rc2 = dst.reserve(std::max<size_t>(bytes, 1));
-        if (rc2 != SNK_OK || bytes == 0) return rc2;
-        SNK_REQUIRE(tab2.n < COPY_TAB_MAX && bytes < (1ull << 32), "scene list too large for the upload table");
-        tab2.src[tab2.n] = src.p, tab2.dst[tab2.n] = dst.p, tab2.bytes[tab2.n] = (unsigned)bytes;
-        ++tab2.n;
-        return SNK_OK;
-    };
-    if (!early_upload) { UP(d_pose, pose); }
-    if (!dup_on_device) { UP(d_pose0, pose); }
-    else if ((rc = dup(h->d_pose0, h->d_pose, pose.size() * sizeof(double))) != SNK_OK) return rc;
-    if (!early_upload) { UP(d_pt, pt); }
-    if (!dup_on_device) { UP(d_pt0, pt); }
-    else if ((rc = dup(h->d_pt0, h->d_pt, pt.size() * sizeof(double))) != SNK_OK) return rc;
-    if (!early_upload)
-    {
-        UP(d_ptc, ptc);
-        UP(d_camidx, camidx);
-        UP(d_ptstart, ptstart);
-        UP(d_oimg, oimg);
-        UP(d_ocam, ocam);
-        UP(d_optfree, optfree);
-        UP(d_ouv, ouv2);
-        UP(d_odepth, odepth);
-        UP(d_oweight, oweight);
-        UP(d_oorig, oorig);
-    }
-    UP(d_camstart, camstart);
-    if (!early_upload) { UP(d_camitems, camitems); }
-    else if ((rc = h->d_camitems.reserve(std::max<size_t>(camitems.size(), 1) * sizeof(int))) != SNK_OK) return rc;
-    if ((rc = h->d_csobs.reserve(std::max<size_t>(camitems.size(), 1) * sizeof(CamObs))) != SNK_OK) return rc;  // gather_cam_records
-    UP(d_setitems, setitems);
-    if ((rc = h->d_setobs.reserve((size_t)std::max<long long>(n_setrec, 1) * sizeof(SetObs))) != SNK_OK) return rc;  // gather_set_records
-    UP(d_setpts, setpts);
-    UP(d_setpairs, setpairs);
-    UP(d_cblkstart, cblkstart);
-    UP(d_cblkitems, cblkitems);
-    UP(d_ccstart, LS.ccstart);
-    UP(d_ccitems, LS.ccitems);
-    if (dev_entries)
-    {
-        if ((rc = h->d_blkstart.reserve((size_t)std::max(blkstart_total, 1) * sizeof(int))) != SNK_OK) return rc;
-        if ((rc = h->d_blkent.reserve((size_t)std::max<long long>(ent_total, 1) * sizeof(int4))) != SNK_OK) return rc;
-        if ((rc = h->d_becnt.reserve((size_t)std::max<long long>(becnt_total, 1) * sizeof(int))) != SNK_OK) return rc;
-    }
-    else
-    {
-        UP(d_blkstart, blkstart);
-        UP(d_blkent, blkent);
-    }
-    if (!early_upload) { UP(d_optidx, optidx); }
-    UP(d_wvpt, wvpt);
-    UP(d_rpcmeta, rpcmeta);
-    UP(d_rpcnext, rpcnext);
-    UP(d_camrpcstart, camrpcstart);
-    UP(d_camrpcitems, camrpcitems);
-    UP(d_blkrpc, blkrpc);
-    if (!dup_on_device) { UP(d_pt_new, pt); }  // points without observations stay put
-    else if ((rc = dup(h->d_pt_new, h->d_pt, pt.size() * sizeof(double))) != SNK_OK) return rc;
-    const auto t_up = std::chrono::steady_clock::now();
-    const size_t nobs = (size_t)std::max(obs_off, 1), npt = (size_t)std::max(pt_off, 1);
-#define RS(buf, bytes) if ((rc = h->buf.reserve(bytes)) != SNK_OK) return rc
-    RS(d_state, (size_t)count * sizeof(State));
-    RS(d_pose_new, (size_t)std::max(img_off, 1) * 7 * 8);
-    RS(d_pt_new, npt * 3 * 8);
-    RS(d_outlier, (size_t)std::max(orig_off, 1));
-    RS(d_chi2, (size_t)std::max(orig_off, 1) * 8);
-    RS(d_r, nobs * 4 * 8);
-    RS(d_W, nobs * 18 * 8);
-    RS(d_ptv, npt * 6 * 8);
-    RS(d_spart, (size_t)std::max(n_partials, 1) * 36 * 8);
-    RS(d_campart, (size_t)std::max(n_cparts, 1) * CS_TERMS * 8);
-    h->cam_sums_ok = cam_sums_ok;
-    h->set_ok = set_ok && max_set_items > 0;
-    h->max_set_items = max_set_items;
-    h->set_small     = max_set_pairs * 6 <= 4 * 64 && max_set_run * 9 + 3 <= 2 * 64;
-    h->set_k_max     = max_set_k;
-    h->set_run_max   = max_set_run;
-    RS(d_Vinv, npt * 6 * 8);
-    RS(d_bp, npt * 3 * 8);
-    RS(d_cost, npt * 8);
-    RS(d_cost_new, npt * 8);
-    RS(d_U, (size_t)std::max(cam_off, 1) * 36 * 8);
-    RS(d_S, (size_t)std::max<long long>(s_off, 1) * 8);
-    RS(d_rhs, (size_t)std::max(vec_off, 1) * 8);
-    RS(d_x, (size_t)std::max(vec_off, 1) * 8);
-    RS(d_rpcout, std::max<size_t>(rpcmeta.size(), 1) * RPC_STRIDE * 8);
     if (h->pcg_large)
     {
         PcgLarge& W = h->pcgw;
@@ -6232,7 +4482,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         const size_t nv = (size_t)std::max(vec_off, 1), ng = (size_t)count * W.G;
         const size_t doubles = 4 * nv + (size_t)std::max(cam_off, 1) * 36 + (size_t)std::max(W.parts, PERSIST_WGS_MAX / rowchunks + 1) * nv + 5 * ng + (size_t)count * 4 +
                                nv + 6 * (size_t)PERSIST_WGS_MAX + 8;
-        RS(d_pcgw, doubles * 8);
+        if ((rc = h->d_pcgw.reserve(doubles * 8)) != SNK_OK) return rc;
         double* w = h->d_pcgw.as<double>();
         W.r = w;            w += nv;
         W.z = w;            w += nv;
@@ -6318,7 +4568,7 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         const size_t nv = (size_t)std::max(vec_off, 1), ng = (size_t)W.G;
         const size_t doubles = 4 * nv + (size_t)std::max(cam_off, 1) * 36 + (size_t)std::max(cam_off, 1) + 5 * ng + 4 + npt * 3 +
                                (size_t)PERSIST_WGS_MAX + 8;
-        RS(d_pcgw, doubles * 8);
+        if ((rc = h->d_pcgw.reserve(doubles * 8)) != SNK_OK) return rc;
         double* w = h->d_pcgw.as<double>();
         W.r = w;     w += nv;
         W.z = w;     w += nv;
@@ -6348,245 +4598,64 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
         }
         (void)hipGetLastError();
     }
-#undef RS
-#undef UP
-    // ... and the buffers that start as zeros are entries of the same table (source NULL): nine fill launches of ~5 us each
-    // stood between the upload and the first kernel of the solve
-    auto zero = [&](DevBuf& b, size_t bytes) -> int
-    {
-        SNK_REQUIRE(tab.n < COPY_TAB_MAX && bytes < (1ull << 32), "scene list too large for the upload table");
-        tab.src[tab.n] = nullptr, tab.dst[tab.n] = b.p, tab.bytes[tab.n] = (unsigned)bytes;
-        ++tab.n;
-        return SNK_OK;
-    };
-    if ((rc = zero(h->d_outlier, (size_t)std::max(orig_off, 1))) != SNK_OK) return rc;
-    {
-        // the state starts as begin_solve would leave it (the first solve of the scene then needs no launch for that)
-        auto& states = LS.states;
-        State s0{};
-        s0.lambda = make_opt(h->opt).lambda_init;
-        s0.vfac   = 2.0;
-        states.assign((size_t)count, s0);
-        SNK_REQUIRE(tab.n < COPY_TAB_MAX, "scene list too large for the upload table");
-        tab.src[tab.n] = states.data(), tab.dst[tab.n] = h->d_state.p, tab.bytes[tab.n] = (unsigned)(states.size() * sizeof(State));
-        ++tab.n;
-        h->state_fresh = true;
-    }
-    if ((rc = zero(h->d_r, nobs * 4 * 8)) != SNK_OK) return rc;
-    if ((rc = zero(h->d_x, (size_t)std::max(vec_off, 1) * 8)) != SNK_OK) return rc;
-    // points without observations are in no work item of schur_fused: their cost, V^-1 and b_p are zero once and for all
-    if ((rc = zero(h->d_cost, npt * 8)) != SNK_OK) return rc;
-    if ((rc = zero(h->d_cost_new, npt * 8)) != SNK_OK) return rc;
-    if ((rc = zero(h->d_Vinv, npt * 6 * 8)) != SNK_OK) return rc;
-    if ((rc = zero(h->d_bp, npt * 3 * 8)) != SNK_OK) return rc;
-    {
-        // enough workgroups per array to keep the bus busy: one per 64 KB of the largest list, 16 .. 256
-        unsigned big = 0;
-        for (int e = 0; e < tab.n; ++e) big = std::max(big, tab.bytes[e]);
-        // (more workgroups per array do not shorten it: 16.3 / 18.3 / 17.1 / 15.2 us with one per 64 / 16 / 4 / 1 KB, r03ag)
-        const int gx = (int)std::min(256u, std::max(16u, big >> 16));
-        hipLaunchKernelGGL(copy_table_kernel, dim3(gx, tab.n), dim3(256), 0, st, tab);
-        SNK_LAUNCH_CHECK();
-        if (tab2.n > 0)
-        {
-            hipLaunchKernelGGL(copy_table_kernel, dim3(gx, tab2.n), dim3(256), 0, st, tab2);  // stream-ordered behind the upload
-            SNK_LAUNCH_CHECK();
-        }
-    }
     if (!h->pcg_large)
     {
         // process-wide, once, to the most the kernels can use (enqueue_lm keeps S in LDS only when it fits 158 KB)
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pcg_solve<true>), 158 * 1024)) != SNK_OK) return rc;
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pcg_solve<false>), 158 * 1024)) != SNK_OK) return rc;
     }
+    return SNK_OK;
+}
+}  // namespace ba
+}  // namespace snk
 
-    Arrays& A   = h->arr;
-    A.prob      = h->d_prob.as<Prob>();
-    A.state     = h->d_state.as<State>();
-    A.pose      = h->d_pose.as<double>();
-    A.pose_new  = h->d_pose_new.as<double>();
-    A.pt        = h->d_pt.as<double>();
-    A.pt_new    = h->d_pt_new.as<double>();
-    A.pt_const  = h->d_ptc.as<unsigned char>();
-    A.cam_idx   = h->d_camidx.as<int>();
-    A.pt_start  = h->d_ptstart.as<int>();
-    A.o_img     = h->d_oimg.as<int>();
-    A.o_cam     = h->d_ocam.as<int>();
-    A.o_ptfree  = h->d_optfree.as<unsigned char>();
-    A.o_uv      = h->d_ouv.as<double2>();
-    A.o_depth   = h->d_odepth.as<double>();
-    A.o_weight  = h->d_oweight.as<double>();
-    A.o_orig    = h->d_oorig.as<int>();
-    A.o_pt      = h->d_optidx.as<int>();
-    A.wv_pt     = h->d_wvpt.as<int>();
-    A.rpc_meta  = h->d_rpcmeta.as<RpcMeta>();
-    A.rpc_out   = h->d_rpcout.as<double>();
-    A.cam_rpc_start = h->d_camrpcstart.as<int>();
-    A.cam_rpc_items = h->d_camrpcitems.as<int>();
-    A.blk_rpc   = h->d_blkrpc.as<int>();
-    A.rpc_next  = h->d_rpcnext.as<int>();
-    A.outlier   = h->d_outlier.as<unsigned char>();
-    A.o_r       = h->d_r.as<double>();
-    A.o_W       = h->d_W.as<double>();
-    A.ptv       = h->d_ptv.as<double>();
-    A.cs_obs    = h->d_csobs.as<CamObs>();
-    A.set_items = h->d_setitems.as<SetItem>();
-    A.set_obs   = h->d_setobs.as<SetObs>();
-    A.set_pts   = h->d_setpts.as<int2>();
-    A.set_pairs = h->d_setpairs.as<int>();
-    A.cc_start   = h->d_ccstart.as<int>();
-    A.cc_items   = h->d_ccitems.as<int>();
-    A.cam_part   = h->d_campart.as<double>();
-    A.cblk_start = h->d_cblkstart.as<int>();
-    A.cblk_items = h->d_cblkitems.as<int>();
-    A.s_part    = h->d_spart.as<double>();
-    A.Vinv      = h->d_Vinv.as<double>();
-    A.bp        = h->d_bp.as<double>();
-    A.cost_pt   = h->d_cost.as<double>();
-    A.cost_pt_new = h->d_cost_new.as<double>();
-    A.U         = h->d_U.as<double>();
-    A.cam_start = h->d_camstart.as<int>();
-    A.cam_items = h->d_camitems.as<int>();
-    A.blk_start = h->d_blkstart.as<int>();
-    A.blk_ent   = h->d_blkent.as<int4>();
-    A.S         = h->d_S.as<double>();
-    A.rhs       = h->d_rhs.as<double>();
-    A.x         = h->d_x.as<double>();
-    A.chi2      = h->d_chi2.as<double>();
-    // the lists the device builds from the uploaded ones (stream ordered behind copy_table_kernel)
-    if (early_upload)
+extern "C" {
+
+int snk_ba_create(const snk_ba_options* options, int device, void* stream, snk_ba** out)
+{
+    SNK_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    SNK_REQUIRE(options != nullptr, "options is NULL");
+    SNK_REQUIRE(options->max_iterations >= 0 && options->max_pcg_iterations >= 0, "negative iteration count");
+    SNK_REQUIRE(options->huber_mono > 0.0 && options->huber_stereo > 0.0, "Huber thresholds must be > 0");
+    snk_ba* h = new snk_ba();
+    h->opt    = *options;
+    int rc    = h->init(device, stream);
+    if (rc != SNK_OK)
     {
-        if (obs_off > 0)
-        {
-            int max_no = 0;
-            for (int b = 0; b < count; ++b) max_no = std::max(max_no, probs[(size_t)b].no);
-            hipLaunchKernelGGL(derive_obs_fields, dim3(ceil_div(std::max(max_no, 1), 256), count), dim3(256), 0, st, A, h->d_optidx.as<int>(), h->d_ocam.as<int>(),
-                               h->d_optfree.as<unsigned char>());
-            SNK_LAUNCH_CHECK();
-        }
-        if (max_nfc > 0 && max_citems > 0)
-        {
-            hipLaunchKernelGGL(derive_cam_items, dim3(max_nfc, count), dim3(64), 0, st, A, (const int*)h->d_ocam.as<int>(), h->d_camitems.as<int>());
-            SNK_LAUNCH_CHECK();
-        }
+        delete h;
+        return rc;
     }
-    if (max_citems > 0)
-    {
-        hipLaunchKernelGGL(gather_cam_records, dim3(ceil_div(max_citems, 256), count), dim3(256), 0, st, A, h->d_csobs.as<CamObs>());
-        SNK_LAUNCH_CHECK();
-    }
-    if (max_set_items > 0)
-    {
-        hipLaunchKernelGGL(gather_set_records, dim3(max_set_items, count), dim3(256), 0, st, A, h->d_setobs.as<SetObs>());
-        SNK_LAUNCH_CHECK();
-    }
-    // batches that will run the point-major kernels never read the block entries (SNK_BA_CHECK_LISTS=1 builds and checks them anyway)
-    static const bool check_lists_be = getenv("SNK_BA_CHECK_LISTS") != nullptr;
-    const bool skip_entries = dev_entries && count >= 16 && ba_sets_will_run(h) && !check_lists_be;
-    h->blk_built = !skip_entries && !imp;
-    if (dev_entries && !skip_entries)
-    {
-        if (max_be_waves > 0)
-        {
-            hipLaunchKernelGGL(block_entries_count, dim3(max_be_waves, count), dim3(64), 0, st, A, h->d_becnt.as<int>());
-            SNK_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(block_entries_scan, dim3(count), dim3(BE_SCAN_THREADS), 0, st, A, h->d_becnt.as<int>(), h->d_blkstart.as<int>());
-        SNK_LAUNCH_CHECK();
-        if (max_be_waves > 0)
-        {
-            const size_t be_lds = (size_t)((max_nfc + 63) / 64) * 64 * 12;  // ballots (8 B) + bases (4 B) per camera
-            hipLaunchKernelGGL(block_entries_fill, dim3(max_be_waves, count), dim3(64), be_lds, st, A, h->d_becnt.as<int>(), h->d_blkent.as<int4>());
-            SNK_LAUNCH_CHECK();
-        }
-    }
-    const auto t_rs = std::chrono::steady_clock::now();
-    static const bool prof = getenv("SNK_BA_PROFILE_CREATE") != nullptr;  // host-side cost of a scene hand-over, in microseconds
-    static const bool check_lists = getenv("SNK_BA_CHECK_LISTS") != nullptr;  // tests / fuzzers: device-built lists against the host builder
-    if (check_lists)
-    {
-        // the host builder's lists (never uploaded here) against what the kernels wrote
-        SNK_HIP_CHECK(hipStreamSynchronize(st));
-        std::vector<CamObs> d_rec(camitems.size());
-        if (!d_rec.empty()) SNK_HIP_CHECK(hipMemcpy(d_rec.data(), h->d_csobs.p, d_rec.size() * sizeof(CamObs), hipMemcpyDeviceToHost));
-        for (int b = 0; b < count; ++b)
-        {
-            const snk_ba_problem& P = problems[b];
-            const Prob& pr          = probs[(size_t)b];
-            const int n_items       = camstart[(size_t)pr.camstart_off + (size_t)pr.nfc];
-            for (int k = 0; k < n_items; ++k)
-            {
-                const int s = camitems[(size_t)pr.citem_off + (size_t)k], o = oorig[(size_t)pr.obs_off + (size_t)s] - pr.orig_off;
-                const CamObs& r = d_rec[(size_t)pr.citem_off + (size_t)k];
-                const bool same = r.u == P.obs_uv[o][0] && r.v == P.obs_uv[o][1] && r.depth == P.obs_depth[o] && r.weight == P.obs_weight[o] &&
-                                  (r.ptw & 0x7FFFFFFF) == P.obs_pt[o] && r.orig == pr.orig_off + o &&
-                                  (r.ptw < 0 ? 1 : 0) == (P.pt_const[P.obs_pt[o]] ? 0 : 1);
-                SNK_REQUIRE(same, "SNK_BA_CHECK_LISTS: a device-gathered camera record differs from the caller's observation");
-            }
-        }
-        {
-            // the work items' observation records (gather_set_records) against the caller's arrays
-            std::vector<SetObs> d_sr((size_t)n_setrec);
-            if (!d_sr.empty()) SNK_HIP_CHECK(hipMemcpy(d_sr.data(), h->d_setobs.p, d_sr.size() * sizeof(SetObs), hipMemcpyDeviceToHost));
-            for (int b = 0; b < count; ++b)
-            {
-                const snk_ba_problem& P = problems[b];
-                const Prob& pr          = probs[(size_t)b];
-                for (int it = 0; it < pr.n_set; ++it)
-                {
-                    const SetItem& si = LS.setitems[(size_t)pr.set_off + (size_t)it];
-                    for (int q = 0; q < si.n_pts; ++q)
-                        for (int a = 0; a < si.run; ++a)
-                        {
-                            const int2 pp = LS.setpts[(size_t)si.pts_off + (size_t)q];
-                            const int s = pp.y + a, o = oorig[(size_t)pr.obs_off + (size_t)s] - pr.orig_off;
-                            const SetObs& r = d_sr[(size_t)si.rec_off + (size_t)q * si.run + (size_t)a];
-                            const bool same = r.u == P.obs_uv[o][0] && r.v == P.obs_uv[o][1] && r.depth == P.obs_depth[o] &&
-                                              r.weight == P.obs_weight[o] && r.orig == pr.orig_off + o &&
-                                              r.pk == set_pack(P.obs_img[o], ocam[(size_t)pr.obs_off + (size_t)s], P.pt_const[pp.x] ? 0 : 1) &&
-                                              P.obs_pt[o] == pp.x;
-                            SNK_REQUIRE(same, "SNK_BA_CHECK_LISTS: a device-gathered work-item record differs from the caller's observation");
-                        }
-                }
-            }
-        }
-        if (dev_entries)
-        {
-            std::vector<int> d_bs((size_t)blkstart_total);
-            std::vector<int4> d_ent((size_t)ent_total);
-            SNK_HIP_CHECK(hipMemcpy(d_bs.data(), h->d_blkstart.p, d_bs.size() * sizeof(int), hipMemcpyDeviceToHost));
-            if (!d_ent.empty()) SNK_HIP_CHECK(hipMemcpy(d_ent.data(), h->d_blkent.p, d_ent.size() * sizeof(int4), hipMemcpyDeviceToHost));
-            pvec<int> h_bs;
-            pvec<int4> h_ent;
-            for (int b = 0; b < count; ++b)
-            {
-                const Prob& pr  = probs[(size_t)b];
-                const size_t nb = (size_t)pr.nfc * pr.nfc, bs_at = h_bs.size(), ent_at = h_ent.size();
-                host_block_entries(b, h_bs, h_ent);
-                for (size_t k = 0; k <= nb; ++k)
-                    SNK_REQUIRE(d_bs[(size_t)pr.blkstart_off + k] == h_bs[bs_at + k], "SNK_BA_CHECK_LISTS: device-built block starts differ from the host builder's");
-                SNK_REQUIRE((long long)h_bs[bs_at + nb] <= ent_bound[(size_t)b], "SNK_BA_CHECK_LISTS: block entries exceed their bound");
-                for (int k = 0; k < h_bs[bs_at + nb]; ++k)
-                {
-                    const int4 d = d_ent[(size_t)pr.ent_off + (size_t)k], w = h_ent[ent_at + (size_t)k];
-                    SNK_REQUIRE(d.x == w.x && d.y == w.y && d.z == w.z, "SNK_BA_CHECK_LISTS: device-built block entries differ from the host builder's");
-                }
-            }
-        }
-    }
-    if (prof)
-    {
-        SNK_HIP_CHECK(hipStreamSynchronize(st));
-        const auto t_end = std::chrono::steady_clock::now();
-        auto us = [](auto a, auto b) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-        fprintf(stderr, "[snk_ba_set_problems] lists %lld us, uploads %lld us, reserve+memset %lld us, sync %lld us\n", us(t_begin, t_lists),
-                us(t_lists, t_up), us(t_up, t_rs), us(t_rs, t_end));
-        fprintf(stderr, "[snk_ba_set_problems] lists in us: values+sort %lld, observation arrays %lld, wave items %lld, camera lists %lld, "
-                        "block entries %lld, point sets %lld (grouping %lld, work items %lld, block lists %lld), constraints %lld, rest %lld\n",
-                sec_us[0] / 1000, sec_us[1] / 1000, sec_us[2] / 1000, sec_us[3] / 1000, sec_us[4] / 1000,
-                (sec_us[5] + sec_us[8] + sec_us[9]) / 1000, sec_us[8] / 1000, sec_us[9] / 1000, sec_us[5] / 1000, sec_us[6] / 1000, sec_us[7] / 1000);
-    }
-    no_set_on_failure.ok = true;
+    *out = h;
+    return SNK_OK;
+}
+
+int snk_ba_destroy(snk_ba* h)
+{
+    if (!h) return SNK_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);  // an upload of a hand-over (it reads the handle's pinned lists) or a solve may still be in flight
+    // every device buffer of the handle (the struct's DevBuf members)
+    DevBuf* all[] = {&h->d_setitems, &h->d_setpts, &h->d_setpairs, &h->d_setobs, &h->d_cblkstart, &h->d_cblkitems, &h->d_spart,
+                     &h->d_prob, &h->d_state, &h->d_pose, &h->d_pose_new, &h->d_pose0, &h->d_pt, &h->d_pt_new,
+                     &h->d_pt0, &h->d_ptc, &h->d_camidx, &h->d_ptstart, &h->d_oimg, &h->d_ocam, &h->d_optfree,
+                     &h->d_ouv, &h->d_odepth, &h->d_oweight, &h->d_oorig, &h->d_outlier, &h->d_csobs, &h->d_r,
+                     &h->d_W, &h->d_ptv, &h->d_Vinv, &h->d_bp, &h->d_cost, &h->d_cost_new, &h->d_U, &h->d_camstart,
+                     &h->d_camitems, &h->d_blkstart, &h->d_blkent, &h->d_S, &h->d_rhs, &h->d_x, &h->d_chi2,
+                     &h->d_pcgw, &h->d_optidx, &h->d_wvpt, &h->d_rpcmeta, &h->d_rpcnext, &h->d_camrpcstart,
+                     &h->d_camrpcitems, &h->d_blkrpc, &h->d_rpcout, &h->d_becnt, &h->d_probcond, &h->d_campart, &h->d_ccstart, &h->d_ccitems};
+    for (DevBuf* b : all) b->release();
+    h->h_stage.release();
+    h->drop_graphs();
+    h->fini();
+    delete h;
+    return SNK_OK;
+}
+
+int snk_ba_sync(snk_ba* h)
+{
+    SNK_REQUIRE(h != nullptr, "ba is NULL");
+    SNK_HIP_CHECK(hipStreamSynchronize(h->stream));
     return SNK_OK;
 }
 
@@ -6596,11 +4665,6 @@ int snk_ba_set_explicit_schur(snk_ba* h, int explicit_schur)
     SNK_REQUIRE(explicit_schur == 0 || explicit_schur == 1, "explicit_schur must be 0 or 1");
     h->explicit_schur = explicit_schur;  // read by the next snk_ba_set_problem(s)
     return SNK_OK;
-}
-
-int snk_ba_set_problem(snk_ba* h, const snk_ba_problem* problem)
-{
-    return snk_ba_set_problems(h, problem, 1);
 }
 
 int snk_ba_pcg_form(const snk_ba* h, int* form, int* workgroups)
@@ -7078,8 +5142,7 @@ int snk_ba_solve_local_scene(snk_ba* h, int problem, double chi2_mono, double ch
     }
     if (tab.n > 0)
     {
-        hipLaunchKernelGGL(copy_table_kernel, dim3(4, tab.n), dim3(256), 0, h->stream, tab);
-        SNK_LAUNCH_CHECK();
+        if ((rc = ba_copy_table(tab, 4, h->stream)) != SNK_OK) return rc;
     }
     SNK_HIP_CHECK(hipStreamSynchronize(h->stream));
     for (int k = 0; k < 4; ++k)

@@ -546,7 +546,7 @@ def test_big_batch_of_unequal_scenes(orc):
 
 def test_hand_over_threads_end_with_the_handle(orc):
     """The host threads that build the lists of a batch hand-over are parked in the handle between hand-overs (HostPool in
-    csrc/ba.hip) -- they must not outlive it, and repeated hand-overs must not add more.  Linux: /proc/self/status."""
+    csrc/ba_types.hpp) -- they must not outlive it, and repeated hand-overs must not add more.  Linux: /proc/self/status."""
     from snake_slam_amd import synth
     from snake_slam_amd.ba import BARec, lba_options
 

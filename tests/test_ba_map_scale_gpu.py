@@ -1,6 +1,6 @@
 """GPU: global BA (FullBA) at map scale, where the form of the reduced-camera-system PCG changes with the size of the system.
 
-n6 = 6 x free keyframes.  The hand-over picks (csrc/ba.hip, snk_ba_set_problems):
+n6 = 6 x free keyframes.  The hand-over picks (csrc/ba.hip, ba_plan_pcg, called by snk_ba_set_problems):
 * pcgl_persist_reg (rows of S in registers) up to n6 = 2048 -- pinned by test_ba_gpu.py's boundary sizes;
 * pcgl_persist1 (one grid barrier, rows of S streamed) up to n6 * 24 <= 150 KB (n6 <= 6400); its preconditioner rows sit in
   registers up to n6 = 16 * 256 = 4096 and are read from memory above;
