@@ -625,6 +625,81 @@ SNK_API int snk_match_relink(snk_matcher* m, const snk_frame_view* frame, const 
                              int feature_threshold, int32_t* action, int32_t* best_idx, int* n_changed);
 
 /* ------------------------------------------------------------------------------------------
+ * New map points from matched keyframe pairs (semantics "snk-tri v1")
+ * ------------------------------------------------------------------------------------------ */
+
+/* One keyframe as the loop of Triangulator::triangulate reads it — Snake/LocalMapping/Triangulator.cpp:135-138,
+ * :176-185, :204-206: kf->frame->undistorted_keypoints / right_points (>= 0 <=> stereo) / depth, has_mp[i] != 0 <=>
+ * kf->GetMapPoint(i) != nullptr (:67), pose = kf->Pose() (qx qy qz qw tx ty tz, world -> camera).  Any feature order;
+ * n <= 65536. */
+typedef struct snk_tri_view
+{
+    int32_t n;
+    int32_t pad;
+    const snk_kp64* kps;
+    const float* right_points;
+    const float* depth;
+    const uint8_t* has_mp;
+    double pose[7];
+} snk_tri_view;
+
+/* TriangulationParams::errorMono / errorStereo (Triangulator.cpp:127-128), the global th_depth (:225,:230),
+ * scalePyramid.Factor() (:132) and settings.inputType == InputType::Mono (:142). */
+typedef struct snk_tri_params
+{
+    float error_mono, error_stereo;
+    double th_depth;
+    float scale_factor;
+    int32_t mono;
+} snk_tri_params;
+
+#define SNK_TRI_TRIANGULATED 1 /* Triangulator.cpp:215-221 */
+#define SNK_TRI_STEREO1 2      /* :222-226: unprojected with keyframe 1's stereo depth */
+#define SNK_TRI_STEREO2 3      /* :227-231 */
+
+/* ImageTriangulationResult::NewPoint (Triangulator.cpp:284-290) plus what the commit loop needs: `neighbour` = index of kf2
+ * in the call, `branch` = which of the three constructions made the point (SNK_TRI_*), `commit` = 1 where the loop of
+ * :61-108 reaches allocateMapPoint for this entry (the test of :67 is false when the entry is visited). */
+typedef struct snk_new_point
+{
+    int32_t feature1, feature2; /* featureId1, featureId2 */
+    int32_t neighbour;
+    uint8_t far_away;
+    uint8_t commit;
+    uint8_t branch;
+    uint8_t pad;
+    double pos[3]; /* worldPosition */
+} snk_new_point;
+
+/* Replaces the geometric loop of Triangulator::triangulate for ONE keyframe pair — Snake/LocalMapping/Triangulator.cpp:127-157
+ * (chi-square thresholds, ratioFactor, the baseline gate) and :174-291 (parallax test, TriangulateHomogeneous, the stereo
+ * fallbacks, behind-camera / chi-square / scale-consistency gates).  pairs = tmp_matches (idx1, idx2) after the matchers of
+ * :164-171; out (capacity n_pairs) receives result.newPoints in pair order, *n_out their number.  median_depth2 =
+ * kf2->MedianDepth() (:145), read in mono mode only.  commit is set as the loop of :61-70 would for this pair alone: from
+ * has_mp of both views and the earlier kept entries of this call.  Absent saiga functions are [DEFINED]: stereo_cam.baseLine()
+ * = bf / fx, K.unproject(p, z) = ((x - cx) / fx * z, (y - cy) / fy * z, z), projectStereo(X) = (u, v, u - bf / z),
+ * SquaredScale(o) = level_scale[o]^2, TriangulateHomogeneous = unit-row homogeneous linear system, smallest right singular
+ * vector.  A feature index outside [0, n), an octave outside [0, n_levels) or a NULL array with a non-zero count:
+ * SNK_ERR_INVALID_ARG, nothing is launched.  n_pairs == 0 is valid. */
+SNK_API int snk_triangulate_pairs(snk_matcher* m, const snk_camera* cam, const snk_tri_params* params, const snk_tri_view* kf1,
+                                  const snk_tri_view* kf2, float median_depth2, const int32_t (*pairs)[2], int n_pairs,
+                                  const float* level_scale, int n_levels, snk_new_point* out, int* n_out);
+
+/* The whole neighbour loop of Triangulator::Process — Snake/LocalMapping/Triangulator.cpp:42-47 — plus the first-wins test of
+ * its commit loop (:61-70) in one call: kf2s[k] = tmp_keyframes[k], pairs = every neighbour's tmp_matches concatenated,
+ * pair_start[n_neighbours + 1] their offsets (pair_start[0] = 0).  out (capacity pair_start[n_neighbours]) receives
+ * newPointsa[0].newPoints, newPointsa[1].newPoints, ... back to back, out_start[n_neighbours + 1] the offsets of each
+ * neighbour's points, *n_out = out_start[n_neighbours].  commit: the entries are visited in that order; one is kept iff
+ * kf1->GetMapPoint(feature1) and kf2->GetMapPoint(feature2) are both still null at that moment, i.e. has_mp is 0 for both and
+ * no earlier kept entry used feature1 of keyframe 1 or feature2 of the same neighbour.  (Neighbours must be distinct
+ * keyframes, as GetBestCovisibilityKeyFrames returns them.)  The map edits of :72-106 stay with the caller, for the entries
+ * with commit = 1, in order.  n_neighbours == 0 and empty pair lists are valid and launch nothing. */
+SNK_API int snk_triangulate_neighbours(snk_matcher* m, const snk_camera* cam, const snk_tri_params* params, const snk_tri_view* kf1,
+                                       const snk_tri_view* kf2s, const float* median_depth2s, int n_neighbours,
+                                       const int32_t (*pairs)[2], const int32_t* pair_start, const float* level_scale, int n_levels,
+                                       snk_new_point* out, int32_t* out_start, int* n_out);
+
+/* ------------------------------------------------------------------------------------------
  * Pose refinement (the step after every projection matcher)
  * ------------------------------------------------------------------------------------------ */
 

@@ -601,6 +601,145 @@ class DeferredMapper
     snk_matcher* h_ = nullptr;
 };
 
+// Snake::Triangulator (reference Snake/LocalMapping/Triangulator.h:23-87) from "pairs" to "points": the geometric loop of
+// triangulate (Triangulator.cpp:127-157, :174-291) and the neighbour loop + first-wins test of Process (:42-47, :61-70),
+// semantics "snk-tri v1".  The matchers that fill tmp_matches are MappingORBMatcher's (:164-171); the map edits of :72-106 stay
+// on the Snake side, for the returned points with commit = 1, in order.
+class Triangulator
+{
+   public:
+    // TriangulationParams (Triangulator.h:27-38), the fields the geometric loop reads
+    struct TriangulationParams
+    {
+        float errorMono   = 2.1f;
+        float errorStereo = 2.3f;
+    };
+    // What the loop reads of one keyframe: kf->frame->undistorted_keypoints / right_points / depth, GetMapPoint(i) != nullptr,
+    // kf->Pose() and (mono) kf->MedianDepth().  The vectors must outlive the call.
+    struct KeyframeView
+    {
+        const std::vector<snk_kp64>* undistorted_keypoints = nullptr;
+        const std::vector<float>* right_points             = nullptr;
+        const std::vector<float>* depth                    = nullptr;
+        const std::vector<uint8_t>* has_map_point          = nullptr;
+        double pose[7]                                     = {0, 0, 0, 1, 0, 0, 0};
+        float median_depth                                 = 0.f;
+        snk_tri_view view() const
+        {
+            if (!undistorted_keypoints || !right_points || !depth || !has_map_point) throw std::invalid_argument("KeyframeView: unset array");
+            const size_t n = undistorted_keypoints->size();
+            if (right_points->size() != n || depth->size() != n || has_map_point->size() != n) throw std::invalid_argument("KeyframeView: array sizes");
+            snk_tri_view v{};
+            v.n            = (int32_t)n;
+            v.kps          = undistorted_keypoints->data();
+            v.right_points = right_points->data();
+            v.depth        = depth->data();
+            v.has_mp       = has_map_point->data();
+            std::memcpy(v.pose, pose, sizeof(v.pose));
+            return v;
+        }
+    };
+    // ImageTriangulationResult (Triangulator.h:41-55) without the Keyframe pointers
+    struct ImageTriangulationResult
+    {
+        std::vector<snk_new_point> newPoints;
+    };
+
+    // K, stereo_cam.bf, scalePyramid (level scales; Factor() = level_scale[1] / level_scale[0]), the global th_depth and
+    // settings.inputType == InputType::Mono
+    Triangulator(const snk_camera& K, const std::vector<float>& level_scale, double th_depth, bool mono, int device = 0)
+        : K_(K), level_scale_(level_scale), th_depth_(th_depth), mono_(mono)
+    {
+        if (level_scale_.empty()) throw std::invalid_argument("level_scale is empty");
+        check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create");
+    }
+    ~Triangulator() { snk_matcher_destroy(h_); }
+    Triangulator(const Triangulator&)            = delete;
+    Triangulator& operator=(const Triangulator&) = delete;
+
+    // triangulate(params, kf1, kf2, precise) — Triangulator.cpp:113-294 — after the matchers: tmp_matches in, result.newPoints out
+    ImageTriangulationResult triangulate(const TriangulationParams& params, const KeyframeView& kf1, const KeyframeView& kf2,
+                                         const std::vector<std::pair<int, int>>& tmp_matches)
+    {
+        const snk_tri_params p = tri_params(params);
+        const snk_tri_view v1 = kf1.view(), v2 = kf2.view();
+        std::vector<int32_t> flat = flatten(tmp_matches);
+        ImageTriangulationResult result;
+        result.newPoints.resize(tmp_matches.size() + 1);
+        int n = 0;
+        check(snk_triangulate_pairs(h_, &K_, &p, &v1, &v2, kf2.median_depth, reinterpret_cast<const int32_t(*)[2]>(flat.data()),
+                                    (int)tmp_matches.size(), level_scale_.data(), (int)level_scale_.size(), result.newPoints.data(), &n),
+              "snk_triangulate_pairs");
+        result.newPoints.resize((size_t)n);
+        return result;
+    }
+
+    // Process(params, kf, out_points) — Triangulator.cpp:15-111 — from the matched pairs of every neighbour (tmp_keyframes order)
+    // to newPointsa with the test of :67 already made: newPointsa[k].newPoints[j].commit == 1 <=> the loop of :61-108 creates a
+    // map point for that entry.  Returns nnew (:106), the number of such entries.
+    int Process(const TriangulationParams& params, const KeyframeView& kf, const std::vector<KeyframeView>& tmp_keyframes,
+                const std::vector<std::vector<std::pair<int, int>>>& matches, std::vector<ImageTriangulationResult>& newPointsa)
+    {
+        if (matches.size() != tmp_keyframes.size()) throw std::invalid_argument("one match list per neighbour keyframe");
+        const snk_tri_params p = tri_params(params);
+        const snk_tri_view v1  = kf.view();
+        std::vector<snk_tri_view> v2;
+        std::vector<float> median;
+        std::vector<int32_t> start{0}, flat;
+        for (size_t k = 0; k < tmp_keyframes.size(); ++k)
+        {
+            v2.push_back(tmp_keyframes[k].view());
+            median.push_back(tmp_keyframes[k].median_depth);
+            const std::vector<int32_t> f = flatten(matches[k]);
+            flat.insert(flat.end(), f.begin(), f.end());
+            start.push_back((int32_t)(flat.size() / 2));
+        }
+        std::vector<snk_new_point> out(flat.size() / 2 + 1);
+        std::vector<int32_t> out_start(tmp_keyframes.size() + 1, 0);
+        int n = 0;
+        check(snk_triangulate_neighbours(h_, &K_, &p, &v1, v2.data(), median.data(), (int)tmp_keyframes.size(),
+                                         reinterpret_cast<const int32_t(*)[2]>(flat.data()), start.data(), level_scale_.data(),
+                                         (int)level_scale_.size(), out.data(), out_start.data(), &n),
+              "snk_triangulate_neighbours");
+        newPointsa.assign(tmp_keyframes.size(), ImageTriangulationResult{});
+        int nnew = 0;
+        for (size_t k = 0; k < tmp_keyframes.size(); ++k)
+        {
+            newPointsa[k].newPoints.assign(out.begin() + out_start[k], out.begin() + out_start[k + 1]);
+            for (const snk_new_point& np : newPointsa[k].newPoints) nnew += np.commit;
+        }
+        return nnew;
+    }
+
+   private:
+    snk_tri_params tri_params(const TriangulationParams& params) const
+    {
+        snk_tri_params p{};
+        p.error_mono   = params.errorMono;
+        p.error_stereo = params.errorStereo;
+        p.th_depth     = th_depth_;
+        p.scale_factor = level_scale_.size() > 1 ? level_scale_[1] / level_scale_[0] : 1.2f;
+        p.mono         = mono_ ? 1 : 0;
+        return p;
+    }
+    static std::vector<int32_t> flatten(const std::vector<std::pair<int, int>>& m)
+    {
+        std::vector<int32_t> f;
+        f.reserve(2 * m.size());
+        for (const auto& [a, b] : m)
+        {
+            f.push_back(a);
+            f.push_back(b);
+        }
+        return f;
+    }
+    snk_matcher* h_ = nullptr;
+    snk_camera K_;
+    std::vector<float> level_scale_;
+    double th_depth_;
+    bool mono_;
+};
+
 // Snake::PoseRefinement (reference Snake/Tracking/PoseRefinement.h:22-99): the robust pose-only
 // optimisation after every matcher call.  The caller gathers wps / obs / idx exactly as refinePose
 // (:35-60) and RefinePoseWithMatches (PoseRefinement.cpp:37-57) do, then writes outlier[i] to

@@ -304,6 +304,89 @@ class DeferredMapper(_Handle):
         return n.value, action[: len(q)], best[: len(q)]
 
 
+class TriView(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32), ("kps", C.c_void_p), ("right_points", C.c_void_p), ("depth", C.c_void_p),
+                ("has_mp", C.c_void_p), ("pose", C.c_double * 7)]
+
+
+class TriParams(C.Structure):
+    _fields_ = [("error_mono", C.c_float), ("error_stereo", C.c_float), ("th_depth", C.c_double), ("scale_factor", C.c_float),
+                ("mono", C.c_int32)]
+
+
+NEW_POINT_DTYPE = np.dtype([("feature1", "<i4"), ("feature2", "<i4"), ("neighbour", "<i4"), ("far_away", "u1"), ("commit", "u1"),
+                            ("branch", "u1"), ("pad", "u1"), ("pos", "<f8", 3)])
+TRI_TRIANGULATED, TRI_STEREO1, TRI_STEREO2 = 1, 2, 3
+
+
+def _tri_view(kf):
+    """kf: dict with kps (undistorted_keypoints), right_points, depth, has_mp (GetMapPoint(i) != nullptr) and pose.
+    Returns (snk_tri_view, arrays to keep alive)."""
+    a = (np.ascontiguousarray(kf["kps"], KP64_DTYPE), np.ascontiguousarray(kf["right_points"], np.float32),
+         np.ascontiguousarray(kf["depth"], np.float32), np.ascontiguousarray(kf["has_mp"], np.uint8))
+    if not (len(a[0]) == len(a[1]) == len(a[2]) == len(a[3])):
+        raise ValueError("array lengths")
+    pose = np.ascontiguousarray(kf["pose"], np.float64).reshape(7)
+    v = TriView()
+    v.n = len(a[0])
+    v.kps, v.right_points, v.depth, v.has_mp = (x.ctypes.data if x.size else 0 for x in a)
+    v.pose = (C.c_double * 7)(*pose)
+    return v, a
+
+
+class Triangulator(_Handle):
+    """The geometric loop and the commit test of ``Snake::Triangulator`` (reference Snake/LocalMapping/Triangulator.cpp:42-47,
+    :61-70, :113-294), semantics "snk-tri v1".  The matchers that produce the pairs are ``MappingORBMatcher``'s; the map edits
+    of :72-106 stay with the caller, for the returned points with ``commit`` set, in order."""
+
+    def __init__(self, cam, level_scale, errorMono, errorStereo, th_depth, mono=False, device: int = 0, stream: int | None = None):
+        super().__init__(device, stream)
+        self._cam = Camera(*cam)
+        self._ls = np.ascontiguousarray(level_scale, np.float32)
+        factor = float(self._ls[1] / self._ls[0]) if len(self._ls) > 1 else 1.2  # scalePyramid.Factor()
+        self._params = TriParams(float(errorMono), float(errorStereo), float(th_depth), factor, 1 if mono else 0)
+
+    def triangulate(self, kf1, kf2, pairs, median_depth2=0.0):
+        """One keyframe pair (Triangulator::triangulate, :174-291).  pairs: tmp_matches [(idx1, idx2)].
+        Returns result.newPoints as a NEW_POINT_DTYPE record array, in pair order."""
+        v1, keep1 = _tri_view(kf1)
+        v2, keep2 = _tri_view(kf2)
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        out = np.zeros(max(len(p), 1), NEW_POINT_DTYPE)
+        n = C.c_int(0)
+        _lib.check(self._lib.snk_triangulate_pairs(self._h, C.byref(self._cam), C.byref(self._params), C.byref(v1), C.byref(v2),
+                                                   float(median_depth2), _ptr(p), len(p), _ptr(self._ls), len(self._ls), _ptr(out),
+                                                   C.byref(n)), "snk_triangulate_pairs")
+        return out[: n.value]
+
+    def Process(self, kf1, kf2s, pairs, median_depth2s=None):
+        """The neighbour loop of Triangulator::Process (:42-47) and the first-wins test of its commit loop (:61-70).
+        kf2s: tmp_keyframes; pairs: one [(idx1, idx2)] list per neighbour.  Returns (nnew = number of points with commit set,
+        points of all neighbours back to back as a NEW_POINT_DTYPE record array, out_start[len(kf2s) + 1])."""
+        if len(pairs) != len(kf2s):
+            raise ValueError("one pair list per neighbour")
+        v1, keep1 = _tri_view(kf1)
+        views = [_tri_view(k) for k in kf2s]
+        varr = (TriView * max(len(views), 1))(*[v for v, _ in views])
+        ps = [np.ascontiguousarray(p, np.int32).reshape(-1, 2) for p in pairs]
+        start = np.zeros(len(ps) + 1, np.int32)
+        start[1:] = np.cumsum([len(p) for p in ps])
+        p = np.ascontiguousarray(np.concatenate(ps), np.int32) if ps else np.zeros((0, 2), np.int32)
+        med = np.zeros(max(len(views), 1), np.float32)
+        if median_depth2s is not None:
+            med[: len(views)] = np.asarray(median_depth2s, np.float32)
+        elif self._params.mono and views:
+            raise ValueError("mono: median_depth2s (kf2->MedianDepth()) is needed")
+        out = np.zeros(max(len(p), 1), NEW_POINT_DTYPE)
+        out_start = np.zeros(len(ps) + 1, np.int32)
+        n = C.c_int(0)
+        _lib.check(self._lib.snk_triangulate_neighbours(self._h, C.byref(self._cam), C.byref(self._params), C.byref(v1), varr, _ptr(med),
+                                                        len(views), _ptr(p), _ptr(start), _ptr(self._ls), len(self._ls), _ptr(out),
+                                                        _ptr(out_start), C.byref(n)), "snk_triangulate_neighbours")
+        out = out[: n.value]
+        return int(out["commit"].sum()), out, out_start
+
+
 class BowFeatures(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("pad", C.c_int32), ("node_id", C.c_void_p), ("node_start", C.c_void_p),
                 ("features", C.c_void_p)]
