@@ -794,6 +794,65 @@ SNK_API int snk_track_backproject_batch_dev(snk_matcher* m, const snk_frames_dev
                                             const snk_camera* cam, const double* poses_dev, double* world_dev, uint8_t* has_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * P3P-RANSAC of TrackBruteForce (semantics "snk-p3p v1")
+ * ------------------------------------------------------------------------------------------ */
+
+/* RansacParameters as Tracking::TrackBruteForce sets them -- Snake/Tracking/TrackingCoarse.cpp:410-414: iterations = maxIterations
+ * (250), residual_threshold = residualThreshold = (2 * reprojectionErrorThresholdMono / K.fx)^2, a squared distance in the
+ * normalised image plane.  `threads` has no meaning here: every hypothesis of every problem of a call runs in one launch.  seed:
+ * the sampler is a counter-based hash of (seed, problem index in the call, hypothesis, draw), so a call is a pure function of its
+ * arguments. */
+typedef struct snk_p3p_params
+{
+    int32_t iterations;
+    int32_t pad;
+    double residual_threshold;
+    uint64_t seed;
+} snk_p3p_params;
+
+/* One call of `pnp2.solve(wps, ips, pose, inlierMatches, inlierMask)` -- TrackingCoarse.cpp:403-440: wps[i] = world point of pair
+ * i, nips[i] = K.unproject2(undistorted keypoint) (:383-385); n <= 3072.  Out: pose (world -> camera, qx qy qz qw tx ty tz; left as
+ * it came in when n < 4 or no hypothesis has a solution), inliers = the return value, inlier_mask[n], inlier_matches[0 .. inliers)
+ * ascending (capacity n), best_iteration / best_solution = the winning hypothesis and the index of the winning pose among that
+ * hypothesis' solutions (-1 / -1 without a winner). */
+typedef struct snk_p3p_problem
+{
+    int32_t n;
+    int32_t inliers;
+    const double (*wps)[3];
+    const double (*nips)[2];
+    uint8_t* inlier_mask;
+    int32_t* inlier_matches;
+    double pose[7];
+    int32_t best_iteration, best_solution;
+} snk_p3p_problem;
+
+/* Replaces P3PRansac::solve for a batch of problems -- Snake/Tracking/TrackingCoarse.cpp:403-440 (call :420): per hypothesis
+ * three distinct pairs, the <= 4 poses of the minimal solver, every pose scored against all n pairs (inlier <=> z_c > 0 and
+ * |p_c.xy / z_c - nip|^2 < residual_threshold); the winner has the most inliers, ties go to the smaller hypothesis, then to the
+ * smaller solution index; no refinement (RefinePoseWithMatches follows at :452).  Host pointers, synchronous, one launch for the
+ * batch; the result is identical from run to run.  n_problems == 0 is valid. */
+SNK_API int snk_p3p_ransac(snk_matcher* m, const snk_p3p_params* params, snk_p3p_problem* problems, int n_problems);
+
+/* The same for ONE problem with every hypothesis laid open, for tests (TrackingCoarse.cpp:403-440 has no counterpart: the loop is
+ * inside P3PRansac): triplets[k] = the three pair indices of hypothesis k, n_solutions[k] in 0..4, poses[k][j] / counts[k][j] = pose
+ * and inlier count of its solution j (zeros past n_solutions[k]).  All arrays have params->iterations entries.  `problem` is filled
+ * as by snk_p3p_ransac. */
+SNK_API int snk_p3p_debug_hypotheses(snk_matcher* m, const snk_p3p_params* params, snk_p3p_problem* problem,
+                                     int32_t (*triplets)[3], int32_t* n_solutions, double (*poses)[4][7], int32_t (*counts)[4]);
+
+/* Device-resident form for every frame of a batch, between snk_track_bf_matches_batch_dev and snk_pose_refine_frame_batch_dev and fed
+ * like the latter -- Snake/Tracking/TrackingCoarse.cpp:373-440: the pairs of frame b are its features f with
+ * 0 <= frame_pt_dev[b][f] < n_pts_dev[b], in feature order (the order of matchesIds, :373-387), world point = 3 doubles at
+ * pts_dev + (b * pts_cap + frame_pt_dev[b][f]) * pts_stride, nip = ((x - cx) / fx, (y - cy) / fy) of frames->kps[b][f] (:383-385);
+ * problem index = b.  poses_dev [batch][7] receives the winner's pose (untouched without a winner), inliers_dev [batch] the count,
+ * and frame_pt_dev[b][f] becomes -1 at every feature that is not an inlier (:433-440: mvpMapPoints keeps the inliers only).
+ * frames->cap <= 3072.  Asynchronous on the handle's stream: BF matches -> RANSAC -> refinement without a host round trip. */
+SNK_API int snk_p3p_ransac_frame_batch_dev(snk_matcher* m, const snk_frames_dev* frames, const snk_camera* cam,
+                                           const snk_p3p_params* params, const void* pts_dev, int pts_stride, int32_t* frame_pt_dev,
+                                           const int32_t* n_pts_dev, int pts_cap, double* poses_dev, int32_t* inliers_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Local bundle adjustment
  * ------------------------------------------------------------------------------------------ */
 

@@ -74,6 +74,9 @@ SIGNATURES = {
     "snk_match_relink": (i32, [vp, vp, vp, vp, vp, i32, f32, f64, i32, vp, vp, C.POINTER(i32)]),
     "snk_triangulate_pairs": (i32, [vp, vp, vp, vp, vp, f32, vp, i32, vp, i32, vp, C.POINTER(i32)]),
     "snk_triangulate_neighbours": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(i32)]),
+    "snk_p3p_ransac": (i32, [vp, vp, vp, i32]),
+    "snk_p3p_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "snk_p3p_ransac_frame_batch_dev": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
     "snk_frontend_create": (i32, [vp, i32, C.POINTER(vp)]),
     "snk_frontend_destroy": (i32, [vp]),
     "snk_frontend_max_keypoints": (i32, [vp, i32, i32, C.POINTER(i32)]),

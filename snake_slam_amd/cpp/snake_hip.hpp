@@ -740,6 +740,65 @@ class Triangulator
     bool mono_;
 };
 
+// Saiga::P3PRansac as Tracking::TrackBruteForce uses it -- Snake/Tracking/TrackingCoarse.cpp:403-440, semantics "snk-p3p v1":
+//   RansacParameters params; params.maxIterations = 250; params.residualThreshold = chi1 * chi1;
+//   P3PRansac pnp2(params);  inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask);
+// Vec3 / Vec2 are three / two contiguous doubles (Eigen::Vector3d / Vector2d, std::array), the pose is qx qy qz qw tx ty tz
+// (world -> camera; left as it came in without a winner).  RansacParameters::threads has no meaning here; `seed` feeds the
+// counter-based sampler (a call is a pure function of its arguments).
+struct RansacParameters
+{
+    int maxIterations        = 250;
+    double residualThreshold = 1e-4;
+    int threads              = 1;
+    uint64_t seed            = 0;
+};
+
+class P3PRansac
+{
+   public:
+    explicit P3PRansac(const RansacParameters& params, int device = 0) : params_(params)
+    {
+        check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create");
+    }
+    ~P3PRansac() { snk_matcher_destroy(h_); }
+    P3PRansac(const P3PRansac&)            = delete;
+    P3PRansac& operator=(const P3PRansac&) = delete;
+
+    template <typename Vec3, typename Vec2>
+    int solve(const std::vector<Vec3>& wps, const std::vector<Vec2>& ips, double (&pose)[7], std::vector<int>& inlierMatches,
+              std::vector<char>& inlierMask)
+    {
+        static_assert(sizeof(Vec3) == 24 && sizeof(Vec2) == 16, "world points / image points must be 3 / 2 contiguous doubles");
+        if (wps.size() != ips.size()) throw std::invalid_argument("P3PRansac::solve: wps / ips sizes");
+        const size_t n = wps.size();
+        std::vector<uint8_t> mask(n + 1);
+        std::vector<int32_t> list(n + 1);
+        snk_p3p_params p{params_.maxIterations, 0, params_.residualThreshold, params_.seed};
+        snk_p3p_problem q{};
+        q.n              = (int32_t)n;
+        q.wps            = reinterpret_cast<const double(*)[3]>(wps.data());
+        q.nips           = reinterpret_cast<const double(*)[2]>(ips.data());
+        q.inlier_mask    = mask.data();
+        q.inlier_matches = list.data();
+        std::memcpy(q.pose, pose, sizeof(q.pose));
+        check(snk_p3p_ransac(h_, &p, &q, 1), "snk_p3p_ransac");
+        std::memcpy(pose, q.pose, sizeof(q.pose));
+        inlierMask.assign(mask.begin(), mask.begin() + (std::ptrdiff_t)n);
+        inlierMatches.assign(list.begin(), list.begin() + q.inliers);
+        best_iteration = q.best_iteration;
+        best_solution  = q.best_solution;
+        return q.inliers;
+    }
+
+    int best_iteration = -1, best_solution = -1;  // the winning hypothesis of the last solve
+
+   private:
+    RansacParameters params_;
+    snk_matcher* h_ = nullptr;
+};
+
+
 // Snake::PoseRefinement (reference Snake/Tracking/PoseRefinement.h:22-99): the robust pose-only
 // optimisation after every matcher call.  The caller gathers wps / obs / idx exactly as refinePose
 // (:35-60) and RefinePoseWithMatches (PoseRefinement.cpp:37-57) do, then writes outlier[i] to

@@ -24,7 +24,7 @@ from .matcher import BruteForceMatcher, Preprocess, Rectification
 from .orb import ORBExtractor
 import ctypes as C
 
-from .tracking import Camera, FeatureGrid, PoseRefinement, pose_observations
+from .tracking import Camera, FeatureGrid, P3PRansac, PoseRefinement, pose_observations
 
 TUM_COLS = 8  # timestamp tx ty tz qx qy qz qw
 
@@ -146,9 +146,14 @@ class MultiSequenceTracker:
     and four counters coming out.  Same chain and same arithmetic per sequence as `SequenceTracker` (which makes one synchronous
     host call per seam and keeps a GPU ~95 % idle); a sequence is still causally serial, the parallelism is across sequences.
 
-    Image uploads are double buffered on a copy stream (pinned host buffers), so step t + 1's upload runs beside step t's kernels."""
+    Image uploads are double buffered on a copy stream (pinned host buffers), so step t + 1's upload runs beside step t's kernels.
 
-    def __init__(self, cam, n_sequences: int, max_frames: int, orb=None, device: int = 0, width: int = 752, height: int = 480):
+    ransac=True puts the P3P-RANSAC of TrackBruteForce (TrackingCoarse.cpp:403-440, `snk_p3p_ransac_frame_batch_dev`: 250 hypotheses,
+    threshold (2 * 2.1 / fx)^2) between the matches and the refinement: the refinement then starts from the RANSAC pose and sees the
+    inliers only.  The default leaves the chain as it was."""
+
+    def __init__(self, cam, n_sequences: int, max_frames: int, orb=None, device: int = 0, width: int = 752, height: int = 480,
+                 ransac: bool = False, ransac_seed: int = 0):
         import torch
 
         from . import _lib
@@ -169,6 +174,7 @@ class MultiSequenceTracker:
         self.grid = FeatureGrid(device, sh)
         self.bf = BruteForceMatcher(device, sh)
         self.ref = PoseRefinement(device=device, stream=sh)
+        self.p3p = P3PRansac.for_camera(self.cam[0], 250, ransac_seed, device=device, stream=sh) if ransac else None
         self.rect = Rectification.make((1.0, 1.0, 0.0, 0.0))
         self.level_scale = (np.float32(orb["scale_factor"]) ** np.arange(orb["n_levels"])).astype(np.float32)
         self.bounds = (0.0, 0.0, float(width), float(height))
@@ -189,6 +195,7 @@ class MultiSequenceTracker:
             self.taken = z(S, cap, dtype=torch.uint8)
             self.knn, self.pairs, self.n_pairs = z(S, cap, 4, dtype=torch.int32), z(S, cap, 2, dtype=torch.int32), z(S, dtype=torch.int32)
             self.match_idx, self.outlier, self.inliers = z(S, cap, dtype=torch.int32), z(S, cap, dtype=torch.uint8), z(S, dtype=torch.int32)
+            self.ransac_inliers = z(S, dtype=torch.int32)
             self.prev_desc, self.prev_n = z(S, cap, 4, dtype=torch.int64), z(S, dtype=torch.int32)
             self.prev_world, self.prev_has = z(S, cap, 3, dtype=torch.float64), z(S, cap, dtype=torch.uint8)
             self.world, self.has = z(S, cap, 3, dtype=torch.float64), z(S, cap, dtype=torch.uint8)
@@ -203,8 +210,9 @@ class MultiSequenceTracker:
 
     def close(self):
         self.torch.cuda.synchronize(self.dev)
-        for h in (self.ext, self.pre, self.grid, self.bf, self.ref):
-            h.close()
+        for h in (self.ext, self.pre, self.grid, self.bf, self.ref, self.p3p):
+            if h is not None:
+                h.close()
 
     def stage(self, lefts, rights, out=None):
         """The 2 S images of one step in the layout the upload wants ([2 S, H, pitch] uint8, left images first), in PINNED host
@@ -261,6 +269,9 @@ class MultiSequenceTracker:
                 lib.check(lib.load().snk_track_bf_matches_batch_dev(self.ref._h, self.pairs.data_ptr(), self.n_pairs.data_ptr(),
                                                                     self.prev_has.data_ptr(), cap, S, self.match_idx.data_ptr()),
                           "snk_track_bf_matches_batch_dev")
+                if self.p3p is not None:  # :403-440: the pose of the best hypothesis, mvpMapPoints keeps the inliers only
+                    self.p3p.solve_frame_batch_dev(fd, self.cam, self.prev_world.view(torch.uint8).view(S, cap, 24), self.match_idx,
+                                                   self.prev_n, self.poses, self.ransac_inliers)
                 self.ref.refine_frame_batch_dev(fd, self.depth, self.cam, self.prev_world.view(torch.uint8).view(S, cap, 24), self.match_idx,
                                                 self.prev_n, self.level_scale, self.poses, self.outlier, self.inliers)
                 self.counters[2] += self.n_pairs.sum()

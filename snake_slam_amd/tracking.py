@@ -387,6 +387,84 @@ class Triangulator(_Handle):
         return int(out["commit"].sum()), out, out_start
 
 
+class P3PParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("pad", C.c_int32), ("residual_threshold", C.c_double), ("seed", C.c_uint64)]
+
+
+class P3PProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("inliers", C.c_int32), ("wps", C.c_void_p), ("nips", C.c_void_p), ("inlier_mask", C.c_void_p),
+                ("inlier_matches", C.c_void_p), ("pose", C.c_double * 7), ("best_iteration", C.c_int32), ("best_solution", C.c_int32)]
+
+
+class P3PRansac(_Handle):
+    """``P3PRansac pnp2(params)`` of Tracking::TrackBruteForce (reference Snake/Tracking/TrackingCoarse.cpp:403-440), semantics
+    "snk-p3p v1": maxIterations / residualThreshold as RansacParameters has them (``threads`` has no meaning here) plus the seed of
+    the counter-based sampler.  ``for_camera`` sets the threshold the way :412-413 does."""
+
+    def __init__(self, maxIterations: int = 250, residualThreshold: float = 1e-4, seed: int = 0, device: int = 0, stream: int | None = None):
+        super().__init__(device, stream)
+        self.params = P3PParams(int(maxIterations), 0, float(residualThreshold), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    @classmethod
+    def for_camera(cls, fx: float, maxIterations: int = 250, seed: int = 0, device: int = 0, stream: int | None = None):
+        chi1 = 2 * REPROJECTION_ERROR_THRESHOLD_MONO / float(fx)
+        return cls(maxIterations, chi1 * chi1, seed, device, stream)
+
+    def _problems(self, problems):
+        probs = (P3PProblem * max(len(problems), 1))()
+        keep = []
+        for P, f in zip(probs, problems):
+            wps = np.ascontiguousarray(f["wps"], np.float64).reshape(-1, 3)
+            nips = np.ascontiguousarray(f["nips"], np.float64).reshape(-1, 2)
+            if len(wps) != len(nips):
+                raise ValueError("wps / nips length mismatch")
+            mask, lst = np.zeros(max(len(wps), 1), np.uint8), np.zeros(max(len(wps), 1), np.int32)
+            keep.append((wps, nips, mask, lst))
+            P.n = len(wps)
+            P.wps, P.nips = (wps.ctypes.data if wps.size else 0), (nips.ctypes.data if nips.size else 0)
+            P.inlier_mask, P.inlier_matches = mask.ctypes.data, lst.ctypes.data
+            pose = f.get("pose")
+            P.pose[:] = [float(v) for v in (pose if pose is not None else (0, 0, 0, 1, 0, 0, 0))]
+        return probs, keep
+
+    @staticmethod
+    def _result(P, k):
+        return dict(pose=np.array(P.pose[:]), inliers=int(P.inliers), mask=k[2][: P.n].copy(), matches=k[3][: P.inliers].copy(),
+                    best=(int(P.best_iteration), int(P.best_solution)))
+
+    def solve_batch(self, problems):
+        """problems: list of dict(wps [n, 3], nips [n, 2], optional pose [7]).  One launch; returns one dict per problem:
+        pose, inliers, mask [n] uint8, matches (ascending indices), best = (iteration, solution)."""
+        probs, keep = self._problems(problems)
+        _lib.check(self._lib.snk_p3p_ransac(self._h, C.byref(self.params), probs, len(problems)), "snk_p3p_ransac")
+        return [self._result(P, k) for P, k in zip(probs, keep)]
+
+    def solve(self, wps, ips, pose=None):
+        """``inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask)``: returns (inliers, pose, inlierMatches, inlierMask)."""
+        r = self.solve_batch([dict(wps=wps, nips=ips, pose=pose)])[0]
+        return r["inliers"], r["pose"], r["matches"], r["mask"]
+
+    def debug_hypotheses(self, wps, nips, pose=None):
+        """snk_p3p_debug_hypotheses: (result dict as solve_batch, triplets [K, 3], n_solutions [K], poses [K, 4, 7], counts [K, 4])."""
+        probs, keep = self._problems([dict(wps=wps, nips=nips, pose=pose)])
+        K = max(int(self.params.iterations), 1)
+        tri, ns = np.zeros((K, 3), np.int32), np.zeros(K, np.int32)
+        poses, cnt = np.zeros((K, 4, 7), np.float64), np.zeros((K, 4), np.int32)
+        _lib.check(self._lib.snk_p3p_debug_hypotheses(self._h, C.byref(self.params), probs, _ptr(tri), _ptr(ns), _ptr(poses), _ptr(cnt)),
+                   "snk_p3p_debug_hypotheses")
+        K = int(self.params.iterations)
+        return self._result(probs[0], keep[0]), tri[:K], ns[:K], poses[:K], cnt[:K]
+
+    def solve_frame_batch_dev(self, frames: FramesDev, cam, pts, frame_pt, n_pts, poses, inliers):
+        """Device-resident form between BruteForce matches and refine_frame_batch_dev, fed like the latter: frame_pt [B, cap] int32 in /
+        out (-1 at every feature that is not an inlier afterwards), pts [B, m_cap, stride] uint8, n_pts [B] int32, poses [B, 7] float64
+        out, inliers [B] int32 out.  Asynchronous on the handle's stream."""
+        c = Camera(*cam)
+        _lib.check(self._lib.snk_p3p_ransac_frame_batch_dev(self._h, C.byref(frames), C.byref(c), C.byref(self.params), pts.data_ptr(),
+                                                            int(pts.shape[2]), frame_pt.data_ptr(), n_pts.data_ptr(), int(pts.shape[1]),
+                                                            poses.data_ptr(), inliers.data_ptr()), "snk_p3p_ransac_frame_batch_dev")
+
+
 class BowFeatures(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("pad", C.c_int32), ("node_id", C.c_void_p), ("node_start", C.c_void_p),
                 ("features", C.c_void_p)]
