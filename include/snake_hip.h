@@ -853,6 +853,84 @@ SNK_API int snk_p3p_ransac_frame_batch_dev(snk_matcher* m, const snk_frames_dev*
                                            const int32_t* n_pts_dev, int pts_cap, double* poses_dev, int32_t* inliers_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Registration RANSAC of the loop detector (semantics "snk-sim3 v1")
+ * ------------------------------------------------------------------------------------------ */
+
+/* What LoopDetector::solve sets on its solver -- Snake/LoopClosing/LoopDetector.cpp:152-205: threshold = 12 squared pixels (:156),
+ * compute_scale (:231: mono input only), and the iteration count of :203, RansacIterationsFromProbability(N, 0.999, 15, 100) =
+ * (probability, min_inliers, max_iterations).  iterations > 0 forces the count; iterations = 0 uses
+ * snk_ransac_iterations(n, probability, min_inliers, max_iterations) per problem.  seed: the sampler is the counter-based hash of
+ * "snk-p3p v1" over (seed, problem index in the call, hypothesis, draw).  Limits: iterations and max_iterations <= 2^20,
+ * 0 < probability < 1, min_inliers >= 1, max_iterations >= 1 (the last three are read only with iterations = 0). */
+typedef struct snk_sim3_params
+{
+    int32_t iterations;
+    int32_t compute_scale;
+    double threshold;
+    uint64_t seed;
+    double probability;
+    int32_t min_inliers, max_iterations;
+} snk_sim3_params;
+
+/* One call of `solver.solve(its, compute_scale)` -- LoopDetector.cpp:152-205: pair i is points1[i] = pose1 * (point of keyframe 1)
+ * (:193), points2[i] = pose2 * (its partner of keyframe 2) (:194), ips1[i] / ips2[i] = their undistorted keypoints in pixels
+ * (:185-190); cam = K for both views (:158-159; bf is not read); n <= 2048.  Out: T = qx qy qz qw tx ty tz and scale with
+ * points2 ~ scale * R * points1 + t (both left as they came in when n < 3 or no hypothesis has an inlier), inliers, inlier_mask[n]
+ * (vbInliers, :200-201), best_iteration (-1 without a winner). */
+typedef struct snk_sim3_problem
+{
+    int32_t n;
+    int32_t inliers;
+    const double (*points1)[3];
+    const double (*points2)[3];
+    const double (*ips1)[2];
+    const double (*ips2)[2];
+    uint8_t* inlier_mask;
+    snk_camera cam;
+    double T[7];
+    double scale;
+    int32_t best_iteration, pad;
+} snk_sim3_problem;
+
+/* RansacIterationsFromProbability of LoopDetector.cpp:203 (the function is in saiga; [DEFINED]): eps = min_inliers / n; 1 when
+ * n <= 0 or eps >= 1, else ceil(log(1 - probability) / log(1 - eps^3)) in double, clamped to [1, max_iterations].  Host helper. */
+SNK_API int snk_ransac_iterations(int n, double probability, int min_inliers, int max_iterations);
+
+/* Replaces LoopDetector::solve's `solver.solve(its, compute_scale)` for a batch of problems -- LoopDetector.cpp:148-206: per
+ * hypothesis three distinct pairs, the similarity (or rigid) transform of the two triplets by Horn's quaternion method, scored
+ * against all n pairs by the reprojection error in both images (inlier <=> both points in front of their camera and both squared
+ * errors < threshold); the winner has the most inliers, ties go to the smaller hypothesis; no refinement (the projection search and
+ * RefinePoseWithMatches follow at :279-284).  Host pointers, synchronous, one launch for the batch; the result is identical from run
+ * to run.  n_problems == 0 is valid; n > 2048 is SNK_ERR_INVALID_ARG. */
+SNK_API int snk_sim3_ransac(snk_matcher* m, const snk_sim3_params* params, snk_sim3_problem* problems, int n_problems);
+
+/* The same for ONE problem with every hypothesis laid open, for tests (LoopDetector.cpp:205 has no counterpart: the loop is inside
+ * the solver): triplets[k] = the three pair indices of hypothesis k, valid[k] = the triplet gave a transform, T[k] / scale[k] /
+ * counts[k] = that transform and its inlier count (zeros when not valid).  All arrays have K entries, K = params->iterations when
+ * that is > 0, else snk_ransac_iterations(problem->n, ...).  `problem` is filled as by snk_sim3_ransac. */
+SNK_API int snk_sim3_debug_hypotheses(snk_matcher* m, const snk_sim3_params* params, snk_sim3_problem* problem,
+                                      int32_t (*triplets)[3], int32_t* valid, double (*T)[7], double* scale, int32_t* counts);
+
+/* Device-resident form for a batch of keyframe pairs (b = 0 .. frames1->batch - 1; keyframe 1 = source, 2 = target) --
+ * LoopDetector.cpp:163-198, 250-278 with Snake/LoopClosing/LoopORBMatcher.cpp:110-116: pairs_dev [batch][pairs_cap][2] = (f1, f2),
+ * n_pairs_dev [batch] is the output of snk_bf_filter_batch_dev with keyframe 1 as the query set.  An entry becomes a pair when both
+ * features carry a point, 0 <= frame_pt1_dev[b][f1] < n_pts1_dev[b] and 0 <= frame_pt2_dev[b][f2] < n_pts2_dev[b]; the pairs keep
+ * the order of the entries.  points1 = poses1_dev[b] * (3 doubles at pts1_dev + (b * pts_cap + frame_pt1) * pts_stride), points2
+ * likewise (:193-194, computed by the kernel), ips = frames1->kps[b][f1] / frames2->kps[b][f2]; problem index = b; with
+ * params->iterations = 0 the count is looked up in a table of snk_ransac_iterations kept by the handle.  Out: T_dev [batch][7],
+ * scale_dev [batch] and corrected_pose_dev [batch][7] = tmpPose of :251-255,278, (R^T R2, R^T (t2 - t) / scale) with (R2, t2) =
+ * poses2_dev[b] -- all three untouched without a winner; inliers_dev [batch]; match12_dev [batch][frames1->cap] = the point index
+ * of keyframe 2 at every inlier's f1 and -1 everywhere else (vpMapPointMatches of :265-269 as indices).  pairs_cap <= 2048.
+ * Asynchronous on the handle's stream: kNN-2 -> filter -> this call run without a host round trip. */
+SNK_API int snk_sim3_ransac_pairs_batch_dev(snk_matcher* m, const snk_frames_dev* frames1, const snk_frames_dev* frames2,
+                                            const snk_camera* cam, const snk_sim3_params* params, const int32_t* pairs_dev,
+                                            const int32_t* n_pairs_dev, int pairs_cap, const void* pts1_dev, const void* pts2_dev,
+                                            int pts_stride, const int32_t* frame_pt1_dev, const int32_t* frame_pt2_dev,
+                                            const int32_t* n_pts1_dev, const int32_t* n_pts2_dev, int pts_cap, const double* poses1_dev,
+                                            const double* poses2_dev, double* T_dev, double* scale_dev, int32_t* inliers_dev,
+                                            int32_t* match12_dev, double* corrected_pose_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Local bundle adjustment
  * ------------------------------------------------------------------------------------------ */
 

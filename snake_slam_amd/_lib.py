@@ -77,6 +77,10 @@ SIGNATURES = {
     "snk_p3p_ransac": (i32, [vp, vp, vp, i32]),
     "snk_p3p_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "snk_p3p_ransac_frame_batch_dev": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+    "snk_ransac_iterations": (i32, [i32, f64, i32, i32]),
+    "snk_sim3_ransac": (i32, [vp, vp, vp, i32]),
+    "snk_sim3_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "snk_sim3_ransac_pairs_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "snk_frontend_create": (i32, [vp, i32, C.POINTER(vp)]),
     "snk_frontend_destroy": (i32, [vp]),
     "snk_frontend_max_keypoints": (i32, [vp, i32, i32, C.POINTER(i32)]),

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -795,6 +796,92 @@ class P3PRansac
 
    private:
     RansacParameters params_;
+    snk_matcher* h_ = nullptr;
+};
+
+// The `solver` member of Snake::LoopDetector as LoopDetector::solve fills and calls it -- Snake/LoopClosing/LoopDetector.cpp:152-205,
+// semantics "snk-sim3 v1":
+//   solver.clear();  solver.pose1 = pKF1->Pose();  solver.pose2 = pKF2->Pose();  solver.threshold = 12;  solver.camera1 = K; ...
+//   solver.ips1.push_back(kp1.point);  solver.points1.push_back(solver.pose1 * pMP1->getPosition());  ...  solver.N++;
+//   int its = RansacIterationsFromProbability(solver.N, 0.999, 15, 100);
+//   auto [T, scale, nInliers] = solver.solve(its, compute_scale);
+// SE3 is qx qy qz qw tx ty tz with points2 ~ scale * R * points1 + t (identity / 1 without a winner); pose1 / pose2 are kept for the
+// caller, who multiplies the map points by them as :193-194 do (`transform`).  inlierMask is vbInliers of :200-201; `seed` feeds the
+// counter-based sampler (a call is a pure function of its arguments).
+inline int RansacIterationsFromProbability(int N, double probability, int minInliers, int maxIterations)
+{
+    return snk_ransac_iterations(N, probability, minInliers, maxIterations);
+}
+
+class RegistrationRansac
+{
+   public:
+    using SE3  = std::array<double, 7>;
+    using Vec3 = std::array<double, 3>;
+    using Vec2 = std::array<double, 2>;
+
+    explicit RegistrationRansac(int device = 0) { check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create"); }
+    ~RegistrationRansac() { snk_matcher_destroy(h_); }
+    RegistrationRansac(const RegistrationRansac&)            = delete;
+    RegistrationRansac& operator=(const RegistrationRansac&) = delete;
+
+    void clear()
+    {
+        points1.clear();
+        points2.clear();
+        ips1.clear();
+        ips2.clear();
+        inlierMask.clear();
+        N = 0;
+    }
+
+    // pose * p for a pose world -> camera (the product of :193-194)
+    static Vec3 transform(const SE3& pose, const Vec3& p)
+    {
+        const double x = pose[0], y = pose[1], z = pose[2], w = pose[3];
+        const double R[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w),       2.0 * (x * z + y * w),
+                             2.0 * (x * y + z * w),       1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w),
+                             2.0 * (x * z - y * w),       2.0 * (y * z + x * w),       1.0 - 2.0 * (x * x + y * y)};
+        Vec3 o;
+        for (int r = 0; r < 3; ++r) o[(size_t)r] = ((R[3 * r] * p[0] + R[3 * r + 1] * p[1]) + R[3 * r + 2] * p[2]) + pose[(size_t)(4 + r)];
+        return o;
+    }
+
+    std::tuple<SE3, double, int> solve(int its, bool compute_scale)
+    {
+        const size_t n = points1.size();
+        if (points2.size() != n || ips1.size() != n || ips2.size() != n) throw std::invalid_argument("RegistrationRansac::solve: sizes");
+        std::vector<uint8_t> mask(n + 1);
+        snk_sim3_params p{its, compute_scale ? 1 : 0, threshold, seed, 0.999, 15, 100};
+        snk_sim3_problem q{};
+        q.n           = (int32_t)n;
+        q.points1     = reinterpret_cast<const double(*)[3]>(points1.data());
+        q.points2     = reinterpret_cast<const double(*)[3]>(points2.data());
+        q.ips1        = reinterpret_cast<const double(*)[2]>(ips1.data());
+        q.ips2        = reinterpret_cast<const double(*)[2]>(ips2.data());
+        q.inlier_mask = mask.data();
+        q.cam         = camera1;
+        q.T[3]        = 1.0;
+        q.scale       = 1.0;
+        check(snk_sim3_ransac(h_, &p, &q, 1), "snk_sim3_ransac");
+        inlierMask.assign(mask.begin(), mask.begin() + (std::ptrdiff_t)n);
+        best_iteration = q.best_iteration;
+        SE3 T;
+        std::memcpy(T.data(), q.T, sizeof(q.T));
+        return {T, q.scale, q.inliers};
+    }
+
+    std::vector<Vec3> points1, points2;
+    std::vector<Vec2> ips1, ips2;
+    SE3 pose1{{0, 0, 0, 1, 0, 0, 0}}, pose2{{0, 0, 0, 1, 0, 0, 0}};
+    double threshold = 12;
+    int N            = 0;
+    snk_camera camera1{}, camera2{};
+    uint64_t seed = 0;
+    std::vector<char> inlierMask;
+    int best_iteration = -1;  // the winning hypothesis of the last solve
+
+   private:
     snk_matcher* h_ = nullptr;
 };
 

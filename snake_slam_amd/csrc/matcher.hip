@@ -897,6 +897,8 @@ int snk_matcher_destroy(snk_matcher* m)
     m->view.release();
     m->h_in.release();
     m->h_res.release();
+    m->sim3_its.release();
+    m->sim3_its_host.release();
     m->fini();
     delete m;
     return SNK_OK;

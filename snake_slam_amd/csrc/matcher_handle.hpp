@@ -15,6 +15,12 @@ struct snk_matcher : snk::HandleBase
     bool view_valid = false;  // snk_match_bind_frame: the arrays below live in `view`
     int view_n = 0, view_cols = 0, view_rows = 0;
     double view_bounds[4] = {0, 0, 0, 0};
+    // sim3.hip: its[n], n = 0 .. sim3_its_cap, of snk_ransac_iterations under the parameters it was last filled with (the device-resident
+    // registration RANSAC looks its iteration count up instead of evaluating log); pinned copy = the source of the upload
+    snk::DevBuf sim3_its;
+    snk::HostBuf sim3_its_host;
+    int sim3_its_cap = -1, sim3_its_min = 0, sim3_its_max = 0;
+    double sim3_its_probability = 0.0;
 };
 
 namespace snk
