@@ -1060,6 +1060,66 @@ SNK_API int snk_ba_solve_local_scene(snk_ba* h, int problem, double chi2_mono, d
                                      double (*pose)[7], double (*pt)[3]);
 
 /* ------------------------------------------------------------------------------------------
+ * Pose-graph optimisation of the loop corrector -- semantics "snk-pgo v1" 
+ * ------------------------------------------------------------------------------------------
+ * Replaces: the solve behind LoopClosing::OptimizeEssentialGraph (Snake/LoopClosing/LoopClosingPGO.cpp:120-264: PGORec / PGOSim3Rec
+ * create + initAndSolve at :134-146, the map-point pass at :231-260) on the graph LoopClosing::ConstructPGO leaves
+ * (LoopClosingPGO.cpp:16-118).  saiga's solver is absent: the residual, the update, the exact Jacobians, the LM schedule and the
+ * linear solve are [DEFINED] in DESIGN.md section 3f and restated in tests/pgo_numpy.py.
+ * A pose is 8 doubles qx qy qz qw tx ty tz s (T_w_i, x -> s R x + t); s is read only when fix_scale == 0.
+ * Limits: up to SNK_PGO_MAX_VERTICES vertices and SNK_PGO_MAX_EDGES edges.  Graphs whose rows do not fit the resident PCG kernel
+ * (more workgroups than the device holds at once, or one vertex with more than about 380 free neighbours) are solved by the
+ * multi-launch PCG instead of being refused.  One handle per thread; calls on a handle are serial and synchronous. */
+typedef struct snk_pgo snk_pgo;
+#define SNK_PGO_MAX_VERTICES 10000 /* the keyframe limit of snk_ba */
+#define SNK_PGO_MAX_EDGES 200000   /* 1 304 bytes of device memory per edge: 260 MB */
+
+typedef struct snk_pgo_options
+{
+    int32_t max_iterations;     /* LM iterations, 50 at LoopClosingPGO.cpp:125 */
+    int32_t max_pcg_iterations; /* cap of the PCG per LM iteration; 10000 (the most a test graph takes is 2 078) */
+    double pcg_tol;             /* stop when r.z <= pcg_tol * (r.z at the start); 1e-20, i.e. 1e-10 on the preconditioned residual norm */
+    double min_chi2_delta;      /* stop after the first accepted step that lowers the cost by less; 1e-10 at LoopClosingPGO.cpp:126 */
+    double lambda_init;         /* 1e-4, the schedule of snk-ba v1 */
+} snk_pgo_options;
+
+typedef struct snk_pgo_result
+{
+    double cost_initial, cost_final; /* what LoopClosingPGO.cpp:137-139 prints */
+    int32_t lm_iterations, pcg_iterations_total, accepted_steps;
+    int32_t pcg_form;   /* of the last linear solve: 0 none ran, 1 one cooperative launch (resident), 2 one launch per phase */
+    int32_t workgroups; /* of that solve */
+    int32_t pcg_iterations_max; /* the most PCG iterations one linear solve took: equal to max_pcg_iterations when the cap cut a solve short */
+} snk_pgo_result;
+
+SNK_API int snk_pgo_create(const snk_pgo_options* options, int device, void* stream, snk_pgo** out);
+SNK_API int snk_pgo_destroy(snk_pgo* h);
+/* The result of ConstructPGO (LoopClosingPGO.cpp:16-118): vertices with their constant flags (:63-70), edges (i, j) with i < j, unique
+ * and sorted (:90,99,108), weights (NULL: all 1).  measurements[e] = T_i_j; NULL: T_w_i^-1 T_w_j of poses_measure, the poses the edges
+ * are measured at (AddVertexEdge at :105, before SetPose at :114 moves the corrected vertices).  poses_init: the start state (NULL:
+ * poses_measure).  Refused with SNK_ERR_INVALID_ARG and a text in snk_last_error(): i >= j, duplicate or unsorted edges, indices out of
+ * range, non-finite input, with fix_scale a scale other than 1 (without: a scale <= 0).  Zero vertices or zero edges is valid.  A refused
+ * call changes nothing: the handle stays usable and keeps the graph it had. */
+SNK_API int snk_pgo_set_graph(snk_pgo* h, int n_vertices, const double (*poses_measure)[8], const double (*poses_init)[8],
+                              const uint8_t* constant, int n_edges, const int32_t (*edges)[2], const double* weights,
+                              const double (*measurements)[8], int fix_scale);
+/* initAndSolve (LoopClosingPGO.cpp:134-146). */
+SNK_API int snk_pgo_solve(snk_pgo* h, snk_pgo_result* result);
+/* The current state (LoopClosingPGO.cpp:148-229 read the optimised vertices back). */
+SNK_API int snk_pgo_get_poses(snk_pgo* h, double (*poses)[8]);
+/* sum of |r_e|^2 at the current state (the chi2 of LoopClosingPGO.cpp:137-139). */
+SNK_API int snk_pgo_cost(snk_pgo* h, double* cost);
+/* Tests: linearises at the current state; residuals [E][7], gradient J^T r [n][7] and diagonal blocks [n][49] of ALL vertices (constant
+ * ones included, before damping); the se3 form leaves entry / row / column 6 zero.  Each may be NULL. */
+SNK_API int snk_pgo_debug_linearisation(snk_pgo* h, double (*residuals)[7], double (*gradient)[7], double (*diag)[49]);
+/* The map-point pass of OptimizeEssentialGraph (LoopClosingPGO.cpp:231-247; MapPoint::Transform spelled out at :256-260): point k with
+ * reference vertex ref_vertex[k] moves by T_w_i^after (T_w_i^before)^-1 as a Sim3 -- position, normal (rotation only), reference_depth
+ * times the scale -- where before = poses_measure of the last snk_pgo_set_graph and after = the current state.  ref -1 or a constant
+ * vertex: untouched.  Host pointers; normals and reference_depth may be NULL. */
+SNK_API int snk_pgo_transform_points(snk_pgo* h, int n_points, const int32_t* ref_vertex, double (*positions)[3], double (*normals)[3],
+                                     double* reference_depth);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU result gather (BASELINE config 5: one sequence per GPU)
  * ------------------------------------------------------------------------------------------
  * The path shards over independent units -- one Snake-SLAM process and one sequence per GPU -- and exchanges nothing while it

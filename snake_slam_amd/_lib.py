@@ -81,6 +81,14 @@ SIGNATURES = {
     "snk_sim3_ransac": (i32, [vp, vp, vp, i32]),
     "snk_sim3_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "snk_sim3_ransac_pairs_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "snk_pgo_create": (i32, [vp, i32, vp, C.POINTER(vp)]),
+    "snk_pgo_destroy": (i32, [vp]),
+    "snk_pgo_set_graph": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32]),
+    "snk_pgo_solve": (i32, [vp, vp]),
+    "snk_pgo_get_poses": (i32, [vp, vp]),
+    "snk_pgo_cost": (i32, [vp, C.POINTER(f64)]),
+    "snk_pgo_debug_linearisation": (i32, [vp, vp, vp, vp]),
+    "snk_pgo_transform_points": (i32, [vp, i32, vp, vp, vp, vp]),
     "snk_frontend_create": (i32, [vp, i32, C.POINTER(vp)]),
     "snk_frontend_destroy": (i32, [vp]),
     "snk_frontend_max_keypoints": (i32, [vp, i32, i32, C.POINTER(i32)]),

@@ -886,6 +886,112 @@ class RegistrationRansac
 };
 
 
+// The pose graph of LoopClosing::ConstructPGO and its solvers (reference Snake/LoopClosing/LoopClosingPGO.cpp:16-118, :120-264; semantics
+// "snk-pgo v1"), used as OptimizeEssentialGraph does:
+//   PoseGraph pg(poses, constant, fixScale);  pg.AddVertexEdge(i, j, weight); ...  pg.sortEdges();  pg.SetPose(source, T_w_correctSource);
+//   PGORec rec (or PGOSim3Rec);  rec.optimizationOptions = ...;  rec.create(pg);  auto result = rec.initAndSolve();   // :134-146
+//   rec.poses() ...;  TransformMapPoints(rec, ref, positions, normals, referenceDepth);                               // :231-260
+// A Sim3 is qx qy qz qw tx ty tz s.  AddVertexEdge measures T_i_j at the poses the graph was built with (:105); SetPose (:114) moves a
+// vertex afterwards without touching those measurements.
+struct PoseGraph
+{
+    using Sim3 = std::array<double, 8>;
+    struct Edge
+    {
+        int from, to;
+        double weight;
+    };
+    PoseGraph() = default;
+    PoseGraph(std::vector<Sim3> p, std::vector<uint8_t> c, bool fix) : posesMeasure(p), poses(std::move(p)), constant(std::move(c)), fixScale(fix) {}
+    void AddVertexEdge(int i, int j, double weight = 1.0) { edges.push_back(i < j ? Edge{i, j, weight} : Edge{j, i, weight}); }
+    void sortEdges()  // by (from, to); of several edges between one pair the first one added stays
+    {
+        std::stable_sort(edges.begin(), edges.end(), [](const Edge& a, const Edge& b) { return a.from != b.from ? a.from < b.from : a.to < b.to; });
+        edges.erase(std::unique(edges.begin(), edges.end(), [](const Edge& a, const Edge& b) { return a.from == b.from && a.to == b.to; }), edges.end());
+    }
+    void SetPose(int i, const Sim3& T) { poses.at((size_t)i) = T; }
+    std::vector<Sim3> posesMeasure, poses;
+    std::vector<uint8_t> constant;
+    std::vector<Edge> edges;
+    bool fixScale = true;
+};
+
+class PGOBase
+{
+   public:
+    PGOBase(const PGOBase&)            = delete;
+    PGOBase& operator=(const PGOBase&) = delete;
+    ~PGOBase() { snk_pgo_destroy(h_); }
+
+    snk_pgo_options optimizationOptions{50, 10000, 1e-20, 1e-10, 1e-4};  // maxIterations, minChi2Delta: LoopClosingPGO.cpp:125-126
+
+    void create(const PoseGraph& pg)
+    {
+        if (pg.fixScale != fix_) throw std::invalid_argument("PGORec solves fixScale graphs, PGOSim3Rec the others");
+        if (pg.posesMeasure.size() != pg.poses.size() || pg.constant.size() != pg.poses.size()) throw std::invalid_argument("PoseGraph: array sizes");
+        if (h_) snk_pgo_destroy(h_);
+        h_ = nullptr;
+        check(snk_pgo_create(&optimizationOptions, device_, nullptr, &h_), "snk_pgo_create");
+        std::vector<int32_t> e;
+        std::vector<double> w;
+        for (const auto& x : pg.edges) e.push_back(x.from), e.push_back(x.to), w.push_back(x.weight);
+        n_ = (int)pg.poses.size();
+        check(snk_pgo_set_graph(h_, n_, reinterpret_cast<const double(*)[8]>(pg.posesMeasure.data()), reinterpret_cast<const double(*)[8]>(pg.poses.data()),
+                                pg.constant.data(), (int)pg.edges.size(), reinterpret_cast<const int32_t(*)[2]>(e.data()), w.data(), nullptr, fix_ ? 1 : 0),
+              "snk_pgo_set_graph");
+    }
+    snk_pgo_result initAndSolve()
+    {
+        snk_pgo_result r{};
+        check(snk_pgo_solve(handle(), &r), "snk_pgo_solve");
+        return r;
+    }
+    std::vector<PoseGraph::Sim3> poses()
+    {
+        std::vector<PoseGraph::Sim3> out((size_t)n_);
+        check(snk_pgo_get_poses(handle(), reinterpret_cast<double(*)[8]>(out.data())), "snk_pgo_get_poses");
+        return out;
+    }
+    snk_pgo* handle()
+    {
+        if (!h_) throw std::logic_error("PGO: create(pg) first");
+        return h_;
+    }
+
+   protected:
+    PGOBase(bool fix, int device) : fix_(fix), device_(device) {}
+
+   private:
+    bool fix_;
+    int device_;
+    int n_      = 0;
+    snk_pgo* h_ = nullptr;
+};
+class PGORec : public PGOBase
+{
+   public:
+    explicit PGORec(int device = 0) : PGOBase(true, device) {}
+};
+class PGOSim3Rec : public PGOBase
+{
+   public:
+    explicit PGOSim3Rec(int device = 0) : PGOBase(false, device) {}
+};
+
+// The map-point pass of OptimizeEssentialGraph (:231-247, MapPoint::Transform at :256-260): normals / referenceDepth may be empty.
+inline void TransformMapPoints(PGOBase& rec, const std::vector<int32_t>& referenceVertex, std::vector<std::array<double, 3>>& positions,
+                               std::vector<std::array<double, 3>>& normals, std::vector<double>& referenceDepth)
+{
+    const size_t n = referenceVertex.size();
+    if (positions.size() != n || (!normals.empty() && normals.size() != n) || (!referenceDepth.empty() && referenceDepth.size() != n))
+        throw std::invalid_argument("TransformMapPoints: sizes");
+    check(snk_pgo_transform_points(rec.handle(), (int)n, referenceVertex.data(), reinterpret_cast<double(*)[3]>(positions.data()),
+                                   normals.empty() ? nullptr : reinterpret_cast<double(*)[3]>(normals.data()),
+                                   referenceDepth.empty() ? nullptr : referenceDepth.data()),
+          "snk_pgo_transform_points");
+}
+
+
 // Snake::PoseRefinement (reference Snake/Tracking/PoseRefinement.h:22-99): the robust pose-only
 // optimisation after every matcher call.  The caller gathers wps / obs / idx exactly as refinePose
 // (:35-60) and RefinePoseWithMatches (PoseRefinement.cpp:37-57) do, then writes outlier[i] to
