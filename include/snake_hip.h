@@ -1120,6 +1120,103 @@ SNK_API int snk_pgo_transform_points(snk_pgo* h, int n_points, const int32_t* re
                                      double* reference_depth);
 
 /* ------------------------------------------------------------------------------------------
+ * Bag-of-words place recognition -- semantics "snk-bow v1" 
+ * ------------------------------------------------------------------------------------------
+ * Replaces, in the order the loop closer and the relocaliser run them: `vocabulary.transform(descriptors, bow_vec, bow_feature_vec, 4,
+ * threads)` of Frame::computeBoW (Snake/Map/Frame.cpp:38-40), KeyframeDatabase::Add / Remove / DetectLoopCandidates /
+ * DetectRelocalizationCandidates (Snake/LoopClosing/KeyframeDatabase.cpp:20-168; call sites Snake/LoopClosing/LoopDetector.cpp:69-87 and
+ * Snake/Tracking/TrackingCoarse.cpp:521), `vocabulary.score` (LoopDetector.cpp:73) and LoopORBmatcher::MatchBoW
+ * (Snake/LoopClosing/LoopORBMatcher.cpp:121-215, called at LoopDetector.cpp:225).  Saiga::MiniBow2 and ORBvoc.minibow are absent: the
+ * descent, the weighting and the score are [DEFINED] in DESIGN.md section 3g (DBoW2's published rules) and restated in
+ * tests/bow_numpy.py; parity with MiniBow2 itself is not pinned.
+ * Limits: SNK_BOW_MAX_FEATURES features per frame (and words per query or database row), SNK_BOW_MAX_CANDIDATES candidates per query,
+ * a vocabulary of depth <= SNK_BOW_MAX_DEPTH.  One handle per thread; a database works on its vocabulary's stream. */
+typedef struct snk_bow_vocab snk_bow_vocab;
+typedef struct snk_bow_db snk_bow_db;
+#define SNK_BOW_MAX_FEATURES 2048
+#define SNK_BOW_MAX_CANDIDATES 64
+#define SNK_BOW_MAX_DEPTH 16
+
+/* The vocabulary `ORBVocabulary vocabulary` of Snake/System/System.cpp:44 as a rooted tree in flat arrays: node 0 is the root; node i
+ * has the children children[child_start[i] .. child_start[i] + child_count[i]) (child_count 0 = leaf), the descriptor desc[i] (the
+ * root's is unused), word_id[i] (dense 0 .. n_words - 1 on leaves, -1 inside) and weight[i] (leaves).  The tree may be irregular.
+ * Validated on the host before a device is touched: every non-root node the child of exactly one node, no cycle, every leaf a word id
+ * and each id once, depth <= 16, weights finite and >= 0 -- anything else is SNK_ERR_INVALID_ARG with the reason in snk_last_error(). */
+SNK_API int snk_bow_vocab_create(int n_nodes, const int32_t* child_start, const int32_t* child_count, const int32_t* children,
+                                 int n_children, const uint64_t (*desc)[4], const int32_t* word_id, const double* weight, int device,
+                                 void* stream, snk_bow_vocab** out);
+SNK_API int snk_bow_vocab_destroy(snk_bow_vocab* v);
+/* vocabulary.size() (KeyframeDatabase.cpp:15-16) = *n_words; also the node count and the depth L of the deepest leaf.  Each may be NULL. */
+SNK_API int snk_bow_vocab_size(const snk_bow_vocab* v, int* n_words, int* n_nodes, int* depth);
+
+/* Frame::computeBoW (Frame.cpp:38-40) for one frame in host memory, n <= SNK_BOW_MAX_FEATURES.  bow_vec: words[*n_words] ascending with
+ * values (count * weight, divided by the L1 norm; *n_words = 0 when the norm is 0).  bow_feature_vec in the snk_bow_features layout:
+ * node_id[*n_nodes] strictly ascending, node_start[*n_nodes + 1], features ascending inside a node; the node of a feature is the one on
+ * its path at depth L - levelsup, and a feature whose node would be the root (L - levelsup <= 0, or a leaf above that depth) is in no
+ * node.  word_of_feature[n] / node_of_feature[n] (0 = none).  Arrays hold n entries, node_start n + 1. */
+SNK_API int snk_bow_transform(snk_bow_vocab* v, const uint64_t (*desc)[4], int n, int levelsup, int32_t* words, double* values,
+                              int* n_words, uint32_t* node_id, int32_t* node_start, int32_t* features, int* n_nodes,
+                              int32_t* word_of_feature, int32_t* node_of_feature);
+/* The same for every frame of a batch that lies in HBM (frames->desc [batch][cap][4], frames->n [batch]; the other members are not
+ * read): straight behind snk_orb_detect_batch_dev / snk_feature_grid_batch_dev.  Outputs [batch][cap], node_start [batch][cap + 1],
+ * n_words / n_nodes [batch]; word_of_feature is -1 and node_of_feature 0 behind a frame's n.  cap <= SNK_BOW_MAX_FEATURES.
+ * Asynchronous on the vocabulary's stream (Frame.cpp:38-40). */
+SNK_API int snk_bow_transform_batch_dev(snk_bow_vocab* v, const snk_frames_dev* frames, int levelsup, int32_t* words_dev,
+                                        double* values_dev, int32_t* n_words_dev, uint32_t* node_id_dev, int32_t* node_start_dev,
+                                        int32_t* features_dev, int32_t* n_nodes_dev, int32_t* word_of_feature_dev,
+                                        int32_t* node_of_feature_dev);
+/* `vocabulary.score(a, b)` (LoopDetector.cpp:73): the L1 score -1/2 sum over the common words of (|a_w - b_w| - a_w - b_w), in double.
+ * Both vectors are in host memory, so this is a merge on the host; the database entry points below score on the device. */
+SNK_API int snk_bow_score(const snk_bow_vocab* v, const int32_t* words_a, const double* values_a, int n_a, const int32_t* words_b,
+                          const double* values_b, int n_b, double* score);
+
+/* KeyframeDatabase (KeyframeDatabase.cpp:10-18): device-resident, one row of at most max_words <= SNK_BOW_MAX_FEATURES words per
+ * keyframe, no inverted file. */
+SNK_API int snk_bow_db_create(snk_bow_vocab* v, int max_keyframes, int max_words, snk_bow_db** out);
+SNK_API int snk_bow_db_destroy(snk_bow_db* db);
+/* KeyframeDatabase::Add (KeyframeDatabase.cpp:20-26).  An id that is already stored, a negative id, unsorted words or a full database:
+ * SNK_ERR_INVALID_ARG, nothing changes. */
+SNK_API int snk_bow_db_add(snk_bow_db* db, int kf_id, const int32_t* words, const double* values, int n);
+/* Add for `count` keyframes whose rows the batched transform left in HBM: kf_ids [count] on the host, words_dev / values_dev
+ * [count][cap], n_words_dev [count], cap <= max_words is not required (a longer row is cut at max_words) (KeyframeDatabase.cpp:20-26). */
+SNK_API int snk_bow_db_add_batch_dev(snk_bow_db* db, const int32_t* kf_ids, int count, const int32_t* words_dev,
+                                     const double* values_dev, const int32_t* n_words_dev, int cap);
+/* KeyframeDatabase::Remove (KeyframeDatabase.cpp:28-56).  An id that is not stored: SNK_ERR_INVALID_ARG.  The id may be added again. */
+SNK_API int snk_bow_db_remove(snk_bow_db* db, int kf_id);
+/* GetKeyframesWithSharingWords + RemoveWeakMatches (KeyframeDatabase.cpp:100-168) as DetectLoopCandidates (:58-80: exclude_ids = the
+ * connected keyframes, 0.8, 0.75, minScore) and DetectRelocalizationCandidates (:83-98: no exclusion, 0.8, 0.75, 0) call them: the
+ * stored keyframes with >= 1 common word that are not excluded; drop common < sharing_word_ratio * maxCommon (float, :137); score;
+ * drop score < score_ratio * best or < min_score (double); order by score descending, ties to the lower id; the first
+ * max_candidates <= SNK_BOW_MAX_CANDIDATES.  out_ids / out_scores / out_common hold max_candidates entries (out_common may be NULL). */
+SNK_API int snk_bow_db_query(snk_bow_db* db, const int32_t* words, const double* values, int n, const int32_t* exclude_ids,
+                             int n_exclude, float sharing_word_ratio, float score_ratio, float min_score, int max_candidates,
+                             int32_t* out_ids, double* out_scores, int32_t* out_common, int* n_out);
+/* n_queries queries in one launch pair (relocalising many frames, TrackingCoarse.cpp:521, or checking many keyframes,
+ * LoopDetector.cpp:69-87): words_dev / values_dev [n_queries][cap], n_words_dev [n_queries]; exclude_ids_dev [n_queries][exclude_cap]
+ * with n_exclude_dev [n_queries], or NULL; outputs [n_queries][max_candidates] and n_out_dev [n_queries].  Asynchronous. */
+SNK_API int snk_bow_db_query_batch_dev(snk_bow_db* db, int n_queries, const int32_t* words_dev, const double* values_dev,
+                                       const int32_t* n_words_dev, int cap, const int32_t* exclude_ids_dev, const int32_t* n_exclude_dev,
+                                       int exclude_cap, float sharing_word_ratio, float score_ratio, float min_score, int max_candidates,
+                                       int32_t* out_ids_dev, double* out_scores_dev, int32_t* out_common_dev, int32_t* n_out_dev);
+
+/* Replaces LoopORBmatcher::MatchBoW(source, target, matches, 50, 0.75) -- LoopORBMatcher.cpp:121-215, call site LoopDetector.cpp:225.
+ * desc / has_mp (GetMapPoint(i) != nullptr and not bad) of each keyframe, bow = its bow_feature_vec.  match12[n1] = the feature of
+ * keyframe 2 whose map point vpMatches12 would hold, or -1; *n_matches = the return value.  0 <= threshold <= 256. */
+SNK_API int snk_match_loop_bow(snk_matcher* m, const uint64_t (*desc1)[4], const uint8_t* has_mp1, int n1, const snk_bow_features* bow1,
+                               const uint64_t (*desc2)[4], const uint8_t* has_mp2, int n2, const snk_bow_features* bow2, int threshold,
+                               float ratio, int32_t* match12, int* n_matches);
+/* MatchBoW (LoopORBMatcher.cpp:121-215) for every keyframe pair of a batch in HBM: frames (desc, n), has_mp [batch][cap] and the
+ * feature vectors as snk_bow_transform_batch_dev leaves them.  match12_dev [batch][frames1->cap]; pairs_dev [batch][frames1->cap][2] =
+ * (feature of keyframe 1, feature of keyframe 2) ascending in the first, n_pairs_dev [batch]: the layout
+ * snk_sim3_ransac_pairs_batch_dev takes, with pairs_cap = frames1->cap.  Asynchronous on the matcher's stream. */
+SNK_API int snk_match_loop_bow_batch_dev(snk_matcher* m, const snk_frames_dev* frames1, const snk_frames_dev* frames2,
+                                         const uint8_t* has_mp1_dev, const uint8_t* has_mp2_dev, const uint32_t* node_id1_dev,
+                                         const int32_t* node_start1_dev, const int32_t* features1_dev, const int32_t* n_nodes1_dev,
+                                         const uint32_t* node_id2_dev, const int32_t* node_start2_dev, const int32_t* features2_dev,
+                                         const int32_t* n_nodes2_dev, int threshold, float ratio, int32_t* match12_dev,
+                                         int32_t* pairs_dev, int32_t* n_pairs_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU result gather (BASELINE config 5: one sequence per GPU)
  * ------------------------------------------------------------------------------------------
  * The path shards over independent units -- one Snake-SLAM process and one sequence per GPU -- and exchanges nothing while it

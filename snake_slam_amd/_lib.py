@@ -89,6 +89,21 @@ SIGNATURES = {
     "snk_pgo_cost": (i32, [vp, C.POINTER(f64)]),
     "snk_pgo_debug_linearisation": (i32, [vp, vp, vp, vp]),
     "snk_pgo_transform_points": (i32, [vp, i32, vp, vp, vp, vp]),
+    "snk_bow_vocab_create": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.POINTER(vp)]),
+    "snk_bow_vocab_destroy": (i32, [vp]),
+    "snk_bow_vocab_size": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "snk_bow_transform": (i32, [vp, vp, i32, i32, vp, vp, C.POINTER(i32), vp, vp, vp, C.POINTER(i32), vp, vp]),
+    "snk_bow_transform_batch_dev": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "snk_bow_score": (i32, [vp, vp, vp, i32, vp, vp, i32, C.POINTER(f64)]),
+    "snk_bow_db_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
+    "snk_bow_db_destroy": (i32, [vp]),
+    "snk_bow_db_add": (i32, [vp, i32, vp, vp, i32]),
+    "snk_bow_db_add_batch_dev": (i32, [vp, vp, i32, vp, vp, vp, i32]),
+    "snk_bow_db_remove": (i32, [vp, i32]),
+    "snk_bow_db_query": (i32, [vp, vp, vp, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, C.POINTER(i32)]),
+    "snk_bow_db_query_batch_dev": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp]),
+    "snk_match_loop_bow": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, C.POINTER(i32)]),
+    "snk_match_loop_bow_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp]),
     "snk_frontend_create": (i32, [vp, i32, C.POINTER(vp)]),
     "snk_frontend_destroy": (i32, [vp]),
     "snk_frontend_max_keypoints": (i32, [vp, i32, i32, C.POINTER(i32)]),

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -880,6 +881,168 @@ class RegistrationRansac
     uint64_t seed = 0;
     std::vector<char> inlierMask;
     int best_iteration = -1;  // the winning hypothesis of the last solve
+
+   private:
+    snk_matcher* h_ = nullptr;
+};
+
+// Bag-of-words place recognition (semantics "snk-bow v1") under the reference's names:
+//   ORBVocabulary vocabulary(arrays);  vocabulary.transform(descriptors, bow_vec, bow_feature_vec, 4);        // Snake/Map/Frame.cpp:38-40
+//   KeyframeDatabase db(vocabulary);  db.Add(id, bow_vec);  db.DetectLoopCandidates(bv, connected, minScore, max_candidates);
+//   LoopORBmatcher::MatchBoW(descriptors1, has_mp1, fv1, descriptors2, has_mp2, fv2, matches12, 50, 0.75);   // LoopDetector.cpp:225
+// BowVector / FeatureVector are the ordered maps of DBoW2; a keyframe is its id.
+using BowVector     = std::map<int32_t, double>;                // word -> value
+using FeatureVector = std::map<uint32_t, std::vector<int32_t>>; // node -> feature indices
+
+struct VocabularyArrays  // the flat tree of snk_bow_vocab_create (node 0 = root)
+{
+    std::vector<int32_t> child_start, child_count, children, word_id;
+    std::vector<DescriptorORB> desc;
+    std::vector<double> weight;
+};
+
+class ORBVocabulary
+{
+   public:
+    explicit ORBVocabulary(const VocabularyArrays& a, int device = 0)
+    {
+        const size_t n = a.child_start.size();
+        if (a.child_count.size() != n || a.word_id.size() != n || a.desc.size() != n || a.weight.size() != n)
+            throw std::invalid_argument("ORBVocabulary: per-node arrays differ in length");
+        check(snk_bow_vocab_create((int)n, a.child_start.data(), a.child_count.data(), a.children.data(), (int)a.children.size(),
+                                   reinterpret_cast<const uint64_t(*)[4]>(a.desc.data()), a.word_id.data(), a.weight.data(), device, nullptr, &h_),
+              "snk_bow_vocab_create");
+    }
+    ~ORBVocabulary() { snk_bow_vocab_destroy(h_); }
+    ORBVocabulary(const ORBVocabulary&)            = delete;
+    ORBVocabulary& operator=(const ORBVocabulary&) = delete;
+
+    // vocabulary.transform(descriptors, bow_vec, bow_feature_vec, levelsup) -- Frame.cpp:38-40 (the thread count has no counterpart)
+    void transform(const std::vector<DescriptorORB>& descriptors, BowVector& bow_vec, FeatureVector& bow_feature_vec, int levelsup) const
+    {
+        const size_t n = descriptors.size(), cap = n + 1;
+        std::vector<int32_t> words(cap), node_start(cap + 1), features(cap), wof(cap), nof(cap);
+        std::vector<uint32_t> node_id(cap);
+        std::vector<double> values(cap);
+        int nw = 0, nn = 0;
+        check(snk_bow_transform(h_, reinterpret_cast<const uint64_t(*)[4]>(descriptors.data()), (int)n, levelsup, words.data(), values.data(), &nw,
+                                node_id.data(), node_start.data(), features.data(), &nn, wof.data(), nof.data()),
+              "snk_bow_transform");
+        bow_vec.clear();
+        bow_feature_vec.clear();
+        for (int i = 0; i < nw; ++i) bow_vec.emplace_hint(bow_vec.end(), words[(size_t)i], values[(size_t)i]);
+        for (int i = 0; i < nn; ++i)
+            bow_feature_vec.emplace_hint(bow_feature_vec.end(), node_id[(size_t)i],
+                                         std::vector<int32_t>(features.begin() + node_start[(size_t)i], features.begin() + node_start[(size_t)i + 1]));
+    }
+    // vocabulary.score(a, b) -- LoopDetector.cpp:73
+    double score(const BowVector& a, const BowVector& b) const
+    {
+        std::vector<int32_t> wa, wb;
+        std::vector<double> va, vb;
+        flatten(a, wa, va);
+        flatten(b, wb, vb);
+        double s = 0.0;
+        check(snk_bow_score(h_, wa.data(), va.data(), (int)wa.size(), wb.data(), vb.data(), (int)wb.size(), &s), "snk_bow_score");
+        return s;
+    }
+    int size() const
+    {
+        int n = 0;
+        check(snk_bow_vocab_size(h_, &n, nullptr, nullptr), "snk_bow_vocab_size");
+        return n;
+    }
+    static void flatten(const BowVector& v, std::vector<int32_t>& words, std::vector<double>& values)
+    {
+        words.clear();
+        values.clear();
+        for (const auto& e : v)
+        {
+            words.push_back(e.first);
+            values.push_back(e.second);
+        }
+    }
+    snk_bow_vocab* handle() const { return h_; }
+
+   private:
+    snk_bow_vocab* h_ = nullptr;
+};
+
+// Snake::KeyframeDatabase -- Snake/LoopClosing/KeyframeDatabase.cpp:20-168
+class KeyframeDatabase
+{
+   public:
+    explicit KeyframeDatabase(ORBVocabulary& vocabulary, int maxKeyframes = 10000, int maxWords = SNK_BOW_MAX_FEATURES)
+    {
+        check(snk_bow_db_create(vocabulary.handle(), maxKeyframes, maxWords, &h_), "snk_bow_db_create");
+    }
+    ~KeyframeDatabase() { snk_bow_db_destroy(h_); }
+    KeyframeDatabase(const KeyframeDatabase&)            = delete;
+    KeyframeDatabase& operator=(const KeyframeDatabase&) = delete;
+
+    void Add(int kf_id, const BowVector& bv)
+    {
+        std::vector<int32_t> w;
+        std::vector<double> v;
+        ORBVocabulary::flatten(bv, w, v);
+        check(snk_bow_db_add(h_, kf_id, w.data(), v.data(), (int)w.size()), "snk_bow_db_add");
+    }
+    void Remove(int kf_id) { check(snk_bow_db_remove(h_, kf_id), "snk_bow_db_remove"); }
+    // :58-80: (keyframe id, score), best first
+    std::vector<std::pair<int, float>> DetectLoopCandidates(const BowVector& bv, const std::vector<int>& connected_keyframes, float minScore,
+                                                            int max_candidates)
+    {
+        return query(bv, connected_keyframes, minScore, max_candidates);
+    }
+    // :83-98: the reference passes 0 as the score floor whatever minScore is (:89)
+    std::vector<std::pair<int, float>> DetectRelocalizationCandidates(const BowVector& bv, float /*minScore*/, int max_candidates)
+    {
+        return query(bv, {}, 0.0f, max_candidates);
+    }
+
+   private:
+    std::vector<std::pair<int, float>> query(const BowVector& bv, const std::vector<int>& exclude, float min_score, int max_candidates)
+    {
+        std::vector<int32_t> w, ids((size_t)max_candidates + 1), ex(exclude.begin(), exclude.end());
+        std::vector<double> v, scores((size_t)max_candidates + 1);
+        ORBVocabulary::flatten(bv, w, v);
+        int n = 0;
+        check(snk_bow_db_query(h_, w.data(), v.data(), (int)w.size(), ex.data(), (int)ex.size(), 0.8f, 0.75f, min_score, max_candidates, ids.data(),
+                               scores.data(), nullptr, &n),
+              "snk_bow_db_query");
+        std::vector<std::pair<int, float>> out;
+        for (int i = 0; i < n; ++i) out.emplace_back(ids[(size_t)i], (float)scores[(size_t)i]);
+        return out;
+    }
+    snk_bow_db* h_ = nullptr;
+};
+
+// Snake::LoopORBmatcher -- Snake/LoopClosing/LoopORBMatcher.cpp:121-215
+class LoopORBmatcher
+{
+   public:
+    explicit LoopORBmatcher(int device = 0) { check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create"); }
+    ~LoopORBmatcher() { snk_matcher_destroy(h_); }
+    LoopORBmatcher(const LoopORBmatcher&)            = delete;
+    LoopORBmatcher& operator=(const LoopORBmatcher&) = delete;
+
+    // MatchBoW(pKF1, pKF2, vpMatches12, threshold, ratio): matches12[i] = the feature of keyframe 2 whose map point vpMatches12[i] holds, or -1
+    int MatchBoW(const std::vector<DescriptorORB>& descriptors1, const std::vector<uint8_t>& has_mp1, const FeatureVector& fv1,
+                 const std::vector<DescriptorORB>& descriptors2, const std::vector<uint8_t>& has_mp2, const FeatureVector& fv2,
+                 std::vector<int32_t>& matches12, int threshold, float ratio)
+    {
+        if (has_mp1.size() != descriptors1.size() || has_mp2.size() != descriptors2.size()) throw std::invalid_argument("MatchBoW: sizes");
+        const auto b1 = MappingORBMatcher::BowFeatureVector::from(fv1), b2 = MappingORBMatcher::BowFeatureVector::from(fv2);
+        const snk_bow_features f1 = b1.view(), f2 = b2.view();
+        std::vector<int32_t> m(descriptors1.size() + 1, -1);
+        int n = 0;
+        check(snk_match_loop_bow(h_, reinterpret_cast<const uint64_t(*)[4]>(descriptors1.data()), has_mp1.data(), (int)descriptors1.size(), &f1,
+                                 reinterpret_cast<const uint64_t(*)[4]>(descriptors2.data()), has_mp2.data(), (int)descriptors2.size(), &f2, threshold,
+                                 ratio, m.data(), &n),
+              "snk_match_loop_bow");
+        matches12.assign(m.begin(), m.begin() + (std::ptrdiff_t)descriptors1.size());
+        return n;
+    }
 
    private:
     snk_matcher* h_ = nullptr;
