@@ -231,7 +231,9 @@ enum
     SNK_ORB_DEBUG_CELL_CANDIDATES = 3, /* u32[64] per cell: score<<12 | (63-dy)<<6 | (63-dx), strongest first */
     SNK_ORB_DEBUG_SELECTED        = 4, /* u32 per slot: x | y<<16 (level pixels) */
     SNK_ORB_DEBUG_SELECTED_COUNT  = 5, /* int */
-    SNK_ORB_DEBUG_LEVEL_INFO      = 6  /* int[8]: w, h, pitch, ncols, nrows, wcell, hcell, nfeat */
+    SNK_ORB_DEBUG_LEVEL_INFO      = 6, /* int[8]: w, h, pitch, ncols, nrows, wcell, hcell, nfeat */
+    SNK_ORB_DEBUG_DIST_QUEUE      = 7  /* int[1 + n]: n, then image * 16 + level of every level the last batched call handed to the
+                                          full-budget launch of the distribution (image / level arguments ignored) */
 };
 SNK_API int snk_orb_debug_fetch(snk_orb* o, int what, int image, int level, void* out, size_t cap_bytes,
                                 size_t* n_bytes);

@@ -22,6 +22,7 @@
 //                      (v_dot4 against a disc table), polynomial atan2, 256 steered BRIEF tests read from an
 //                      LDS copy of the blurred patch, 4 ballots assemble the 256-bit descriptor
 #include "common.hpp"
+#include "orb_keys.hpp"
 
 #include <array>
 #include <vector>
@@ -1301,30 +1302,16 @@ __global__ __launch_bounds__(256, SNK_LEVEL_MIN_WAVES) void level_kernel(Layout 
 // ------------------------------------------------------------------------------------------------
 // quadtree distribution
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 point_key(int x, int y, int W, int H, int nroots)
+// Subdivision key of a candidate (8 + 32 bits).  The split rule lives in orb_keys.hpp: key_tab (snk_orb_configure) holds, per level, the x word
+// (with the root) of every column and the y word of every row, so a key is two table reads and a bit-interleave (about 20 vector
+// instructions; the loop form is up to 16 dependent steps of two midpoints, two compares and four selects, about 140).  key_tab:
+// [MAX_LEVELS] offsets, then keyx[W] | keyy[H] per level.  nullptr (SNK_ORB_DIST_KEY_LOOP=1, A/B): the loop form.
+// 0 <= x < W and 0 <= y < H: a candidate lies in a FAST cell, and the cells cover [EDGE_THRESHOLD, w - EDGE_THRESHOLD) x
+// [EDGE_THRESHOLD, h - EDGE_THRESHOLD) of the level, EDGE_THRESHOLD - MIN_BORDER = 3 pixels inside the tables' extent on every side.
+__device__ __forceinline__ u64 point_key(int x, int y, int W, int H, int nroots, const u32* __restrict__ keyx, const u32* __restrict__ keyy)
 {
-    // x, W < 2^16 and nroots <= 255: every product below stays under 2^24, 32-bit division suffices (the 64-bit one is
-    // ~5 times the instructions and this runs once per candidate)
-    const u32 ux = (u32)x, uw = (u32)W, un = (u32)nroots;
-    const int root = (int)((ux * un) / uw);
-    int x0 = (int)(((u32)root * uw + un - 1u) / un), x1 = (int)(((u32)(root + 1) * uw + un - 1u) / un);
-    int y0 = 0, y1 = H;
-    u64 key = (u64)root;
-    // A node's extent at least halves (rounded up) per level, so after nd = ceil(log2(max(W, H))) levels it is one pixel in both
-    // axes and every further digit is 0 (the midpoint of [x, x + 1) is x + 1): the loop stops there, the rest is a shift.
-    const int ext = max(max(W, H), 2);
-    const int nd  = min(KEY_DIGITS, 32 - __clz(ext - 1));
-    for (int d = 0; d < nd; ++d)
-    {
-        const int mx = x0 + (x1 - x0 + 1) / 2, my = y0 + (y1 - y0 + 1) / 2;
-        const int cx = x >= mx, cy = y >= my;
-        x0 = cx ? mx : x0;
-        x1 = cx ? x1 : mx;
-        y0 = cy ? my : y0;
-        y1 = cy ? y1 : my;
-        key = (key << 2) | (u64)(cx + 2 * cy);
-    }
-    return key << (2 * (KEY_DIGITS - nd));  // 8 + 32 bits
+    if (keyx) return orb_key_from_tables(keyx[x], keyy[y]);
+    return orb_point_key(x, y, W, H, nroots);
 }
 
 // Bitonic sort of n_pow2 keys in LDS (ascending), all threads of the block participate.  Every wavefront
@@ -1397,18 +1384,33 @@ __device__ void bitonic_sort(u64* a, int n_pow2, int tid, int nthreads)
     __syncthreads();
 }
 
-// block-wide inclusive scan of one int per thread (512 threads = 8 waves)
+// block-wide inclusive scan of one int per thread (512 threads = 8 waves), ONE workgroup barrier per call: the wavefront totals
+// alternate between two buffers (`par`, the same in every thread, flips per call), so a wavefront that runs ahead into the next
+// call writes the other buffer, and nobody writes this one again before the next call's barrier, which every reader of this call
+// has then passed.  `total` is the sum over the block, in every thread: callers keep running bases in registers.
 constexpr int DIST_THREADS = 512;
-__device__ int block_scan_incl(int v, int tid, int* wave_tot /* >= 8 */)
+struct ScanBuf
+{
+    int4 tot[2][2];  // [par][8 wavefronts]
+};
+__device__ __forceinline__ int block_scan_incl(int v, int tid, ScanBuf& sb, int& par, int& total)
 {
     const int lane = tid & 63, wave = tid >> 6;
     int x = v;
     x = wave_scan_incl_dpp(x);
-    if (lane == 63) wave_tot[wave] = x;
+    if (lane == 63) reinterpret_cast<int*>(sb.tot[par])[wave] = x;
     __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    __syncthreads();
+    const int4 a = sb.tot[par][0], b = sb.tot[par][1];
+    par ^= 1;
+    const int t[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    int base = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w)
+    {
+        base += w < wave ? t[w] : 0;
+        sum += t[w];
+    }
+    total = __builtin_amdgcn_readfirstlane(sum);  // the same in every lane: scalar, so are the callers' running bases
     return x + base;
 }
 
@@ -1420,7 +1422,7 @@ __device__ int block_scan_incl(int v, int tid, int* wave_tot /* >= 8 */)
 // members, and a key's final position is its bucket's start plus the number of smaller keys in the bucket (a handful; at most the
 // candidates of the few FAST cells a bucket's region overlaps).  Distinct keys: the result does not depend on the atomics' order.
 // tmp: cap * 4 bytes (the node list of the careful phase, free at this point): u16 idx[n] | int hist[nb + 1].
-__device__ void bucket_rank_sort(u64* keys, int n, int cap, int nroots, unsigned char* tmp, int tid, int* wave_tot)
+__device__ void bucket_rank_sort(u64* keys, int n, int cap, int nroots, unsigned char* tmp, int tid, ScanBuf& sb, int& par)
 {
     u16* idx  = reinterpret_cast<u16*>(tmp);
     int* hist = reinterpret_cast<int*>(tmp + 2 * cap);
@@ -1436,7 +1438,8 @@ __device__ void bucket_rank_sort(u64* keys, int n, int cap, int nroots, unsigned
     {
         // exclusive scan of the bucket counts, two buckets per thread
         const int b0 = 2 * tid, c0 = b0 < nb ? hist[b0] : 0, c1 = b0 + 1 < nb ? hist[b0 + 1] : 0;
-        const int incl = block_scan_incl(c0 + c1, tid, wave_tot);
+        int total;
+        const int incl = block_scan_incl(c0 + c1, tid, sb, par, total);
         if (b0 < nb) hist[b0] = incl - c0 - c1;
         if (b0 + 1 < nb) hist[b0 + 1] = incl - c1;
     }
@@ -1492,7 +1495,8 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
                                 unsigned long long* __restrict__ dbg_t = nullptr /* SNK_ORB_DIST_TIMING: [levels][16] cycle sums */,
                                 u32* cand_h = nullptr /* "orb.response" = 1: Harris rank per candidate slot (moves with its slot) */,
                                 u32* __restrict__ sel_resp = nullptr /* ... and the selected keypoints' ranks */,
-                                u32* __restrict__ h_global = nullptr /* ranks of this workgroup's candidates when the LDS carve has no room (full-budget launch) */)
+                                u32* __restrict__ h_global = nullptr /* ranks of this workgroup's candidates when the LDS carve has no room (full-budget launch) */,
+                                const u32* __restrict__ key_tab = nullptr /* subdivision-key tables (point_key); nullptr: the loop form */)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int cap     = lds_cap;      // LDS carve of this launch
@@ -1507,9 +1511,10 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
     // Harris ranks of the gathered candidates: behind the carve (the launch adds 4 * cap bytes) or in global scratch
     u32* hv       = cand_h ? (h_global ? h_global : reinterpret_cast<u32*>(smem + ((cap * 8 + cap / 2 * 8 + cap * 2 * 2 + cap + (cap + 16) + cap + 15) & ~15)))
                            : nullptr;
-    __shared__ int wave_tot[8];
+    __shared__ ScanBuf sb;
     __shared__ int hist_lcp[20], hist_m[20];
-    __shared__ int s_n, s_k, s_D, s_careful, s_size, s_nnodes, s_finish, s_jstar, s_out;
+    __shared__ int s_D, s_careful, s_size, s_nnodes, s_jstar;
+    int par = 0, total;  // block_scan_incl: buffer parity and the block total of the last scan (the same in every thread)
 
     const int tid = threadIdx.x;
     unsigned long long t_prev = dbg_t ? __builtin_readcyclecounter() : 0ull;
@@ -1531,22 +1536,19 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
     int* out_cnt    = sel_cnt + b * MAX_LEVELS + l;
 
     // ---- 1. per-cell budget k: largest k <= CELL_SLOTS with sum(min(cnt, k)) <= cap -------------
-    if (tid == 0) s_k = CELL_SLOTS;
-    __syncthreads();
+    // the count of this thread's first cell stays in a register, for every k and for the gather (a level of up to DIST_THREADS cells --
+    // every level of the EuRoC and KITTI shapes -- reads its counts from global memory once); k and n are the same in every thread
+    const int cnt0 = tid < ncell ? (int)cc[tid] : 0;
+    int kcell = CELL_SLOTS, n;
     for (;;)
     {
-        const int k = s_k;
-        int part    = 0;
-        for (int c = tid; c < ncell; c += DIST_THREADS) part += min((int)cc[c], k);
-        const int incl = block_scan_incl(part, tid, wave_tot);
-        if (tid == DIST_THREADS - 1) s_n = incl;
-        __syncthreads();
-        if (s_n <= sem_cap || k == 0) break;
-        if (tid == 0) s_k = k - 1;
-        __syncthreads();
+        int part = min(cnt0, kcell);
+        for (int c = tid + DIST_THREADS; c < ncell; c += DIST_THREADS) part += min((int)cc[c], kcell);
+        block_scan_incl(part, tid, sb, par, total);
+        n = total;
+        if (n <= sem_cap || kcell == 0) break;
+        --kcell;
     }
-    const int kcell = s_k;
-    const int n     = s_n;
     mark(0);
     if (n > cap) return false;
     // fast_kernel leaves the slots of a cell with <= CELL_SLOTS candidates in no particular order (cells with more hold their
@@ -1591,8 +1593,8 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
         for (int c0 = 0; c0 < ncell; c0 += DIST_THREADS)
         {
             const int c   = c0 + tid;
-            const int cnt = c < ncell ? min((int)cc[c], kcell) : 0;
-            const int incl = block_scan_incl(cnt, tid, wave_tot);
+            const int cnt = c0 == 0 ? min(cnt0, kcell) : (c < ncell ? min((int)cc[c], kcell) : 0);
+            const int incl = block_scan_incl(cnt, tid, sb, par, total);
             const int off  = base + incl - cnt;
             if (cnt > 0)
             {
@@ -1623,22 +1625,41 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
                     }
                 }
             }
-            if (tid == DIST_THREADS - 1) s_out = incl;
-            __syncthreads();
-            base += s_out;
-            __syncthreads();
+            base += total;
         }
+        __syncthreads();  // px, py, sc (and hv) of every candidate are in the LDS
     }
     mark(1);
     const int W = lv.w - 2 * MIN_BORDER, H = lv.h - 2 * MIN_BORDER;
-    for (int i = tid; i < n_pow2; i += DIST_THREADS)
-        keys[i] = i < n ? ((point_key(px[i] - MIN_BORDER, py[i] - MIN_BORDER, W, H, lv.nroots) << 13) | (u64)i) : ~0ull;
+    {
+        // four candidates per thread in flight: their table reads (L2 / vector cache hits) are independent.  Staging the tables in the
+        // node-list region of the carve, with the loads requested before the budget scan, measured neutral (profiles/NOTES.md)
+        const u32* keyx = key_tab ? key_tab + key_tab[l] : nullptr;
+        const u32* keyy = key_tab ? keyx + max(W, 0) : nullptr;
+        constexpr int KEY_ILP = 4;
+        for (int i0 = tid; i0 < n_pow2; i0 += KEY_ILP * DIST_THREADS)
+        {
+            u64 k[KEY_ILP];
+#pragma unroll
+            for (int u = 0; u < KEY_ILP; ++u)
+            {
+                const int i = i0 + u * DIST_THREADS;
+                k[u] = i < n ? ((point_key(px[i] - MIN_BORDER, py[i] - MIN_BORDER, W, H, lv.nroots, keyx, keyy) << 13) | (u64)i) : ~0ull;
+            }
+#pragma unroll
+            for (int u = 0; u < KEY_ILP; ++u)
+            {
+                const int i = i0 + u * DIST_THREADS;
+                if (i < n_pow2) keys[i] = k[u];
+            }
+        }
+    }
     __syncthreads();
 
     mark(2);
     // ---- 3. sort by subdivision key -------------------------------------------------------------
     if (n <= 4 * DIST_THREADS && cap >= 512)
-        bucket_rank_sort(keys, n, cap, lv.nroots, reinterpret_cast<unsigned char*>(nodes), tid, wave_tot);
+        bucket_rank_sort(keys, n, cap, lv.nroots, reinterpret_cast<unsigned char*>(nodes), tid, sb, par);
     else
         bitonic_sort(keys, n_pow2, tid, DIST_THREADS);  // the full-budget launch (levels with > 2048 candidates)
     mark(3);
@@ -1703,10 +1724,10 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
         s_D       = D;
         s_careful = careful;
         s_size    = size_D;
-        s_finish  = 0;
     }
     __syncthreads();
     const int D = s_D;
+    int size    = s_size;  // nodes so far: from here on kept in step by every thread (the block totals of the scans)
     for (int i = tid; i < n; i += DIST_THREADS) fd[i] = (u8)D;
     __syncthreads();
 
@@ -1723,7 +1744,7 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
         for (int dd = D; dd < KEY_DIGITS; ++dd)
         {
             for (int k = tid; k < HN; k += DIST_THREADS) hist[k] = 0;
-            if (tid == 0) s_jstar = HN;  // "the total never reaches N"
+            if (tid == 0) s_jstar = HN << 16;  // "the total never reaches N"
             if (dbg_t && tid == 0) atomicAdd(&dbg_t[l * 16 + 14], 1ull);  // rounds
             __syncthreads();
             int cntv[4], delv[4];
@@ -1770,8 +1791,8 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
                     loc[u]      = k < HN ? hist[HN - 1 - k] : 0;
                     sum += loc[u];
                 }
-                const int incl = block_scan_incl(sum, tid, wave_tot);
-                int run        = s_size + incl - sum;  // nodes before this thread's first class
+                const int incl = block_scan_incl(sum, tid, sb, par, total);
+                int run        = size + incl - sum;  // nodes before this thread's first class
                 int found      = -1;
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -1779,16 +1800,16 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
                     if (found < 0 && loc[u] > 0 && run + loc[u] >= N) { found = 4 * tid + u; before_mine = run; }
                     run += loc[u];
                 }
-                if (found >= 0) atomicMin(&s_jstar, found);
-                if (tid == DIST_THREADS - 1) s_out = run - s_size;  // new nodes if every node is split
+                // the class index and, below it, the running total above that class travel in one word: the minimum picks the first
+                // class, whose owner is one thread (found < HN < 2^11; run <= nodes + new nodes <= n + 3 n / 2 < 2^16 for n <= 2048)
+                if (found >= 0) atomicMin(&s_jstar, (found << 16) | before_mine);
             }
             __syncthreads();
             mark(10);
-            const int kstar = s_jstar;
-            if (kstar < HN && 4 * tid <= kstar && kstar < 4 * tid + 4) s_nnodes = before_mine;  // running total above class c*
-            __syncthreads();
+            const int jst    = s_jstar;
+            const int kstar  = jst >> 16;
             const int cstar  = kstar < HN ? HN - 1 - kstar + 2 : 0;  // 0: every node is split
-            const int before = kstar < HN ? s_nnodes : 0;
+            const int before = kstar < HN ? (jst & 0xFFFF) : 0;      // running total above class c*
             int my_add = 0;
             bool split[4];
 #pragma unroll
@@ -1802,7 +1823,7 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
                     d[u] = cntv[u] == cstar ? delv[u] : 0;
                     sum += d[u];
                 }
-                int run = before + block_scan_incl(sum, tid, wave_tot) - sum;
+                int run = before + block_scan_incl(sum, tid, sb, par, total) - sum;
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
                 {
@@ -1814,19 +1835,17 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
             for (int u = 0; u < 4; ++u)
                 if (split[u]) my_add += delv[u];
             mark(11);
-            const int add = block_scan_incl(my_add, tid, wave_tot);
-            if (tid == DIST_THREADS - 1)
-            {
-                s_finish = (s_size + add >= N || add == 0) ? 1 : 0;
-                s_size += add;
-            }
+            block_scan_incl(my_add, tid, sb, par, total);
+            const int add     = total;
+            const bool finish = size + add >= N || add == 0;
+            size += add;
 #pragma unroll
             for (int u = 0; u < 4; ++u)
                 if (split[u])
                     for (int e = 4 * tid + u, e1 = e + cntv[u]; e < e1; ++e) fd[e] = (u8)(dd + 1);
             __syncthreads();
             mark(12);
-            if (s_finish) break;
+            if (finish) break;
         }
     }
     else if (s_careful)
@@ -1867,32 +1886,28 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
             // running node count after splitting the first j+1 nodes; j* = first j reaching N
             if (tid == 0) s_jstar = m;  // "none"
             __syncthreads();
-            int base = s_size;
+            int base = size;
             for (int j0 = 0; j0 < m; j0 += DIST_THREADS)
             {
                 const int j     = j0 + tid;
                 const int delta = j < m ? (int)(nodes[j] & 0xFFFFu) : 0;
-                const int incl  = block_scan_incl(delta, tid, wave_tot);
+                const int incl  = block_scan_incl(delta, tid, sb, par, total);
                 if (j < m && base + incl >= N) atomicMin(&s_jstar, j);
-                if (tid == DIST_THREADS - 1) s_out = incl;
-                __syncthreads();
-                base += s_out;
-                __syncthreads();
+                base += total;
             }
+            __syncthreads();
             const int jstar = s_jstar;
             const int last  = jstar < m ? jstar : m - 1;  // nodes 0..last are split
             // size after this round
+            bool finish;
             {
                 // nodes created by this round's splits: block-wide sum (one thread walking the list paid an LDS round trip
                 // per node)
                 int part = 0;
                 for (int j = tid; j <= last; j += DIST_THREADS) part += (int)(nodes[j] & 0xFFFFu);
-                const int add = block_scan_incl(part, tid, wave_tot);
-                if (tid == DIST_THREADS - 1)
-                {
-                    s_finish = (s_size + add >= N || add == 0) ? 1 : 0;
-                    s_size += add;
-                }
+                block_scan_incl(part, tid, sb, par, total);
+                finish = size + total >= N || total == 0;
+                size += total;
             }
             for (int j = tid; j <= last; j += DIST_THREADS)
             {
@@ -1905,7 +1920,7 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
                 } while (e < n && (int)lcp[e] >= dd);
             }
             __syncthreads();
-            if (s_finish) break;
+            if (finish) break;
         }
     }
     __syncthreads();
@@ -1935,14 +1950,12 @@ __device__ bool distribute_body(const Layout& L, int b, int l, int lds_cap, u32*
         {
             const int i     = i0 + tid;
             const bool head = i < n && (int)lcp[i] < (int)fd[i];
-            const int incl  = block_scan_incl(head ? 1 : 0, tid, wave_tot);
+            const int incl  = block_scan_incl(head ? 1 : 0, tid, sb, par, total);
             const int pos   = base + incl - 1;
             if (i < n && pos < best_cap) atomicMax(&best[pos], (unsigned long long)keys[i]);
-            if (tid == DIST_THREADS - 1) s_out = incl;
-            __syncthreads();
-            base += s_out;
-            __syncthreads();
+            base += total;
         }
+        __syncthreads();  // every winner is in
         const int count = base < lv.slot_cap ? base : lv.slot_cap;
         for (int k = tid; k < count; k += DIST_THREADS)
         {
@@ -1964,10 +1977,11 @@ __global__ __launch_bounds__(DIST_THREADS, SNK_DIST_MIN_WAVES) void distribute_k
                                                                   u8* __restrict__ sel_score, int* __restrict__ sel_cnt,
                                                                   int* __restrict__ cand_total, int* __restrict__ queue,
                                                                   unsigned long long* __restrict__ dbg_t, u32* cand_h,
-                                                                  u32* __restrict__ sel_resp)
+                                                                  u32* __restrict__ sel_resp, const u32* __restrict__ key_tab)
 {
     const int l = blockIdx.x, b = blockIdx.y;
-    if (!distribute_body(L, b, l, lds_cap, cand, cell_cnt, sel, sel_score, sel_cnt, cand_total, dbg_t, cand_h, sel_resp) && threadIdx.x == 0)
+    if (!distribute_body(L, b, l, lds_cap, cand, cell_cnt, sel, sel_score, sel_cnt, cand_total, dbg_t, cand_h, sel_resp, nullptr, key_tab) &&
+        threadIdx.x == 0)
         queue[1 + atomicAdd(&queue[0], 1)] = b * MAX_LEVELS + l;
 }
 
@@ -1977,14 +1991,15 @@ __global__ __launch_bounds__(DIST_THREADS) void distribute_large_kernel(Layout L
                                                                         u32* __restrict__ sel, u8* __restrict__ sel_score,
                                                                         int* __restrict__ sel_cnt, int* __restrict__ cand_total,
                                                                         const int* __restrict__ queue, u32* cand_h,
-                                                                        u32* __restrict__ sel_resp, u32* __restrict__ h_scratch)
+                                                                        u32* __restrict__ sel_resp, u32* __restrict__ h_scratch,
+                                                                        const u32* __restrict__ key_tab)
 {
     const int count = queue[0];
     for (int i = blockIdx.x; i < count; i += gridDim.x)
     {
         const int item = queue[1 + i];
         distribute_body(L, item / MAX_LEVELS, item % MAX_LEVELS, L.level_cap, cand, cell_cnt, sel, sel_score, sel_cnt, cand_total, nullptr,
-                        cand_h, sel_resp, cand_h ? h_scratch + (size_t)blockIdx.x * L.level_cap : nullptr);
+                        cand_h, sel_resp, cand_h ? h_scratch + (size_t)blockIdx.x * L.level_cap : nullptr, key_tab);
         __syncthreads();
     }
 }
@@ -2521,6 +2536,7 @@ struct snk_orb : HandleBase
     DevBuf blur[MAX_LEVELS];  // blurred levels (all)
     DevBuf tables;           // resize tables
     DevBuf cell_tab;         // FAST cell geometry
+    DevBuf key_tab;          // subdivision-key tables of the distribution (orb_keys.hpp): [MAX_LEVELS] offsets, keyx | keyy per level
     DevBuf img0;             // level-0 staging for the host API
     DevBuf cand, cell_cnt, sel, sel_score, sel_cnt, cand_total, dist_queue;
     DevBuf cand_h, sel_resp, dist_h;  // "orb.response" = 1 only (reserved by the first call that runs under it)
@@ -2594,9 +2610,8 @@ static int compute_layout(snk_orb* o, int w, int h)
         }
         lv.cell_off = cell_off;
         cell_off += lv.ncols * lv.nrows;
-        int nroots = height > 0 ? (2 * width + height) / (2 * height) : 1;
-        nroots     = nroots < 1 ? 1 : (nroots > 255 ? 255 : nroots);
-        lv.nroots  = nroots;
+        const int nroots = orb_key_nroots(width, height);  // orb_keys.hpp: the root count the key tables are filled with
+        lv.nroots        = nroots;
         lv.slot_off = slot_off;
         lv.slot_cap = lv.nfeat + 3 > 4 * nroots ? lv.nfeat + 3 : 4 * nroots;
         slot_off += lv.slot_cap;
@@ -2768,6 +2783,7 @@ int snk_orb_destroy(snk_orb* o)
     o->cand.release();
     o->cell_cnt.release();
     o->cell_tab.release();
+    o->key_tab.release();
     o->sel.release();
     o->sel_score.release();
     o->sel_cnt.release();
@@ -2888,6 +2904,22 @@ int snk_orb_configure(snk_orb* o, int width, int height, int max_batch)
         if ((rc = o->cell_tab.reserve(ct.size() * sizeof(int4))) != SNK_OK) return rc;
         if ((rc = copy_sync(o->cell_tab.p, ct.data(), ct.size() * sizeof(int4), hipMemcpyHostToDevice, o->stream)) != SNK_OK) return rc;
         L.cell_tab = o->cell_tab.as<int4>();
+    }
+    {
+        // subdivision keys: the x word (with the root) of every column and the y word of every row of a level's bordered extent; they
+        // depend on the level sizes alone, which this call fixes
+        std::vector<u32> kt(MAX_LEVELS, 0u);
+        for (int l = 0; l < L.n_levels; ++l)
+        {
+            const LevelInfo& lv = L.lv[l];
+            const int W = std::max(lv.w - 2 * MIN_BORDER, 0), H = std::max(lv.h - 2 * MIN_BORDER, 0);
+            kt[l] = (u32)kt.size();
+            if (W == 0 || H == 0) continue;  // no candidates: the tables are never read (and keyy is addressed as keyx + W)
+            for (int x = 0; x < W; ++x) kt.push_back(orb_keyx_entry(x, W, H, lv.nroots));
+            for (int y = 0; y < H; ++y) kt.push_back(orb_keyy_entry(y, W, H));
+        }
+        if ((rc = o->key_tab.reserve(kt.size() * sizeof(u32))) != SNK_OK) return rc;
+        if ((rc = copy_sync(o->key_tab.p, kt.data(), kt.size() * sizeof(u32), hipMemcpyHostToDevice, o->stream)) != SNK_OK) return rc;
     }
     const size_t cells = (size_t)(L.total_cells > 0 ? L.total_cells : 1) * max_batch;
     const size_t slots = (size_t)(L.total_slots > 0 ? L.total_slots : 1) * max_batch;
@@ -3086,6 +3118,8 @@ static int run_part(snk_orb* o, hipStream_t st, int part, int b0, const u8* imag
     if (stages != 3 || L.total_cells <= 0) SNK_HIP_CHECK(hipMemsetAsync(d_queue, 0, sizeof(int), st));
     // SNK_ORB_DIST_TIMING=1 (diagnostic): cycle sums per phase and level, printed after a synchronisation
     static const bool dist_timing = getenv("SNK_ORB_DIST_TIMING") != nullptr;
+    static const bool key_loop    = getenv("SNK_ORB_DIST_KEY_LOOP") != nullptr;  // A/B: subdivision keys by the loop form, not from the tables
+    const u32* d_keytab           = key_loop ? nullptr : o->key_tab.as<u32>();
     unsigned long long* d_dbg = nullptr;
     if (dist_timing)
     {
@@ -3116,7 +3150,7 @@ static int run_part(snk_orb* o, hipStream_t st, int part, int b0, const u8* imag
     hipLaunchKernelGGL(distribute_kernel, dim3(L.n_levels, batch), dim3(DIST_THREADS),
                        one_dist_launch ? o->dist_lds : o->dist_lds_small + (harris ? 4 * (size_t)o->dist_small_cap + 16 : 0), st, L,
                        one_dist_launch ? L.level_cap : o->dist_small_cap, d_cand, d_cellcnt, d_sel, d_selscore,
-                       d_selcnt, d_candtot, d_queue, d_dbg, d_candh, d_selresp);
+                       d_selcnt, d_candtot, d_queue, d_dbg, d_candh, d_selresp, d_keytab);
     SNK_LAUNCH_CHECK();
     if (dist_timing)
     {
@@ -3136,7 +3170,7 @@ static int run_part(snk_orb* o, hipStream_t st, int part, int b0, const u8* imag
     {
         hipLaunchKernelGGL(distribute_large_kernel, dim3(large_workers), dim3(DIST_THREADS), o->dist_lds, st, L,
                            d_cand, d_cellcnt, d_sel, d_selscore,
-                           d_selcnt, d_candtot, d_queue, d_candh, d_selresp, d_disth);
+                           d_selcnt, d_candtot, d_queue, d_candh, d_selresp, d_disth, d_keytab);
         SNK_LAUNCH_CHECK();
     }
     if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[4], st));
@@ -3391,6 +3425,10 @@ int snk_orb_debug_fetch(snk_orb* o, int what, int image, int level, void* out, s
         case SNK_ORB_DEBUG_SELECTED_COUNT:
             src   = o->sel_cnt.as<int>() + image * MAX_LEVELS + level;
             bytes = sizeof(int);
+            break;
+        case SNK_ORB_DEBUG_DIST_QUEUE:  // of the plain call (chain slot 0); the counter is reset by the next call
+            src   = o->dist_queue.as<int>();
+            bytes = ((size_t)o->max_batch * MAX_LEVELS + 1) * sizeof(int);
             break;
         case SNK_ORB_DEBUG_LEVEL_INFO:
         {

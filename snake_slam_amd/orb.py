@@ -18,6 +18,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
                            ("octave", "<i4")])
 
 DEBUG_PYRAMID, DEBUG_CELL_COUNTS, DEBUG_CELL_CANDIDATES, DEBUG_SELECTED, DEBUG_SELECTED_COUNT, DEBUG_LEVEL_INFO = range(1, 7)
+DEBUG_DIST_QUEUE = 7  # int[1 + n]: the (image * 16 + level) entries the last batched call queued for distribute_large_kernel
 
 
 class OrbParams(C.Structure):
