@@ -9,6 +9,7 @@
 // unsigned min, and reproduces the sequential scan's "strict <, first index wins" tie-break
 // exactly (the two lexicographically smallest (dist, idx) pairs).
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace snk
 {
@@ -318,7 +319,7 @@ __device__ __forceinline__ int iround_d(double x, int mode)
 
 constexpr u64 ST_INF_KEY = (250ull << 40) | 0xFFFFFFFFFFull;
 constexpr int ST_ROW_BIAS    = 4096;  // rounded rows are clamped to [-4096, 61439] for the index only
-constexpr int ST_SORT_MAX    = 8192;  // right keypoints per image the in-LDS sort handles
+// ST_SORT_MAX, the right keypoints per image the in-LDS sort handles: dispatch.hpp
 
 // row-sorted index of the right keypoints of every image: (clamped rounded row + bias) << 16 | index
 __device__ __forceinline__ void stereo_sort_network(const snk_kp64* __restrict__ rb, int nr, int iround_mode, u32* keys, u32* __restrict__ out)
@@ -370,8 +371,7 @@ __global__ __launch_bounds__(256) void stereo_sort_kernel(const snk_kp64* __rest
 // The same index by counting: the rows of a frame's right keypoints span the image height, so a histogram over [min row, max row]
 // (LDS atomics), its scan and a rank inside each row's members replace the 55 compare-exchange stages of the network (18.6 -> ~5 us for
 // the one frame of a per-frame call).  Identical output: keys ascending = (row, then index).  A frame whose rows span more than
-// ST_COUNT_ROWS (rectification pushed keypoints far outside the image) runs the network inside the same launch.
-constexpr int ST_COUNT_ROWS = 4096;
+// ST_COUNT_ROWS (dispatch.hpp; rectification pushed keypoints far outside the image) runs the network inside the same launch.
 // n_matches / prefill_rp / prefill_dp (may be NULL): the frame's match counter is reset here and -- for the one-call front-end --
 // right_points / depth get Frame::allocateTmp's -1000 (Snake/Map/Frame.cpp:25-26) here, instead of one fill launch each in front of
 // a chain of a dozen short launches (a fill is a 4.5 us kernel of its own: profiles/r05/r05e_pipeline_trace_after.txt).
@@ -693,8 +693,7 @@ __global__ __launch_bounds__(256) void stereo_kernel16(const snk_kp64* __restric
 // ST_ROWS - 1, so a band is start[bucket(lo)] .. start[bucket(hi) + 1] without a search; the order inside a bucket is
 // whatever the atomics gave -- the result is the minimum of (distance, row, index) keys and every gate is evaluated
 // on the true values, so neither that order nor the clamping can change it.
-// Replaces stereo_sort_kernel + stereo_kernel16 when the right side fits (nr_cap <= ST_FRAME_MAX).
-constexpr int ST_FRAME_MAX = 2560;
+// Replaces stereo_sort_kernel + stereo_kernel16 when the right side fits (nr_cap <= ST_FRAME_MAX, dispatch.hpp).
 constexpr int ST_ROWS      = 2048;
 __host__ __device__ inline size_t stereo_frame_lds(int nr_cap) { return (size_t)nr_cap * 56 + (size_t)(ST_ROWS + 2) * 4 + 16; }
 
@@ -915,26 +914,25 @@ static int launch_knn2(snk_matcher* m, const uint64_t* q, const int32_t* nq_dev,
                        const uint64_t* t, const int32_t* nt_dev, int nt_cap, int nt_host, int batch, snk_knn2* out)
 {
     if (batch <= 0 || nq_cap <= 0) return SNK_OK;
-    // Matrix-core path once a query block (32) and a train tile (32) are mostly full; the vector kernel below for
-    // small sets (SNK_BF_NO_MFMA=1 forces it, for A/B measurements).
+    // The form by the launch shape (dispatch.hpp): the matrix-core kernel once a query block (32) and a train tile (32) are mostly
+    // full; the vector kernel for small sets (SNK_BF_NO_MFMA=1 forces it, for A/B measurements), with 4 queries per wavefront once
+    // there is enough work to fill 256 CUs, else 1 (latency).
     static const bool no_mfma = getenv("SNK_BF_NO_MFMA") != nullptr;
-    if (!no_mfma && nq_cap >= 24 && nt_cap >= 24)
+    switch (knn2_form(nq_cap, nt_cap, batch, no_mfma))
     {
+    case Knn2Form::mfma:
         hipLaunchKernelGGL(bf_knn2_mfma_kernel, dim3(ceil_div(nq_cap, 128), batch), dim3(256), 0, m->stream, (const uint4*)q, nq_dev,
                            nq_cap, nq_host, (const uint4*)t, nt_dev, nt_cap, nt_host, out);
-        SNK_LAUNCH_CHECK();
-        return SNK_OK;
+        break;
+    case Knn2Form::vector4:
+        hipLaunchKernelGGL(bf_knn2_kernel<4>, dim3(ceil_div(nq_cap, 16), batch), dim3(256), 0, m->stream, (const uint4*)q, nq_dev, nq_cap,
+                           nq_host, (const uint4*)t, nt_dev, nt_cap, nt_host, out);
+        break;
+    case Knn2Form::vector1:
+        hipLaunchKernelGGL(bf_knn2_kernel<1>, dim3(ceil_div(nq_cap, 4), batch), dim3(256), 0, m->stream, (const uint4*)q, nq_dev, nq_cap,
+                           nq_host, (const uint4*)t, nt_dev, nt_cap, nt_host, out);
+        break;
     }
-    // 4 queries per wavefront once there is enough work to fill 256 CUs, else 1 (latency).
-    const bool wide = (long long)batch * nq_cap >= 16384;
-    const int qw    = wide ? 4 : 1;
-    dim3 grid(ceil_div(nq_cap, 4 * qw), batch);
-    if (wide)
-        hipLaunchKernelGGL(bf_knn2_kernel<4>, grid, dim3(256), 0, m->stream, (const uint4*)q, nq_dev, nq_cap, nq_host,
-                           (const uint4*)t, nt_dev, nt_cap, nt_host, out);
-    else
-        hipLaunchKernelGGL(bf_knn2_kernel<1>, grid, dim3(256), 0, m->stream, (const uint4*)q, nq_dev, nq_cap, nq_host,
-                           (const uint4*)t, nt_dev, nt_cap, nt_host, out);
     SNK_LAUNCH_CHECK();
     return SNK_OK;
 }
@@ -1074,15 +1072,16 @@ int snk_stereo_match(snk_matcher* m, const snk_kp64* left, const uint64_t (*desc
     memset(hb + o_cnt, 0, 4);
     SNK_HIP_CHECK(hipMemcpyAsync(ab, hb, in_b, hipMemcpyHostToDevice, m->stream));
     const u32* srt = nullptr;
-    if (nr <= ST_SORT_MAX)
+    static const bool sort_network = getenv("SNK_STEREO_SORT_NETWORK") != nullptr;  // A/B, tests: the bitonic network
+    const StereoForm form = stereo_host_form(nr, sort_network);
+    if (form != StereoForm::unindexed)
     {
         if ((rc = m->out.reserve((size_t)nr * 4)) != SNK_OK) return rc;
         int np2 = 2;
         while (np2 < nr) np2 <<= 1;
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_sort_kernel), ST_SORT_MAX * 4)) != SNK_OK) return rc;
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_kernel16), ST_SORT_MAX * 4)) != SNK_OK) return rc;
-        static const bool sort_network = getenv("SNK_STEREO_SORT_NETWORK") != nullptr;  // A/B, tests: the bitonic network
-        if (!sort_network)
+        if (form == StereoForm::count16)
         {
             const int nrc    = nr > 0 ? nr : 1;
             const size_t lds = std::max(((size_t)2 * (ST_COUNT_ROWS + 1) + (size_t)2 * nrc) * 4, (size_t)np2 * 4);
@@ -1144,10 +1143,9 @@ int snk::stereo_match_batch_dev_impl(snk_matcher* m, const snk_kp64* left_dev, c
     const u32* srt = nullptr;
     static const bool no_frame_kernel = getenv("SNK_STEREO_NO_FRAME_KERNEL") != nullptr;  // A/B measurements
     static const bool sort_network    = getenv("SNK_STEREO_SORT_NETWORK") != nullptr;     // A/B, tests: the bitonic network
-    const bool frame_kernel = !no_frame_kernel && nr_cap <= ST_FRAME_MAX && batch >= 8;
+    const StereoForm form = stereo_batch_form(nr_cap, batch, no_frame_kernel, sort_network);
     // the counting kernel of the small-batch path resets the counter and does the prefill itself; every other path pays the fills
-    const bool count_path = !frame_kernel && nr_cap <= ST_SORT_MAX && !sort_network;
-    if (!count_path)
+    if (form != StereoForm::count16)
     {
         SNK_HIP_CHECK(hipMemsetAsync(n_matches_dev, 0, (size_t)batch * sizeof(int), m->stream));
         if (prefill)
@@ -1156,7 +1154,7 @@ int snk::stereo_match_batch_dev_impl(snk_matcher* m, const snk_kp64* left_dev, c
             SNK_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(depth_dev), 0xC47A0000u, (size_t)batch * nl_cap, m->stream));
         }
     }
-    if (frame_kernel)
+    if (form == StereoForm::frame)
     {
         // enough frames to give every CU its own: one workgroup per frame, the right side resident in LDS
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_frame_kernel), (int)stereo_frame_lds(ST_FRAME_MAX))) != SNK_OK) return rc;
@@ -1166,14 +1164,14 @@ int snk::stereo_match_batch_dev_impl(snk_matcher* m, const snk_kp64* left_dev, c
         SNK_LAUNCH_CHECK();
         return SNK_OK;
     }
-    if (nr_cap <= ST_SORT_MAX)
+    if (form != StereoForm::unindexed)
     {
         if ((rc = m->out.reserve((size_t)batch * nr_cap * 4)) != SNK_OK) return rc;
         int np2 = 2;
         while (np2 < nr_cap) np2 <<= 1;
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_sort_kernel), ST_SORT_MAX * 4)) != SNK_OK) return rc;
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_kernel16), ST_SORT_MAX * 4)) != SNK_OK) return rc;
-        if (!sort_network)
+        if (form == StereoForm::count16)
         {
             const size_t lds = std::max(((size_t)2 * (ST_COUNT_ROWS + 1) + (size_t)2 * nr_cap) * 4, (size_t)np2 * 4);
             if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_count_kernel), (2 * (ST_COUNT_ROWS + 1) + 2 * ST_SORT_MAX) * 4)) != SNK_OK)

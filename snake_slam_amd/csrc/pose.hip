@@ -9,6 +9,7 @@
 // (deterministic), and one wavefront solves the 6x6 system.  Problems of a batch run side by side.
 #include <cmath>
 
+#include "dispatch.hpp"
 #include "matcher_handle.hpp"
 
 // Floating-point contraction of this file (round 6): pose refinement is specified by a tolerance and its kernel is bound by fp64 issue
@@ -277,10 +278,8 @@ __device__ int chol_solve6(const double* A, const double* b, double* x)
 #ifndef SNK_POSE_MIN_WAVES
 #define SNK_POSE_MIN_WAVES 2  // two wavefronts per SIMD (<= 256 registers incl. accumulation registers): without the bound the allocator has gone to 254 + 6 = one wavefront
 #endif
-#ifndef SNK_POSE_RED_STEPS  // DPP steps of the 27 sums before they meet in LDS: 4 = rows of 16 lanes, 2 = quads (see the kernel)
-#define SNK_POSE_RED_STEPS 2
-#endif
-constexpr int POSE_SLOTS_PER_WAVE = 64 >> SNK_POSE_RED_STEPS;
+// SNK_POSE_RED_STEPS (DPP steps of the 27 sums before they meet in LDS: 4 = rows of 16 lanes, 2 = quads, see the kernel) and
+// POSE_SLOTS_PER_WAVE = 64 >> SNK_POSE_RED_STEPS: dispatch.hpp
 template <int WAVES, bool LDSM>
 __global__ __launch_bounds__(64 * WAVES, SNK_POSE_MIN_WAVES) void pose_kernel(const PoseMeta* __restrict__ meta, const double* __restrict__ wps,
                                                           const snk_pose_obs* __restrict__ obs, u8* __restrict__ outlier,
@@ -838,35 +837,36 @@ extern "C" int snk_pose_refine(snk_matcher* m, const snk_camera* cam, const snk_
     char* o = m->out.as<char>();
     SNK_HIP_CHECK(hipMemcpyAsync(d, stage, in_b, hipMemcpyHostToDevice, m->stream));
     CamD C{cam->fx, cam->fy, cam->cx, cam->cy, cam->bf};
-    if (total >= (size_t)n_problems * 192)  // ~200 matches per frame and more: four wavefronts per frame
+    // the form by the call's shape (dispatch.hpp): ~200 matches per frame and more: four wavefronts per frame, with the matches of a
+    // problem in LDS for its 40 steps (as in the device-resident form): one problem per call is a chain of latencies, and a
+    // global-memory round trip per match and step was most of it
+    // (eight wavefronts per problem for calls with one or a few large problems -- the reference's call is ONE frame of ~900 matches,
+    // a chain of latencies on an empty chip -- measured nothing: 0.229 vs 0.224 ms per call, round 4; a step is bound by its serial
+    // part: reduction, 6 x 6 solve, pose hand-over)
+    static const bool no_lds = getenv("SNK_POSE_NO_LDS") != nullptr;
+    switch (pose_host_form(total, n_problems, no_lds))
     {
-        // the matches of a problem in LDS for its 40 steps (as in the device-resident form): one problem per call is a chain of
-        // latencies, and a global-memory round trip per match and step was most of it
-        static const bool no_lds = getenv("SNK_POSE_NO_LDS") != nullptr;
-        const int dyn_max = 160 * 1024 - (4 * POSE_SLOTS_PER_WAVE * 28 + 28) * 8 - 2048;
-        int lds_matches   = n_max;
-        if (n_problems > 256) lds_matches = std::min(lds_matches, (80 * 1024 - (4 * POSE_SLOTS_PER_WAVE * 28 + 28) * 8 - 256) / 56);  // two problems per CU
-        if ((size_t)lds_matches * 56 > (size_t)dyn_max) lds_matches = dyn_max / 56;
-        // (eight wavefronts per problem for calls with one or a few large problems -- the reference's call is ONE frame of ~900 matches,
-        // a chain of latencies on an empty chip -- measured nothing: 0.229 vs 0.224 ms per call, round 4; a step is bound by its serial
-        // part: reduction, 6 x 6 solve, pose hand-over)
-        if (!no_lds)
-        {
-            if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pose_kernel<4, true>), dyn_max)) != SNK_OK) return rc;
-            hipLaunchKernelGGL((pose_kernel<4, true>), dim3(n_problems), dim3(256), (size_t)lds_matches * 56, m->stream,
-                               reinterpret_cast<const PoseMeta*>(d), reinterpret_cast<const double*>(d + o_wps),
-                               reinterpret_cast<const snk_pose_obs*>(d + o_obs), reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose),
-                               reinterpret_cast<int*>(o + o_inl), C, *opt, lds_matches);
-        }
-        else
-            hipLaunchKernelGGL((pose_kernel<4, false>), dim3(n_problems), dim3(256), 0, m->stream, reinterpret_cast<const PoseMeta*>(d),
-                               reinterpret_cast<const double*>(d + o_wps), reinterpret_cast<const snk_pose_obs*>(d + o_obs),
-                               reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose), reinterpret_cast<int*>(o + o_inl), C, *opt, 0);
+    case PoseForm::wave4_lds:
+    {
+        const int lds_matches = pose_host_carve(n_max, n_problems);
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pose_kernel<4, true>), pose_dyn_max())) != SNK_OK) return rc;
+        hipLaunchKernelGGL((pose_kernel<4, true>), dim3(n_problems), dim3(256), (size_t)lds_matches * POSE_MATCH_BYTES, m->stream,
+                           reinterpret_cast<const PoseMeta*>(d), reinterpret_cast<const double*>(d + o_wps),
+                           reinterpret_cast<const snk_pose_obs*>(d + o_obs), reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose),
+                           reinterpret_cast<int*>(o + o_inl), C, *opt, lds_matches);
+        break;
     }
-    else
+    case PoseForm::wave4_global:
+        hipLaunchKernelGGL((pose_kernel<4, false>), dim3(n_problems), dim3(256), 0, m->stream, reinterpret_cast<const PoseMeta*>(d),
+                           reinterpret_cast<const double*>(d + o_wps), reinterpret_cast<const snk_pose_obs*>(d + o_obs),
+                           reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose), reinterpret_cast<int*>(o + o_inl), C, *opt, 0);
+        break;
+    default:  // wave1 (the host entry has no two-wavefront form)
         hipLaunchKernelGGL((pose_kernel<1, false>), dim3(n_problems), dim3(64), 0, m->stream, reinterpret_cast<const PoseMeta*>(d),
                            reinterpret_cast<const double*>(d + o_wps), reinterpret_cast<const snk_pose_obs*>(d + o_obs),
                            reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose), reinterpret_cast<int*>(o + o_inl), C, *opt, 0);
+        break;
+    }
     SNK_LAUNCH_CHECK();
     char* back = m->h_res.as<char>();
     SNK_HIP_CHECK(hipMemcpyAsync(back, o, out_b, hipMemcpyDeviceToHost, m->stream));
@@ -930,16 +930,6 @@ static int refine_batch_impl(snk_matcher* m, const snk_frames_dev* frames, const
     // wavefronts per SIMD; until round 4 the carve was sized for four frames, 656 matches, and a frame with the usual ~770 read
     // the rest from global memory in every step).  SNK_POSE_LDS_MATCHES overrides; tests force the global-memory tail with a small value.
     static const int lds_env = getenv("SNK_POSE_LDS_MATCHES") ? atoi(getenv("SNK_POSE_LDS_MATCHES")) : 0;
-    int lds_matches = stride;
-    if (lds_env > 0) lds_matches = lds_env < stride ? lds_env : stride;
-    else
-    {
-        const int two_per_cu = (80 * 1024 - (4 * POSE_SLOTS_PER_WAVE * 28 + 28) * 8 - 256) / 56;  // carve + static LDS <= 80 KB
-        if (batch > 256 && lds_matches > two_per_cu) lds_matches = two_per_cu;
-    }
-    const int dyn_max = 160 * 1024 - (4 * POSE_SLOTS_PER_WAVE * 28 + 28) * 8 - 2048;  // what a workgroup can have beside the static part
-    if ((size_t)lds_matches * 56 > (size_t)dyn_max) lds_matches = dyn_max / 56;
-    const size_t match_lds = (size_t)lds_matches * 7 * sizeof(double);
 #define POSE_LAUNCH(W_, L_, LDS_)                                                                                                    \
     hipLaunchKernelGGL((pose_kernel<W_, L_>), dim3(batch), dim3(64 * W_), LDS_, m->stream, reinterpret_cast<const PoseMeta*>(d),  \
                        reinterpret_cast<const double*>(d + o_wps), reinterpret_cast<const snk_pose_obs*>(d + o_obs),                \
@@ -957,25 +947,22 @@ static int refine_batch_impl(snk_matcher* m, const snk_frames_dev* frames, const
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
         return v > 0 ? v : 256;
     }();
-    const bool two_waves = waves_env == 2 || (waves_env != 4 && batch > 2 * n_cu);
-    if (stride >= 256 && !no_lds && two_waves)
+    const PoseForm form   = pose_batch_form(stride, batch, n_cu, waves_env, no_lds);
+    const int lds_matches = pose_batch_carve(stride, batch, lds_env, form == PoseForm::wave2_lds);  // dispatch.hpp
+    const size_t match_lds = (size_t)lds_matches * POSE_MATCH_BYTES;
+    if (form == PoseForm::wave2_lds || form == PoseForm::wave4_lds)
     {
-        int rc = set_max_lds_once(reinterpret_cast<const void*>(pose_kernel<2, true>), dyn_max);
+        const void* fn = form == PoseForm::wave2_lds ? reinterpret_cast<const void*>(pose_kernel<2, true>) : reinterpret_cast<const void*>(pose_kernel<4, true>);
+        int rc = set_max_lds_once(fn, pose_dyn_max());
         if (rc != SNK_OK) return rc;
-        int lm = (160 * 1024 / 4 - (2 * POSE_SLOTS_PER_WAVE * 28 + 28) * 8 - 512) / 56;  // four frames per CU
-        if (lds_env > 0) lm = lds_env;
-        lds_matches = lm < stride ? lm : stride;
-        if ((size_t)lds_matches * 56 > (size_t)dyn_max) lds_matches = dyn_max / 56;
-        POSE_LAUNCH(2, true, (size_t)lds_matches * 56);
     }
-    else if (stride >= 256 && !no_lds)
+    switch (form)
     {
-        int rc = set_max_lds_once(reinterpret_cast<const void*>(pose_kernel<4, true>), dyn_max);
-        if (rc != SNK_OK) return rc;
-        POSE_LAUNCH(4, true, match_lds);
+    case PoseForm::wave2_lds: POSE_LAUNCH(2, true, match_lds); break;
+    case PoseForm::wave4_lds: POSE_LAUNCH(4, true, match_lds); break;
+    case PoseForm::wave4_global: POSE_LAUNCH(4, false, 0); break;
+    case PoseForm::wave1: POSE_LAUNCH(1, false, 0); break;
     }
-    else if (stride >= 256) POSE_LAUNCH(4, false, 0);
-    else POSE_LAUNCH(1, false, 0);
 #undef POSE_LAUNCH
     hipLaunchKernelGGL(scatter_pose_kernel, dim3(batch), dim3(64), 0, m->stream, reinterpret_cast<const PoseMeta*>(d),
                        reinterpret_cast<const double*>(o + o_pose), reinterpret_cast<const u8*>(o), reinterpret_cast<const int*>(d + o_slot),

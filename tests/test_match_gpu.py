@@ -95,7 +95,7 @@ def test_bf_batch_dev_parity(bf, orc):
     import torch
 
     rng = np.random.default_rng(SEED)
-    B, capq, capt = 24, 1000, 1000  # B*capq >= 16384 -> exercises the 4-queries-per-wave kernel
+    B, capq, capt = 24, 1000, 1000  # both capacities >= 24: the matrix-core kernel (tests/forms.py; four queries per wave: test_match_forms_gpu.py)
     nq = rng.integers(0, capq + 1, B).astype(np.int32)
     nt = rng.integers(0, capt + 1, B).astype(np.int32)
     nq[0], nt[0] = capq, capt

@@ -258,23 +258,16 @@ def test_lockstep_glue_kernels_against_numpy():
     ref.close()
 
 
-def test_refine_frame_batch_dev_walks_features_like_the_reference(orc):
-    """snk_pose_refine_frame_batch_dev: `frame.mvpMapPoints` as indices, pairs in FEATURE order (PoseRefinement.cpp:37-57) -- what
-    TrackBruteForce leaves behind (TrackingCoarse.cpp:373-377: several frame features may carry the point of one reference feature).
-    A ragged batch: an ordinary frame, one whose features share few points, an empty frame, a frame with two pairs (pose untouched),
-    indices beyond the frame's point count (ignored) -- against orc.pose_refine on the pairs gathered in feature order; mvbOutlier
-    per feature identical, pose within 1e-9."""
-    import torch
-
-    from snake_slam_amd.tracking import KP64_DTYPE, PoseRefinement, frames_dev, pose_observations
+def frame_batch_case(cap, mcap, nf, npts):
+    """Inputs of snk_pose_refine_frame_batch_dev for five frames of capacity cap with nf features and npts of mcap points each: an
+    ordinary frame, one whose features share few points, an empty frame (nf[2] = 0), a frame with two pairs (features 5 and 200 of
+    frame 3), and in frame 4 indices beyond the frame's point count and beyond the table."""
+    from snake_slam_amd.tracking import KP64_DTYPE
 
     rng = np.random.default_rng(SEED + 4242)
-    B, cap, mcap = 5, 700, 500
-    dev = torch.device("cuda", 0)
-    cam = PH.CAM
-    ls = (np.float32(1.2) ** np.arange(4)).astype(np.float32)
-    nf = np.array([650, 400, 0, 300, 700], np.int32)
-    npts = np.array([500, 40, 10, 500, 480], np.int32)
+    B = 5
+    nf, npts = np.array(nf, np.int32), np.array(npts, np.int32)
+    assert len(nf) == len(npts) == B and nf.max() <= cap and npts.max() <= mcap and nf[2] == 0 and nf[3] > 200 and nf[4] > 7
     kps = np.zeros((B, cap), KP64_DTYPE)
     depth = np.full((B, cap), -1.0, np.float32)
     pts = np.zeros((B, mcap, 3))
@@ -300,24 +293,44 @@ def test_refine_frame_batch_dev_walks_features_like_the_reference(orc):
         if b == 4:
             frame_pt[b, 7] = npts[b] + 3    # beyond the frame's points: ignored
             frame_pt[b, n - 1] = mcap + 50  # beyond the table: ignored
+    ls = (np.float32(1.2) ** np.arange(4)).astype(np.float32)
+    return dict(B=B, cap=cap, mcap=mcap, nf=nf, npts=npts, kps=kps, depth=depth, pts=pts, frame_pt=frame_pt, poses0=poses0, ls=ls)
+
+
+def run_frame_batch(case):
+    """The call on the device; returns (poses [B, 7], mvbOutlier [B, cap], inliers [B])."""
+    import torch
+
+    from snake_slam_amd.tracking import PoseRefinement, frames_dev
+
+    B, cap, mcap = case["B"], case["cap"], case["mcap"]
+    dev = torch.device("cuda", 0)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    d_kps, d_depth, d_n = t(kps.view(np.uint8).reshape(B, cap, 24)), t(depth), t(nf)
+    d_kps, d_depth, d_n = t(case["kps"].view(np.uint8).reshape(B, cap, 24)), t(case["depth"]), t(case["nf"])
     d_desc = torch.zeros((B, cap, 4), dtype=torch.int64, device=dev)
     d_rp, d_tk = torch.zeros((B, cap), dtype=torch.float32, device=dev), torch.zeros((B, cap), dtype=torch.uint8, device=dev)
     d_cs = torch.zeros((B, 38 * 24 + 1), dtype=torch.int32, device=dev)
-    d_pts, d_fp, d_np, d_pose = t(pts.view(np.uint8).reshape(B, mcap, 24)), t(frame_pt), t(npts), t(poses0)
+    d_pts, d_fp, d_np, d_pose = t(case["pts"].view(np.uint8).reshape(B, mcap, 24)), t(case["frame_pt"]), t(case["npts"]), t(case["poses0"])
     outl = torch.full((B, cap), 9, dtype=torch.uint8, device=dev)
     inl = torch.full((B,), -7, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
     ref = PoseRefinement()
     try:
         fd = frames_dev((0.0, 0.0, 752.0, 480.0), d_n, d_kps, d_desc, d_rp, d_tk, d_cs)
-        ref.refine_frame_batch_dev(fd, d_depth, cam, d_pts, d_fp, d_np, ls, d_pose, outl, inl)
+        ref.refine_frame_batch_dev(fd, d_depth, PH.CAM, d_pts, d_fp, d_np, case["ls"], d_pose, outl, inl)
         ref.sync()
     finally:
         ref.close()
-    got_pose, got_outl, got_inl = d_pose.cpu().numpy(), outl.cpu().numpy(), inl.cpu().numpy()
-    for b in range(B):
+    return d_pose.cpu().numpy(), outl.cpu().numpy(), inl.cpu().numpy()
+
+
+def check_frame_batch(orc, case, got):
+    """Against orc.pose_refine on the pairs gathered in feature order: mvbOutlier per feature identical, pose within 1e-9."""
+    from snake_slam_amd.tracking import pose_observations
+
+    cap, nf, npts, kps, depth, pts, frame_pt, poses0, ls = (case[k] for k in ("cap", "nf", "npts", "kps", "depth", "pts", "frame_pt", "poses0", "ls"))
+    got_pose, got_outl, got_inl = got
+    for b in range(case["B"]):
         n = int(nf[b])
         f = np.nonzero((frame_pt[b, :n] >= 0) & (frame_pt[b, :n] < npts[b]))[0]
         want_outl = np.zeros(cap, np.uint8)
@@ -325,8 +338,18 @@ def test_refine_frame_batch_dev_walks_features_like_the_reference(orc):
             assert np.array_equal(got_pose[b], poses0[b]) and got_inl[b] == 0 and not got_outl[b].any(), b
             continue
         obs = pose_observations(kps[b, f], depth[b, f], ls)
-        wpose, woutl, winl = orc.pose_refine(poses0[b], orc.Camera(*cam), pts[b, frame_pt[b, f]], obs)
+        wpose, woutl, winl = orc.pose_refine(poses0[b], orc.Camera(*PH.CAM), pts[b, frame_pt[b, f]], obs)
         want_outl[f] = woutl
         assert np.allclose(got_pose[b], wpose, rtol=0, atol=1e-9), b
         assert got_inl[b] == winl and np.array_equal(got_outl[b], want_outl), b
     assert len(set(frame_pt[0][frame_pt[0] >= 0].tolist())) < (frame_pt[0] >= 0).sum()  # the case did contain shared points
+
+
+def test_refine_frame_batch_dev_walks_features_like_the_reference(orc):
+    """snk_pose_refine_frame_batch_dev: `frame.mvpMapPoints` as indices, pairs in FEATURE order (PoseRefinement.cpp:37-57) -- what
+    TrackBruteForce leaves behind (TrackingCoarse.cpp:373-377: several frame features may carry the point of one reference feature).
+    A ragged batch: an ordinary frame, one whose features share few points, an empty frame, a frame with two pairs (pose untouched),
+    indices beyond the frame's point count (ignored) -- against orc.pose_refine on the pairs gathered in feature order; mvbOutlier
+    per feature identical, pose within 1e-9.  (The same at the capacities where the kernel form changes: test_pose_forms_gpu.py.)"""
+    case = frame_batch_case(700, 500, [650, 400, 0, 300, 700], [500, 40, 10, 500, 480])
+    check_frame_batch(orc, case, run_frame_batch(case))

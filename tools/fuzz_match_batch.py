@@ -1,5 +1,6 @@
 """Seeded fuzz of the BATCHED, device-resident stereo and brute-force matchers and of the rectification kernel against the oracle:
-random batch sizes (both stereo kernels: B < 8 row-index sort, B >= 8 one workgroup per frame; both kNN-2 kernels), capacities, counts
+random batch sizes and capacities (three kNN-2 kernels: one or four queries per wavefront and the matrix-core kernel; four stereo forms: B >= 8 one
+workgroup per frame, otherwise the row index by counting or by the network with 16 lanes per keypoint, unindexed past 8192 right keypoints), counts
 per frame including 0 and 1, level counts, relaxed / strict gates, random distortion / rotation / new-K rectifications.
 
     python tools/fuzz_match_batch.py [--seconds 120] [--seed 1]
@@ -36,7 +37,7 @@ def main():
         kind = int(rng.integers(0, 3))
         B = int(rng.choice([1, 2, 7, 8, 9, 24, 40]))
         if kind == 0:
-            capq, capt = int(rng.choice([1, 64, 300, 1000])), int(rng.choice([1, 65, 400, 1000]))
+            capq, capt = int(rng.choice([1, 64, 300, 1000])), int(rng.choice([1, 20, 65, 400, 1000]))
             nq, nt = rng.integers(0, capq + 1, B).astype(np.int32), rng.integers(0, capt + 1, B).astype(np.int32)
             q, tr = rand_desc(rng, B * capq).reshape(B, capq, 4), rand_desc(rng, B * capt).reshape(B, capt, 4)
             out = torch.full((B, capq, 4), -7, dtype=torch.int32, device=dev)
@@ -64,7 +65,7 @@ def main():
             what = f"bf B {B} cap {capq}x{capt} th {th} ratio {ratio}" + (detail if not ok else "")
             n["bf"] += 1
         elif kind == 1:
-            capl, capr = int(rng.choice([70, 700, 1500])), int(rng.choice([65, 650, 1400]))
+            capl, capr = int(rng.choice([70, 700, 1500])), int(rng.choice([65, 650, 1400, 2600]))
             levels, relaxed = int(rng.integers(1, 8)), bool(rng.integers(0, 2))
             L, R = np.zeros((B, capl), KP64), np.zeros((B, capr), KP64)
             DL, DR = np.zeros((B, capl, 4), np.uint64), np.zeros((B, capr, 4), np.uint64)
