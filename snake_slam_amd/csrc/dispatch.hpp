@@ -23,6 +23,24 @@ inline Knn2Form knn2_form(int nq_cap, int nt_cap, int batch, bool no_mfma)
     return (long long)batch * nq_cap >= BF_WIDE_MIN_WORK ? Knn2Form::vector4 : Knn2Form::vector1;
 }
 
+// Inside Knn2Form::mfma: two query blocks (64 queries) per wavefront -- the wide form, 256 queries per workgroup -- instead of one.
+// It halves the LDS reads, the train expansion and the barriers per query, and the number of workgroups with them; so it is
+// taken from BF_MFMA_WIDE_MIN_WGS wide workgroups on: with 1000 queries per frame it equals the narrow form at 64 frames (256 wide
+// workgroups) and is ahead at 128 (512), the first measured point where it wins (profiles/NOTES.md, r08).
+// wide_env: SNK_BF_MFMA_WIDE (0 / 1 force a form, -1 = unset).
+constexpr int BF_MFMA_WIDE_MIN_WGS = 512;
+
+constexpr bool knn2_mfma_wide(int nq_cap, int /*nt_cap*/, int batch, int wide_env)
+{
+    return wide_env >= 0 ? wide_env != 0 : (long long)batch * ((nq_cap + 255) / 256) >= BF_MFMA_WIDE_MIN_WGS;
+}
+
+// Inside Knn2Form::mfma: keys of distance << 13 | index, which the matrix pipe forms whole (matcher.hip), while every train index
+// fits 13 bits; 20-bit keys formed by the vector ALU beyond.  allowed: false under SNK_BF_MFMA_NO_SHORT.
+constexpr int BF_MFMA_SHORT_NT = 8192;
+
+constexpr bool knn2_mfma_short(int nt_cap, bool allowed) { return allowed && nt_cap <= BF_MFMA_SHORT_NT; }
+
 // ---- stereo matcher (snk_stereo_match, stereo_match_batch_dev_impl) ---------------------------------------------------------------
 constexpr int ST_SORT_MAX     = 8192;  // right keypoints per image the in-LDS row index handles
 constexpr int ST_FRAME_MAX    = 2560;  // right keypoints per frame stereo_frame_kernel keeps in LDS

@@ -126,94 +126,125 @@ __global__ __launch_bounds__(256) void bf_knn2_kernel(const uint4* __restrict__ 
 // kNN-2 on the matrix cores.  The 256-bit Hamming distance is h = |q| + |t| - 2 (q . t) with q . t the dot product of
 // the descriptors' bits -- an exact int8 GEMM.  The all-pairs scan is bound by the vector popcount rate (22 VALU
 // instructions per pair in bf_knn2_kernel); v_mfma_i32_32x32x32_i8 computes 32 x 32 dot products over 32 bit-bytes in
-// one instruction, leaving the vector ALU the top-2 bookkeeping (4 instructions per pair).
-//   workgroup = 4 wavefronts = 4 blocks of 32 queries; train descriptors go by in tiles of 32.
-//   bit -> byte expansion: byte c of dword ((w >> kc) & 0x01010101) is bit kc + 8 c of descriptor word w; lane group
+// one instruction, leaving the vector ALU the top-2 bookkeeping (2 or 3 instructions per pair, below).
+//   workgroup = 4 wavefronts, each with NB blocks of 32 queries (NB = 1: the narrow form, 128 queries per workgroup; NB = 2: the wide
+//   form, 256 -- dispatch.hpp, knn2_mfma_wide); train descriptors go by in tiles of 32.
+//   bit -> byte expansion: byte c of the dword expanded at shift kc is bit kc + 8 c of descriptor word w; lane group
 //   g = lane >> 5 takes the g-th 128-bit half, MFMA step kc the shift kc.  Queries (B operand) are expanded once into
-//   32 registers; every train tile is expanded once per workgroup into LDS (8 KiB, double buffered) and read as the
-//   A operand by the four wavefronts.  C[row = train][col = query]: lane holds 16 trains of query lane & 31
-//   (row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)).
-//   keys: |t| << 20 | train index (per tile in LDS, sentinel for rows past nt) minus dot << 21 orders a query's
-//   candidates like distance << 20 | index (the query's own popcount is a constant, added at the end).
+//   32 NB registers; every train tile is expanded once per workgroup into LDS (8 KiB, double buffered) and read as the A operand
+//   by the four wavefronts, each fragment feeding NB independent accumulator chains.  C[row = train][col = query]: lane holds 16
+//   trains of query lane & 31 (row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)).
+//   keys, SHORT = false (any train set the API takes): trains expand to bytes 0 / 1, queries to 0 / -1, so the accumulator is MINUS
+//   the dot product and (acc << 21) + (|t| << 20 | train index) (the second term per tile in LDS, sentinel for rows past nt) -- one
+//   v_lshl_add_u32 -- orders a query's candidates like distance << 20 | index; the two smallest are kept (v_med3_i32 + v_min_i32).
+//   keys, SHORT = true (nt_cap <= BF_MFMA_SHORT_NT, the index fits 13 bits): both sides expand to bytes 0 / -128, a common bit adds
+//   2^14, and the chain STARTS from -(|t| << 13 | index) instead of zero: the accumulator is then minus the whole key, no vector
+//   instruction forms it, and the two LARGEST are kept (v_med3_i32 + v_max_i32).  An MFMA holds the SIMD's vector issue for 8 of
+//   its 32 cycles and every vector instruction for 4, so the vector work hides behind the matrix pipe only up to 6 instructions per
+//   MFMA: 32 + 32 per 16 MFMAs of top-2 in this form against 96 in the other.
+//   The query's own popcount is a constant of the order, added at the end.
+//   __launch_bounds__(256, 2): at most 256 registers, which lets the compiler keep the accumulators in VGPRs (the register file is
+//   unified) -- no v_accvgpr_read in front of the top-2.
 // ------------------------------------------------------------------------------------------------
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-constexpr int BFM_SENTINEL = 0x7F000000;  // "no train": larger than any key, survives the subtraction of dot << 21 (dot = 0)
+constexpr int BFM_SENTINEL = 0x7F000000;  // "no train": beyond any key, and stays there when dot << 21 (<< 14) is added: dot = 0
+constexpr u32 BFS_IDX_BITS = 13;          // SHORT keys: distance << 13 | index
+static_assert(BF_MFMA_SHORT_NT == 1 << BFS_IDX_BITS, "the SHORT key's index field holds every index below BF_MFMA_SHORT_NT");
 
+template <bool SHORT>
 __device__ __forceinline__ v4i expand_bits(const uint4& h, int kc)
 {
+    if constexpr (SHORT)
+    {
+        const u32 M = 0x80808080u;
+        return v4i{(int)((h.x << (7 - kc)) & M), (int)((h.y << (7 - kc)) & M), (int)((h.z << (7 - kc)) & M), (int)((h.w << (7 - kc)) & M)};
+    }
     const u32 M = 0x01010101u;
     return v4i{(int)((h.x >> kc) & M), (int)((h.y >> kc) & M), (int)((h.z >> kc) & M), (int)((h.w >> kc) & M)};
 }
 __device__ __forceinline__ int popc128(const uint4& h) { return __popc(h.x) + __popc(h.y) + __popc(h.z) + __popc(h.w); }
+__device__ __forceinline__ int med3s(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }  // selected as v_med3_i32
+// k1 <= k2 (MAXK: k1 >= k2) are the two smallest (largest) so far: the new second is the median of (k1, k2, key)
+template <bool MAXK>
 __device__ __forceinline__ void insert2s(int& k1, int& k2, int key)
 {
-    // k1 <= k2: the new second smallest is the median of (k1, k2, key) -- v_med3_i32 + v_min_i32, two instructions per
-    // pair instead of three in the kernel's epilogue (which, not the matrix pipe, is what limits it)
-    int m;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(m) : "v"(k1), "v"(k2), "v"(key));
-    k2 = m;
-    k1 = min(k1, key);
+    k2 = med3s(k1, k2, key);
+    k1 = MAXK ? max(k1, key) : min(k1, key);
 }
 
-__global__ __launch_bounds__(256) void bf_knn2_mfma_kernel(const uint4* __restrict__ query, const int* __restrict__ nq_dev,
-                                                           int nq_cap, int nq_host, const uint4* __restrict__ train,
-                                                           const int* __restrict__ nt_dev, int nt_cap, int nt_host,
-                                                           snk_knn2* __restrict__ out)
+template <int NB, bool SHORT>
+__global__ __launch_bounds__(256, 2) void bf_knn2_mfma_kernel(const uint4* __restrict__ query, const int* __restrict__ nq_dev,
+                                                              int nq_cap, int nq_host, const uint4* __restrict__ train,
+                                                              const int* __restrict__ nt_dev, int nt_cap, int nt_host,
+                                                              snk_knn2* __restrict__ out)
 {
     __shared__ v4i As[2][8 * 2 * 32];  // [buffer][(kc * 2 + g) * 32 + train row]
-    __shared__ __attribute__((aligned(16))) int ptk[2][32];
+    __shared__ v16i ptk[2][2];         // [buffer][g]: the key terms of the 16 rows a lane of group g holds, in the accumulator's order
+    constexpr int NONE = SHORT ? -BFM_SENTINEL : BFM_SENTINEL;
     const int b = blockIdx.y;
     int nq      = nq_dev ? nq_dev[b] : nq_host;
     int nt      = nt_dev ? nt_dev[b] : nt_host;
     nq          = nq < nq_cap ? nq : nq_cap;
     nt          = nt < nt_cap ? nt : nt_cap;
-    if ((int)blockIdx.x * 128 >= nq) return;  // whole workgroup
+    if ((int)blockIdx.x * (128 * NB) >= nq) return;  // whole workgroup
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int j = lane & 31, g = lane >> 5;
-    const int q0 = (blockIdx.x * 4 + wave) * 32;
+    const int q0 = (blockIdx.x * 4 + wave) * (32 * NB);
     const uint4* qb = query + (size_t)b * nq_cap * 2;
     const uint4* tb = train + (size_t)b * nt_cap * 2;
 
-    // B operand: this lane's half of query q0 + j, all 8 shifts
-    const int qi   = min(q0 + j, nq - 1);
-    const uint4 qh = qb[(size_t)qi * 2 + g], qo = qb[(size_t)qi * 2 + (1 - g)];
-    const int pq   = popc128(qh) + popc128(qo);
-    v4i B[8];
+    // B operands: this lane's half of query q0 + 32 n + j, all 8 shifts
+    int pq[NB];
+    v4i B[NB][8];
 #pragma unroll
-    for (int kc = 0; kc < 8; ++kc) B[kc] = expand_bits(qh, kc);
+    for (int n = 0; n < NB; ++n)
+    {
+        const int qi   = min(q0 + 32 * n + j, nq - 1);
+        const uint4 qh = qb[(size_t)qi * 2 + g], qo = qb[(size_t)qi * 2 + (1 - g)];
+        pq[n]          = popc128(qh) + popc128(qo);
+#pragma unroll
+        for (int kc = 0; kc < 8; ++kc) {
+            const v4i e = expand_bits<SHORT>(qh, kc);
+            if constexpr (SHORT) B[n][kc] = e;
+            else B[n][kc] = v4i{(int)((u32)e.x * 0xFFu), (int)((u32)e.y * 0xFFu), (int)((u32)e.z * 0xFFu), (int)((u32)e.w * 0xFFu)};  // bytes 0 / -1
+        }
+    }
 
     // expansion role of this lane: train row e_i of the tile, half e_g, shifts 2 e_k and 2 e_k + 1
     const int e_i = wave * 8 + (lane & 7), e_g = (lane >> 3) & 1, e_k = lane >> 4;
+    const int e_p = ((e_i >> 2) & 1) * 16 + (e_i & 3) + 4 * (e_i >> 3);  // where row e_i stands in ptk[buf]
     const int ntiles = (nt + 31) >> 5;
-    auto fetch = [&](int t, uint4& h, uint4& o)
+    auto fetch = [&](int t, uint4& h)
     {
         const int ti = t * 32 + e_i;
         h = uint4{0u, 0u, 0u, 0u};
         if (ti < nt) h = tb[(size_t)ti * 2 + e_g];
-        (void)o;
     };
-    auto expand = [&](int t, int buf, const uint4& h, const uint4&)
+    auto expand = [&](int t, int buf, const uint4& h)
     {
-        As[buf][((2 * e_k) * 2 + e_g) * 32 + e_i]     = expand_bits(h, 2 * e_k);
-        As[buf][((2 * e_k + 1) * 2 + e_g) * 32 + e_i] = expand_bits(h, 2 * e_k + 1);
+        As[buf][((2 * e_k) * 2 + e_g) * 32 + e_i]     = expand_bits<SHORT>(h, 2 * e_k);
+        As[buf][((2 * e_k + 1) * 2 + e_g) * 32 + e_i] = expand_bits<SHORT>(h, 2 * e_k + 1);
         // |t| of the row: this lane's half + the other half, which the lane 8 further (e_g = 1, same e_i, e_k) holds
         const int ph = popc128(h);
         const int pt = ph + __shfl_down(ph, 8);
         if (lane < 8)
         {
-            const int ti  = t * 32 + e_i;
-            ptk[buf][e_i] = ti < nt ? ((pt << BF_IDX_BITS) | ti) : BFM_SENTINEL;
+            const int ti = t * 32 + e_i;
+            const int k  = SHORT ? -((pt << BFS_IDX_BITS) | ti) : ((pt << BF_IDX_BITS) | ti);
+            reinterpret_cast<int*>(&ptk[buf][0])[e_p] = ti < nt ? k : NONE;
         }
     };
 
-    int k1 = BFM_SENTINEL, k2 = BFM_SENTINEL;
-    uint4 h, o;
+    int k1[NB], k2[NB];
+#pragma unroll
+    for (int n = 0; n < NB; ++n) k1[n] = k2[n] = NONE;
+    uint4 h;
     if (ntiles > 0)
     {
-        fetch(0, h, o);
-        expand(0, 0, h, o);
-        if (ntiles > 1) fetch(1, h, o);
+        fetch(0, h);
+        expand(0, 0, h);
+        if (ntiles > 1) fetch(1, h);
     }
     __syncthreads();
     for (int t = 0; t < ntiles; ++t)
@@ -221,42 +252,61 @@ __global__ __launch_bounds__(256) void bf_knn2_mfma_kernel(const uint4* __restri
         const int buf = t & 1;
         if (t + 1 < ntiles)
         {
-            expand(t + 1, buf ^ 1, h, o);            // loaded one iteration ago
-            if (t + 2 < ntiles) fetch(t + 2, h, o);  // lands during this iteration
+            expand(t + 1, buf ^ 1, h);            // loaded one iteration ago
+            if (t + 2 < ntiles) fetch(t + 2, h);  // lands during this iteration
         }
-        v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        v4i a[8], pk[4];
+        v16i acc[NB];
+        v4i a[8];
 #pragma unroll
-        for (int kc = 0; kc < 8; ++kc) a[kc] = As[buf][(kc * 2 + g) * 32 + j];  // all LDS reads in flight before the MFMA chain
+        for (int kc = 0; kc < 8; ++kc) a[kc] = As[buf][(kc * 2 + g) * 32 + j];
+        const v16i pk = ptk[buf][g];
 #pragma unroll
-        for (int rq = 0; rq < 4; ++rq) pk[rq] = *reinterpret_cast<const v4i*>(&ptk[buf][8 * rq + 4 * g]);
+        for (int n = 0; n < NB; ++n)
+        {
+            acc[n] = SHORT ? pk : v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-        for (int kc = 0; kc < 8; ++kc) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kc], B[kc], acc, 0, 0, 0);
+            for (int kc = 0; kc < 8; ++kc) acc[n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[kc], B[n][kc], acc[n], 0, 0, 0);
+        }
 #pragma unroll
-        for (int rq = 0; rq < 4; ++rq)
+        for (int n = 0; n < NB; ++n)
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr)  // key' = (|t| << 20 | idx) - (dot << 21): one v_mad_i32_i24
-                insert2s(k1, k2, __mul24(acc[4 * rq + rr], -(1 << (BF_IDX_BITS + 1))) + pk[rq][rr]);
+            for (int r = 0; r < 16; ++r)
+            {
+                if constexpr (SHORT) insert2s<true>(k1[n], k2[n], acc[n][r]);
+                else insert2s<false>(k1[n], k2[n], (int)(((u32)acc[n][r] << (BF_IDX_BITS + 1)) + (u32)pk[r]));
+            }
+        // Left alone the scheduler reads one A fragment, waits, issues its MFMAs and reads the next.  Asked for here: the A fragments
+        // of the tile first (with the key terms when the chains start from them), then the first chain, the key terms behind it
+        // otherwise.  What is emitted: all fragment reads in flight ahead of the MFMAs, the MFMAs of the NB chains with no vector instruction
+        // among them (the tile's s_barrier may stand among them: they need registers only), one s_nop for the result latency of the last MFMA, then the top-2 of all
+        // chains.  The top-2 of one chain does NOT run in the shadow of the next: hints of (1 MFMA, n VALU) groups came out empty,
+        // so that latency is covered by the other wavefronts of the SIMD, not inside this one.
+        __builtin_amdgcn_sched_group_barrier(0x100, SHORT ? 12 : 8, 0);  // DS read
+        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);               // MFMA
+        if constexpr (!SHORT) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
         __syncthreads();
     }
-    // the two halves of the wavefront hold disjoint trains of the same query
+#pragma unroll
+    for (int n = 0; n < NB; ++n)
     {
-        const int o1 = __shfl_xor(k1, 32), o2 = __shfl_xor(k2, 32);
-        const int lo = min(k1, o1), hi = max(k1, o1), m = min(k2, o2);
-        k1 = lo;
-        k2 = min(hi, m);
-    }
-    if (lane < 32 && q0 + lane < nq)
-    {
-        snk_knn2 r;
-        const int a1 = k1 >= BFM_SENTINEL - (1 << 30) ? -1 : k1 + (pq << BF_IDX_BITS);
-        const int a2 = k2 >= BFM_SENTINEL - (1 << 30) ? -1 : k2 + (pq << BF_IDX_BITS);
-        const bool v1 = a1 >= 0 && (a1 >> BF_IDX_BITS) < SNK_DIST_INF, v2 = a2 >= 0 && (a2 >> BF_IDX_BITS) < SNK_DIST_INF;
-        r.dist1 = v1 ? a1 >> BF_IDX_BITS : SNK_DIST_INF;
-        r.idx1  = v1 ? (int)((u32)a1 & BF_IDX_MASK) : -1;
-        r.dist2 = v2 ? a2 >> BF_IDX_BITS : SNK_DIST_INF;
-        r.idx2  = v2 ? (int)((u32)a2 & BF_IDX_MASK) : -1;
-        out[(size_t)b * nq_cap + q0 + lane] = r;
+        // the two halves of the wavefront hold disjoint trains of the same query
+        const int o1 = __shfl_xor(k1[n], 32), o2 = __shfl_xor(k2[n], 32);
+        int r1, r2;
+        if constexpr (SHORT) r1 = -max(k1[n], o1), r2 = -max(min(k1[n], o1), max(k2[n], o2));
+        else r1 = min(k1[n], o1), r2 = min(max(k1[n], o1), min(k2[n], o2));
+        if (lane < 32 && q0 + 32 * n + lane < nq)
+        {
+            constexpr u32 IB = SHORT ? BFS_IDX_BITS : BF_IDX_BITS, IM = (1u << IB) - 1u;
+            snk_knn2 r;
+            const int a1 = r1 >= BFM_SENTINEL - (1 << 30) ? -1 : r1 + (pq[n] << IB);
+            const int a2 = r2 >= BFM_SENTINEL - (1 << 30) ? -1 : r2 + (pq[n] << IB);
+            const bool v1 = a1 >= 0 && (a1 >> IB) < SNK_DIST_INF, v2 = a2 >= 0 && (a2 >> IB) < SNK_DIST_INF;
+            r.dist1 = v1 ? a1 >> IB : SNK_DIST_INF;
+            r.idx1  = v1 ? (int)((u32)a1 & IM) : -1;
+            r.dist2 = v2 ? a2 >> IB : SNK_DIST_INF;
+            r.idx2  = v2 ? (int)((u32)a2 & IM) : -1;
+            out[(size_t)b * nq_cap + q0 + 32 * n + lane] = r;
+        }
     }
 }
 
@@ -915,14 +965,23 @@ static int launch_knn2(snk_matcher* m, const uint64_t* q, const int32_t* nq_dev,
 {
     if (batch <= 0 || nq_cap <= 0) return SNK_OK;
     // The form by the launch shape (dispatch.hpp): the matrix-core kernel once a query block (32) and a train tile (32) are mostly
-    // full; the vector kernel for small sets (SNK_BF_NO_MFMA=1 forces it, for A/B measurements), with 4 queries per wavefront once
-    // there is enough work to fill 256 CUs, else 1 (latency).
+    // full -- two query blocks per wavefront once that still fills the chip (SNK_BF_MFMA_WIDE=0 / 1 forces one / two), 13-bit keys
+    // made by the matrix pipe where the train capacity allows (SNK_BF_MFMA_NO_SHORT=1: never) --; the vector
+    // kernel for small sets (SNK_BF_NO_MFMA=1 forces it, for A/B measurements), with 4 queries per wavefront once there is enough
+    // work to fill 256 CUs, else 1 (latency).
     static const bool no_mfma = getenv("SNK_BF_NO_MFMA") != nullptr;
+    static const int wide_env  = getenv("SNK_BF_MFMA_WIDE") ? (atoi(getenv("SNK_BF_MFMA_WIDE")) != 0 ? 1 : 0) : -1;
+    static const bool short_env = getenv("SNK_BF_MFMA_NO_SHORT") == nullptr;  // A/B, tests: the 20-bit keys for every train set
     switch (knn2_form(nq_cap, nt_cap, batch, no_mfma))
     {
     case Knn2Form::mfma:
-        hipLaunchKernelGGL(bf_knn2_mfma_kernel, dim3(ceil_div(nq_cap, 128), batch), dim3(256), 0, m->stream, (const uint4*)q, nq_dev,
-                           nq_cap, nq_host, (const uint4*)t, nt_dev, nt_cap, nt_host, out);
+    {
+        const bool wide = knn2_mfma_wide(nq_cap, nt_cap, batch, wide_env), shrt = knn2_mfma_short(nt_cap, short_env);
+        auto kernel = wide ? (shrt ? bf_knn2_mfma_kernel<2, true> : bf_knn2_mfma_kernel<2, false>)
+                           : (shrt ? bf_knn2_mfma_kernel<1, true> : bf_knn2_mfma_kernel<1, false>);
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(nq_cap, wide ? 256 : 128), batch), dim3(256), 0, m->stream, (const uint4*)q, nq_dev, nq_cap,
+                           nq_host, (const uint4*)t, nt_dev, nt_cap, nt_host, out);
+    }
         break;
     case Knn2Form::vector4:
         hipLaunchKernelGGL(bf_knn2_kernel<4>, dim3(ceil_div(nq_cap, 16), batch), dim3(256), 0, m->stream, (const uint4*)q, nq_dev, nq_cap,
