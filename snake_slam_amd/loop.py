@@ -69,12 +69,15 @@ class RegistrationRansac(_Handle):
     def _result(P, k):
         return dict(T=np.array(P.T[:]), scale=float(P.scale), inliers=int(P.inliers), mask=k[1][: P.n].copy(), best=int(P.best_iteration))
 
-    def solve_batch(self, problems):
+    def solve_batch(self, problems, first_problem: int = 0):
         """problems: list of dict(points1 [n, 3], points2 [n, 3], ips1 [n, 2], ips2 [n, 2], optional T [7] and scale).  One launch;
-        returns one dict per problem: T (qx qy qz qw tx ty tz), scale, inliers, mask [n] uint8, best (the winning hypothesis)."""
-        probs, keep = self._problems(problems)
-        _lib.check(self._lib.snk_sim3_ransac(self._h, C.byref(self.params), probs, len(problems)), "snk_sim3_ransac")
-        return [self._result(P, k) for P, k in zip(probs, keep)]
+        returns one dict per problem: T (qx qy qz qw tx ty tz), scale, inliers, mask [n] uint8, best (the winning hypothesis).  The
+        sampler draws problem i of a call from (seed, i); ``first_problem`` = j gives the problems the indices j, j + 1, ... by putting
+        j empty problems in front, so that a problem solved on its own repeats what it gave as entry j of a batch."""
+        empty = dict(points1=np.zeros((0, 3)), points2=np.zeros((0, 3)), ips1=np.zeros((0, 2)), ips2=np.zeros((0, 2)))
+        probs, keep = self._problems([empty] * int(first_problem) + list(problems))
+        _lib.check(self._lib.snk_sim3_ransac(self._h, C.byref(self.params), probs, len(keep)), "snk_sim3_ransac")
+        return [self._result(P, k) for P, k in zip(probs, keep)][int(first_problem):]
 
     def solve(self, points1, points2, ips1, ips2):
         """``auto [T, scale, nInliers] = solver.solve(its, compute_scale)``: returns (T, scale, inliers, vbInliers)."""

@@ -432,12 +432,15 @@ class P3PRansac(_Handle):
         return dict(pose=np.array(P.pose[:]), inliers=int(P.inliers), mask=k[2][: P.n].copy(), matches=k[3][: P.inliers].copy(),
                     best=(int(P.best_iteration), int(P.best_solution)))
 
-    def solve_batch(self, problems):
+    def solve_batch(self, problems, first_problem: int = 0):
         """problems: list of dict(wps [n, 3], nips [n, 2], optional pose [7]).  One launch; returns one dict per problem:
-        pose, inliers, mask [n] uint8, matches (ascending indices), best = (iteration, solution)."""
-        probs, keep = self._problems(problems)
-        _lib.check(self._lib.snk_p3p_ransac(self._h, C.byref(self.params), probs, len(problems)), "snk_p3p_ransac")
-        return [self._result(P, k) for P, k in zip(probs, keep)]
+        pose, inliers, mask [n] uint8, matches (ascending indices), best = (iteration, solution).  The sampler draws problem i of a
+        call from (seed, i); ``first_problem`` = j gives the problems the indices j, j + 1, ... by putting j empty problems in front,
+        so that a problem solved on its own repeats what it gave as entry j of a batch."""
+        empty = dict(wps=np.zeros((0, 3)), nips=np.zeros((0, 2)))
+        probs, keep = self._problems([empty] * int(first_problem) + list(problems))
+        _lib.check(self._lib.snk_p3p_ransac(self._h, C.byref(self.params), probs, len(keep)), "snk_p3p_ransac")
+        return [self._result(P, k) for P, k in zip(probs, keep)][int(first_problem):]
 
     def solve(self, wps, ips, pose=None):
         """``inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask)``: returns (inliers, pose, inlierMatches, inlierMask)."""

@@ -458,3 +458,132 @@ def gpu_cases():
             for c, noise in enumerate((0.0, 1.0)):
                 out.append(make_case(n, share, noise, 1000 + 100 * a + 10 * b + c))
     return out
+
+
+# ------------------------------------------------------------------ edge cases ------------
+# the numbers of snake_slam_amd/csrc/p3p.hip the table below is built on (tests/test_p3p_numpy.py::test_pinned_limits_of_the_kernel
+# reads them from the source): pairs per problem, iterations per call, hypotheses per pass of the kernel's loop, bytes of LDS a pair and
+# per launch, and what a launch may ask for before the kernel's limit has to be raised
+MAX_PAIRS = 3072
+MAX_ITERATIONS = 1 << 20
+GROUP = 256
+LDS_BYTES_PER_PAIR, LDS_BYTES_FIXED = 44, 8
+LDS_DEFAULT_LIMIT = 65536
+
+
+def winner_is_exact(want) -> bool:
+    """True where the restatement decides the winner beyond rounding: it has one, the winning hypothesis is not borderline, and no
+    borderline hypothesis comes within its own count spread of the best count."""
+    H = want["hyp"]
+    kb = want["best"][0]
+    if H is None or kb < 0 or H["borderline"][kb]:
+        return False
+    top = H["counts"].max(1)
+    spread = (H["counts_hi"] - H["counts_lo"]).max(1)
+    return all(top[kb] - top[h] > spread[h] for h in np.nonzero(H["borderline"])[0])
+
+
+def groups_at_best(want):
+    """The groups of GROUP hypotheses (k // GROUP) that hold a hypothesis with the best count."""
+    top = want["hyp"]["counts"].max(1)
+    return sorted({int(k) // GROUP for k in np.nonzero(top == top.max())[0]})
+
+
+# property name -> what the restatement's run `r` of case `c` has to show, beyond a borderline share of at most half the cap
+EDGE_PROPERTIES = {
+    # nothing more: the shape is the point
+    "shape": lambda c, r: True,
+    # every hypothesis reaches n, so every lane of every group ties and the first hypothesis has to win
+    "all_tie": lambda c, r: bool((r["hyp"]["counts"].max(1) == len(c["wps"])).all()) and r["best"][0] == 0 and winner_is_exact(r),
+    # the winner lies beyond the first group / in the last group of 1024 iterations
+    "late": lambda c, r: r["best"][0] >= GROUP and winner_is_exact(r),
+    "last_group": lambda c, r: r["best"][0] >= 3 * GROUP and winner_is_exact(r),
+    # the best count is reached in two different groups, the first of them not group 0: the running best has to keep the earlier one
+    "cross_tie": lambda c, r: len(groups_at_best(r)) >= 2 and r["best"][0] >= GROUP and winner_is_exact(r),
+}
+
+
+def edge_grid():
+    """(n, wrong share, noise in px, iterations, property) of the edge cases: the strides of the scoring loop (64) and of the mask / list
+    compaction (256) with one, two and three groups of hypotheses, winners and ties beyond the first group, either side of the 64 KB
+    of LDS a launch gets without asking (1489 / 1490 pairs), and the maximum."""
+    out = [(n, 0.0, 0.0, 2 * GROUP + 1, "all_tie") for n in (63, 64, 65)]
+    out += [(255, 0.3, 1.0, GROUP, "shape"), (256, 0.3, 1.0, GROUP + 1, "shape"), (257, 0.3, 1.0, 2 * GROUP, "shape")]
+    out += [(200, 0.9, 0.0, 4 * GROUP, "late"), (65, 0.9, 0.0, 4 * GROUP, "last_group"), (257, 0.9, 0.0, 4 * GROUP, "cross_tie")]
+    out += [(1489, 0.3, 1.0, GROUP + 1, "shape"), (1490, 0.3, 1.0, GROUP + 1, "shape")]
+    out += [(MAX_PAIRS, 0.3, 1.0, 600, "shape"), (MAX_PAIRS, 0.0, 0.0, 300, "all_tie")]
+    return out
+
+
+def edge_ok(c, prop, r=None):
+    r = r if r is not None else ransac(c["wps"], c["nips"], c["iterations"], c["threshold"], c["seed"])
+    return float(r["hyp"]["borderline"].mean()) <= 0.5 * BORDERLINE_CAP and bool(EDGE_PROPERTIES[prop](c, r))
+
+
+def make_edge_case(g, seed):
+    n, share, noise, iterations, prop = g
+    c = make_case(n, share, noise, seed, iterations)
+    c["name"] += f"_it{iterations}_{prop}"
+    c["property"] = prop
+    return c
+
+
+def first_edge_seed(j, g, limit=200):
+    """The first generator seed of 5000 + 100 j + 0, 1, 2, ... whose case satisfies the property of entry j of edge_grid()."""
+    return next(5000 + 100 * j + o for o in range(limit) if edge_ok(make_edge_case(g, 5000 + 100 * j + o), g[4]))
+
+
+# the generator seed of every entry of edge_grid(), found by first_edge_seed on the CPU
+# (tests/test_p3p_numpy.py::test_edge_seeds_are_the_first_that_qualify fails when this table is stale)
+EDGE_SEEDS = [5000 + 100 * j + o for j, o in enumerate([1, 0, 1, 0, 0, 0, 0, 3, 6, 0, 0, 0, 0])]
+
+
+def edge_cases():
+    return [make_edge_case(g, seed) for g, seed in zip(edge_grid(), EDGE_SEEDS)]
+
+
+# ------------------------------------------------------------------ the comparison of the GPU tests ------------
+def device_pose_distance(p7, R, t):
+    return pose_distance(quat_to_R(p7[:4]), p7[4:], R, t)
+
+
+def check_device_against_restatement(c, want, res, tri, ns, poses, cnt):
+    """What tests/test_p3p_gpu.py and tests/test_p3p_edges_gpu.py assert of one snk_p3p_debug_hypotheses call (`res, tri, ns, poses,
+    cnt` as P3PRansac.debug_hypotheses returns them) on case `c`, against `want` = ransac() of the same case: triplets equal; solution
+    counts and inlier counts equal on the hypotheses that are not borderline, poses within pose_tolerance(); winner, mask and ascending
+    list exact where winner_is_exact(want); the mask consistent with the returned pose; ground truth on the noise-free cases."""
+    H = want["hyp"]
+    assert np.array_equal(tri, H["triplets"])
+    border = H["borderline"]
+    print(f"{c['name']}: borderline share {border.mean():.4f}")
+    assert border.mean() <= BORDERLINE_CAP
+    ok = ~border
+    assert np.array_equal(ns[ok], H["valid"].sum(1)[ok])
+    worst = 0.0
+    for k in np.nonzero(ok)[0]:
+        slots = np.nonzero(H["valid"][k])[0]
+        for j, s in enumerate(slots):
+            worst = max(worst, device_pose_distance(poses[k, j], H["R"][k, s], H["t"][k, s]))
+            assert cnt[k, j] == H["counts"][k, s], (int(k), j, cnt[k].tolist(), H["counts"][k].tolist())
+    print(f"{c['name']}: largest pose difference to the restatement {worst:.2e}")
+    assert worst <= pose_tolerance()
+    # the winner
+    assert res["inliers"] == int(res["mask"].sum()) == len(res["matches"])
+    assert np.array_equal(np.nonzero(res["mask"])[0], res["matches"])
+    kb, sb = want["best"]
+    if winner_is_exact(want):
+        assert res["best"] == want["best"] and res["inliers"] == want["inliers"]
+        assert np.array_equal(res["mask"], want["mask"]) and np.array_equal(res["matches"], want["matches"])
+        assert device_pose_distance(res["pose"], H["R"][kb, want["slot"]], H["t"][kb, want["slot"]]) <= pose_tolerance()
+    elif kb >= 0:
+        assert res["inliers"] >= H["counts_lo"][kb, want["slot"]]
+    if res["best"][0] >= 0:
+        Rg, tg = quat_to_R(res["pose"][:4]).reshape(9), res["pose"][4:]
+        lo = inlier_mask(Rg, tg, c["wps"], c["nips"], c["threshold"] * (1 - BORDERLINE))
+        hi = inlier_mask(Rg, tg, c["wps"], c["nips"], c["threshold"] * (1 + BORDERLINE))
+        m = res["mask"].astype(bool)
+        assert (m[lo]).all() and not (m[~hi]).any()
+    true_inl = ~c["outlier"]
+    if c["noise_px"] == 0.0 and true_inl.sum() >= 4:
+        assert res["mask"][true_inl].all()
+        assert device_pose_distance(res["pose"], quat_to_R(c["pose"][:4]), c["pose"][4:]) <= pose_tolerance()

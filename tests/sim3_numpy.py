@@ -316,6 +316,18 @@ def measure_transform_floor(n_triplets=20000, seed=2026):
     return worst
 
 
+def measure_case_floor(cases):
+    """The same distance over the triplets of every valid hypothesis that is not borderline of the given cases."""
+    worst = 0.0
+    for c in cases:
+        H = hypotheses(c["P1"], c["P2"], c["ip1"], c["ip2"], c["iterations"], c["threshold"], c["compute_scale"], c["seed"])
+        tri = H["triplets"]
+        for k in np.nonzero(H["valid"] & ~H["borderline"])[0]:
+            Ru, tu, su = umeyama(c["P1"][tri[k]], c["P2"][tri[k]], c["compute_scale"])
+            worst = max(worst, transform_distance(H["R"][k], H["t"][k], H["s"][k], Ru, tu, su))
+    return worst
+
+
 # measured by tests/test_sim3_numpy.py::test_transform_tolerance_is_the_measured_floor: see its docstring
 TRANSFORM_FLOOR = 4.5e-6
 
@@ -398,3 +410,123 @@ CASE_SEEDS = [1000 * j + o for j, o in enumerate([0] * 8 + [7] + [0] * 28)]
 
 def gpu_cases():
     return [make_case(*g, seed) for g, seed in zip(case_grid(), CASE_SEEDS)]
+
+
+# ------------------------------------------------------------------ edge cases ------------
+# the numbers of snake_slam_amd/csrc/sim3.hip the table below is built on (tests/test_sim3_numpy.py::test_pinned_limits_of_the_kernel
+# reads them from the source): pairs of a problem kept in LDS (the rest go to the problem's slab in global memory), hypotheses per
+# pass of the kernel's loop, bytes a pair
+LDS_PAIRS = 1024
+GROUP = 256
+BYTES_PER_PAIR = 80
+
+
+def winner_is_exact(want) -> bool:
+    """True where the restatement decides the winner beyond rounding: it has one, the winning hypothesis is not borderline, and no
+    borderline hypothesis comes within its own count spread of the best count."""
+    H, kb = want["hyp"], want["best"]
+    if H is None or kb < 0 or H["borderline"][kb]:
+        return False
+    spread = H["counts_hi"] - H["counts_lo"]
+    return all(H["counts"][kb] - H["counts"][h] > spread[h] for h in np.nonzero(H["borderline"])[0])
+
+
+def groups_at_best(want):
+    """The groups of GROUP hypotheses (k // GROUP) that hold a hypothesis with the best count."""
+    c = want["hyp"]["counts"]
+    return sorted({int(k) // GROUP for k in np.nonzero(c == c.max())[0]})
+
+
+# property name -> what the restatement's run `r` of case `c` has to show, beyond a borderline share of at most half the cap
+EDGE_PROPERTIES = {
+    "shape": lambda c, r: True,  # nothing more: the shape is the point
+    "late": lambda c, r: r["best"] >= GROUP and winner_is_exact(r),  # the winner lies beyond the first group
+    # the best count is reached in two different groups, the first of them not group 0: the running best has to keep the earlier one
+    "cross_tie": lambda c, r: len(groups_at_best(r)) >= 2 and r["best"] >= GROUP and winner_is_exact(r),
+}
+
+
+def edge_grid():
+    """(n, wrong-pair share, noise, compute_scale, iterations, property) of the edge cases: one pair below, at, one pair above and well
+    above the LDS_PAIRS pairs that stay in LDS, each with the scale estimated and not, at 300 iterations; a winner and a tie beyond the first group."""
+    out = [(n, 0.3, 1.0, cs, 300, "shape") for n in (LDS_PAIRS - 1, LDS_PAIRS, LDS_PAIRS + 1, 1280) for cs in (True, False)]
+    out += [(200, 0.9, 0.0, True, 4 * GROUP, "late"), (257, 0.9, 0.0, False, 4 * GROUP, "cross_tie")]
+    return out
+
+
+def edge_ok(c, prop, r=None):
+    r = r if r is not None else ransac(c["P1"], c["P2"], c["ip1"], c["ip2"], c["iterations"], c["threshold"], c["compute_scale"], c["seed"])
+    return float(r["hyp"]["borderline"].mean()) <= 0.5 * BORDERLINE_CAP and bool(EDGE_PROPERTIES[prop](c, r))
+
+
+def make_edge_case(g, seed):
+    c = make_case(*g[:5], seed)
+    c["name"] += "_" + g[5]
+    c["property"] = g[5]
+    return c
+
+
+def first_edge_seed(j, g, limit=200):
+    """The first generator seed of 100000 + 1000 j + 0, 1, 2, ... whose case satisfies the property of entry j of edge_grid()."""
+    return next(100000 + 1000 * j + o for o in range(limit) if edge_ok(make_edge_case(g, 100000 + 1000 * j + o), g[5]))
+
+
+# the generator seed of every entry of edge_grid(), found by first_edge_seed on the CPU
+# (tests/test_sim3_numpy.py::test_edge_seeds_are_the_first_that_qualify fails when this table is stale)
+EDGE_SEEDS = [100000 + 1000 * j + o for j, o in enumerate([0] * 10)]
+
+
+def edge_cases():
+    return [make_edge_case(g, seed) for g, seed in zip(edge_grid(), EDGE_SEEDS)]
+
+
+# ------------------------------------------------------------------ the comparison of the GPU tests ------------
+def device_distance(T, scale, R, t, s):
+    return transform_distance(quat_to_R(T[:4]), T[4:], scale, R, t, s)
+
+
+def _case_mask(T, scale, c, th):
+    return inlier_mask(quat_to_R(T[:4]).reshape(9), T[4:], scale, c["P1"], c["P2"], c["ip1"], c["ip2"], th)
+
+
+def check_device_against_restatement(c, want, res, tri, valid, Ts, sc, cnt):
+    """What tests/test_sim3_gpu.py and tests/test_sim3_edges_gpu.py assert of one snk_sim3_debug_hypotheses call (`res, tri, valid, Ts,
+    sc, cnt` as RegistrationRansac.debug_hypotheses returns them) on case `c`, against `want` = ransac() of the same case: triplets
+    equal; validity and inlier counts equal on the hypotheses that are not borderline, transforms within transform_tolerance(); the
+    winner and its mask exact where winner_is_exact(want); the result consistent with the winning hypothesis; ground truth where the
+    restatement's own winner is a triplet of true pairs of a noise-free case."""
+    H = want["hyp"]
+    assert np.array_equal(tri, H["triplets"])
+    border = H["borderline"]
+    print(f"{c['name']}: borderline share {border.mean():.4f}")
+    assert border.mean() <= BORDERLINE_CAP
+    ok = ~border
+    assert np.array_equal(valid.astype(bool)[ok], H["valid"][ok])
+    assert np.array_equal(cnt[ok], H["counts"][ok]), np.nonzero(cnt != H["counts"])[0].tolist()
+    worst = 0.0
+    for k in np.nonzero(ok & H["valid"])[0]:
+        worst = max(worst, device_distance(Ts[k], sc[k], H["R"][k], H["t"][k], H["s"][k]))
+    print(f"{c['name']}: largest transform difference to the restatement {worst:.2e}")
+    assert worst <= transform_tolerance()
+    # the winner
+    assert res["inliers"] == int(res["mask"].sum())
+    kb = want["best"]
+    if winner_is_exact(want):
+        assert res["best"] == kb and res["inliers"] == want["inliers"] and np.array_equal(res["mask"], want["mask"])
+        assert device_distance(res["T"], res["scale"], H["R"][kb], H["t"][kb], H["s"][kb]) <= transform_tolerance()
+    elif kb >= 0:
+        assert res["inliers"] >= H["counts_lo"][kb]
+    else:
+        assert res["best"] == -1 or border[res["best"]]
+    if res["best"] >= 0:
+        assert res["T"].tobytes() == Ts[res["best"]].tobytes() and res["scale"] == sc[res["best"]] and res["inliers"] == cnt[res["best"]]
+        lo = _case_mask(res["T"], res["scale"], c, c["threshold"] * (1 - BORDERLINE))
+        hi = _case_mask(res["T"], res["scale"], c, c["threshold"] * (1 + BORDERLINE))
+        m = res["mask"].astype(bool)
+        assert m[lo].all() and not m[~hi].any()
+    else:
+        assert res["inliers"] == 0 and np.array_equal(res["T"], [0, 0, 0, 1, 0, 0, 0]) and res["scale"] == 1.0
+    # ground truth
+    if c["noise_px"] == 0.0 and kb >= 0 and not c["outlier"][H["triplets"][kb]].any():
+        assert res["mask"][~c["outlier"]].all()
+        assert device_distance(res["T"], res["scale"], c["R"], c["t"], c["s"]) <= transform_tolerance()

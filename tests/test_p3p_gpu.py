@@ -36,52 +36,11 @@ def run(solver, c, debug=True):
     return solver.solve_batch([dict(wps=c["wps"], nips=c["nips"])])[0]
 
 
-def pose_dist(p7, R, t):
-    return P.pose_distance(P.quat_to_R(p7[:4]), p7[4:], R, t)
-
-
 @pytest.mark.parametrize("c", CASES, ids=[c["name"] for c in CASES])
 def test_hypotheses_and_winner_match_the_restatement(solver, c):
-    res, tri, ns, poses, cnt = run(solver, c)
+    """The comparison is p3p_numpy.check_device_against_restatement, shared with tests/test_p3p_edges_gpu.py."""
     want = P.ransac(c["wps"], c["nips"], c["iterations"], c["threshold"], c["seed"])
-    H = want["hyp"]
-    assert np.array_equal(tri, H["triplets"])
-    border = H["borderline"]
-    print(f"{c['name']}: borderline share {border.mean():.4f}")
-    assert border.mean() <= P.BORDERLINE_CAP
-    ok = ~border
-    assert np.array_equal(ns[ok], H["valid"].sum(1)[ok])
-    worst = 0.0
-    for k in np.nonzero(ok)[0]:
-        slots = np.nonzero(H["valid"][k])[0]
-        for j, s in enumerate(slots):
-            worst = max(worst, pose_dist(poses[k, j], H["R"][k, s], H["t"][k, s]))
-            assert cnt[k, j] == H["counts"][k, s], (int(k), j, cnt[k].tolist(), H["counts"][k].tolist())
-    print(f"{c['name']}: largest pose difference to the restatement {worst:.2e}")
-    assert worst <= P.pose_tolerance()
-    # the winner
-    assert res["inliers"] == int(res["mask"].sum()) == len(res["matches"])
-    assert np.array_equal(np.nonzero(res["mask"])[0], res["matches"])
-    kb, sb = want["best"]
-    top = H["counts"].max(1)
-    spread = (H["counts_hi"] - H["counts_lo"]).max(1)
-    exact = kb >= 0 and not border[kb] and all(top[kb] - top[h] > spread[h] for h in np.nonzero(border)[0])
-    if exact:
-        assert res["best"] == want["best"] and res["inliers"] == want["inliers"]
-        assert np.array_equal(res["mask"], want["mask"]) and np.array_equal(res["matches"], want["matches"])
-        assert pose_dist(res["pose"], H["R"][kb, want["slot"]], H["t"][kb, want["slot"]]) <= P.pose_tolerance()
-    elif kb >= 0:
-        assert res["inliers"] >= H["counts_lo"][kb, want["slot"]]
-    if res["best"][0] >= 0:
-        Rg, tg = P.quat_to_R(res["pose"][:4]).reshape(9), res["pose"][4:]
-        lo = P.inlier_mask(Rg, tg, c["wps"], c["nips"], c["threshold"] * (1 - P.BORDERLINE))
-        hi = P.inlier_mask(Rg, tg, c["wps"], c["nips"], c["threshold"] * (1 + P.BORDERLINE))
-        m = res["mask"].astype(bool)
-        assert (m[lo]).all() and not (m[~hi]).any()
-    true_inl = ~c["outlier"]
-    if c["noise_px"] == 0.0 and true_inl.sum() >= 4:
-        assert res["mask"][true_inl].all()
-        assert pose_dist(res["pose"], P.quat_to_R(c["pose"][:4]), c["pose"][4:]) <= P.pose_tolerance()
+    P.check_device_against_restatement(c, want, *run(solver, c))
 
 
 def test_small_all_outlier_and_empty_inputs_return_cleanly(solver):

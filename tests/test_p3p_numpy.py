@@ -1,13 +1,18 @@
 """CPU: the numpy restatement of "snk-p3p v1" (tests/p3p_numpy.py) against ground truth and against itself -- the solver finds the
 true pose, every solution fits its own three points, the sampler is a pure function with distinct indices and a pinned vector, the
 restatement's own borderline share stays at most half the cap of the GPU test on every case that test uses, and pose_tolerance() is
-the measured floor."""
+the measured floor.  The edge cases of tests/test_p3p_edges_gpu.py (p3p_numpy.edge_cases()) are held to the same: their seeds are the
+first that show the stated property, and the numbers of p3p.hip they are built on are read from the source."""
+import re
+from pathlib import Path
+
 import numpy as np
 import pytest
 
 import p3p_numpy as P
 
 CASES = P.gpu_cases()
+EDGES = P.edge_cases()
 
 
 @pytest.fixture(scope="module")
@@ -109,9 +114,57 @@ def test_small_and_empty_inputs():
 def test_pose_tolerance_is_the_measured_floor():
     """pose_tolerance() = 10 x POSE_FLOOR, and POSE_FLOOR is what this test measures: the largest disagreement (largest entry of the
     rotation difference, translation difference relative to max(1, |t|)) between the closed form and the closed form polished by
-    Gauss-Newton on its three points, over every solution of every hypothesis that is not borderline of the 24 cases.  Measured
-    1.92e-12, kept as 2.0e-12."""
+    Gauss-Newton on its three points, over every solution of every hypothesis that is not borderline of the 24 cases of gpu_cases()
+    and the 13 of edge_cases().  Measured 1.92e-12 on the former, 6.45e-13 on the latter, kept as 2.0e-12."""
     floor = P.measure_pose_floor(CASES)
-    print(f"closed form vs Gauss-Newton polish: {floor:.3e}")
-    assert 0.5 * P.POSE_FLOOR <= floor <= P.POSE_FLOOR
+    edge = P.measure_pose_floor(EDGES)
+    print(f"closed form vs Gauss-Newton polish: {floor:.3e} on gpu_cases(), {edge:.3e} on edge_cases()")
+    assert 0.5 * P.POSE_FLOOR <= max(floor, edge) <= P.POSE_FLOOR
     assert P.pose_tolerance() == 10.0 * P.POSE_FLOOR
+
+
+# ------------------------------------------------------------------ the edge cases ------------
+def test_edge_grid_is_the_stated_one():
+    got = [(len(c["wps"]), c["outlier_share"], c["noise_px"], c["iterations"], c["property"]) for c in EDGES]
+    assert got == P.edge_grid() and len({c["name"] for c in EDGES}) == len(EDGES) == 13
+    assert [g[:4] for g in got[:6]] == [(63, 0.0, 0.0, 513), (64, 0.0, 0.0, 513), (65, 0.0, 0.0, 513), (255, 0.3, 1.0, 256),
+                                        (256, 0.3, 1.0, 257), (257, 0.3, 1.0, 512)]
+    for g, prop in zip(got[6:9], ("late", "last_group", "cross_tie")):
+        assert g[0] <= 300 and 0.85 <= g[1] <= 0.9 and g[2:] == (0.0, 1024, prop)
+    assert [g[:4] for g in got[9:]] == [(1489, 0.3, 1.0, 257), (1490, 0.3, 1.0, 257), (3072, 0.3, 1.0, 600), (3072, 0.0, 0.0, 300)]
+    # either side of what a launch gets without raising the kernel's limit, and the maximum
+    lds = lambda n: P.LDS_BYTES_PER_PAIR * n + P.LDS_BYTES_FIXED  # noqa: E731
+    assert lds(1489) <= P.LDS_DEFAULT_LIMIT < lds(1490) and P.MAX_PAIRS == 3072 and lds(P.MAX_PAIRS) == 135176
+
+
+def test_edge_seeds_are_the_first_that_qualify_and_borderline_share_is_at_most_half_the_cap():
+    for j, (g, seed, c) in enumerate(zip(P.edge_grid(), P.EDGE_SEEDS, EDGES)):
+        assert seed == P.first_edge_seed(j, g), (g, seed)
+        r = P.ransac(c["wps"], c["nips"], c["iterations"], c["threshold"], c["seed"])
+        share = float(r["hyp"]["borderline"].mean())
+        print(f"{c['name']}: borderline share {share:.4f}, winner {r['best']}, {r['inliers']} inliers, groups at the best count {P.groups_at_best(r)}")
+        assert share <= 0.5 * P.BORDERLINE_CAP, (c["name"], share)
+        k = r["best"][0]
+        if g[4] == "all_tie":  # every hypothesis explains every pair; the first one wins, with its first solution that does
+            assert k == 0 and r["inliers"] == g[0] and len(P.groups_at_best(r)) == -(-g[3] // P.GROUP) and P.winner_is_exact(r)
+            assert r["slot"] == int(np.argmax(r["hyp"]["counts"][0] == g[0]))
+        if g[4] in ("late", "last_group", "cross_tie"):
+            assert k >= (3 * P.GROUP if g[4] == "last_group" else P.GROUP) and P.winner_is_exact(r)
+        if g[4] == "cross_tie":
+            assert len(P.groups_at_best(r)) >= 2 and P.groups_at_best(r)[0] == k // P.GROUP
+
+
+def test_pinned_limits_of_the_kernel():
+    """The numbers the edge cases are built on, read from snake_slam_amd/csrc/p3p.hip: a moved carve fails here instead of leaving an
+    edge untested."""
+    src = (Path(__file__).resolve().parent.parent / "snake_slam_amd" / "csrc" / "p3p.hip").read_text()
+    one = lambda pattern: (lambda m: (len(m) == 1 and m[0]) or pytest.fail(f"{pattern}: {m}"))(re.findall(pattern, src))  # noqa: E731
+    assert int(one(r"constexpr int P3P_MAX_PAIRS\s*=\s*(\d+);")) == P.MAX_PAIRS
+    assert one(r"constexpr int P3P_MAX_ITERATIONS\s*=\s*([^;]+);").replace(" ", "") == "1<<20" and P.MAX_ITERATIONS == 1 << 20
+    assert int(one(r"for \(int k0 = 0; k0 < iterations; k0 \+= (\d+)\)")) == P.GROUP
+    assert int(one(r"__launch_bounds__\((\d+)\) void p3p_ransac_kernel")) == P.GROUP
+    per_pair, fixed = one(r"size_t lds_bytes\(int pairs\)\s*\{\s*return \(size_t\)pairs \* (\d+) \+ (\d+);")
+    assert (int(per_pair), int(fixed)) == (P.LDS_BYTES_PER_PAIR, P.LDS_BYTES_FIXED)
+    # the scoring loop walks the pairs 64 at a time, the mask / list compaction 256 at a time
+    assert len(re.findall(r"for \(int i0 = 0; i0 < n; i0 \+= 64\)", src)) == 1 and len(re.findall(r"for \(int i0 = 0; i0 < n; i0 \+= 256\)", src)) == 1
+    assert "pairs per problem outside [0, 3072]" in src and "frames->cap above 3072 features" in src

@@ -43,56 +43,10 @@ def setup(solver, c, iterations=None):
     return dict(points1=c["P1"], points2=c["P2"], ips1=c["ip1"], ips2=c["ip2"])
 
 
-def dist(T, scale, R, t, s):
-    return S.transform_distance(S.quat_to_R(T[:4]), T[4:], scale, R, t, s)
-
-
-def masks(T, scale, c, th):
-    R = S.quat_to_R(T[:4]).reshape(9)
-    return S.inlier_mask(R, T[4:], scale, c["P1"], c["P2"], c["ip1"], c["ip2"], th)
-
-
 @pytest.mark.parametrize("c", CASES, ids=[c["name"] for c in CASES])
 def test_hypotheses_and_winner_match_the_restatement(solver, restated, c):
-    res, tri, valid, Ts, sc, cnt = solver.debug_hypotheses(**setup(solver, c))
-    want = restated[c["name"]]
-    H = want["hyp"]
-    assert np.array_equal(tri, H["triplets"])
-    border = H["borderline"]
-    print(f"{c['name']}: borderline share {border.mean():.4f}")
-    assert border.mean() <= S.BORDERLINE_CAP
-    ok = ~border
-    assert np.array_equal(valid.astype(bool)[ok], H["valid"][ok])
-    assert np.array_equal(cnt[ok], H["counts"][ok]), np.nonzero(cnt != H["counts"])[0].tolist()
-    worst = 0.0
-    for k in np.nonzero(ok & H["valid"])[0]:
-        worst = max(worst, dist(Ts[k], sc[k], H["R"][k], H["t"][k], H["s"][k]))
-    print(f"{c['name']}: largest transform difference to the restatement {worst:.2e}")
-    assert worst <= S.transform_tolerance()
-    # the winner
-    assert res["inliers"] == int(res["mask"].sum())
-    kb = want["best"]
-    spread = H["counts_hi"] - H["counts_lo"]
-    exact = kb >= 0 and not border[kb] and all(H["counts"][kb] - H["counts"][h] > spread[h] for h in np.nonzero(border)[0])
-    if exact:
-        assert res["best"] == kb and res["inliers"] == want["inliers"] and np.array_equal(res["mask"], want["mask"])
-        assert dist(res["T"], res["scale"], H["R"][kb], H["t"][kb], H["s"][kb]) <= S.transform_tolerance()
-    elif kb >= 0:
-        assert res["inliers"] >= H["counts_lo"][kb]
-    else:
-        assert res["best"] == -1 or border[res["best"]]
-    if res["best"] >= 0:
-        assert res["T"].tobytes() == Ts[res["best"]].tobytes() and res["scale"] == sc[res["best"]] and res["inliers"] == cnt[res["best"]]
-        lo = masks(res["T"], res["scale"], c, c["threshold"] * (1 - S.BORDERLINE))
-        hi = masks(res["T"], res["scale"], c, c["threshold"] * (1 + S.BORDERLINE))
-        m = res["mask"].astype(bool)
-        assert m[lo].all() and not m[~hi].any()
-    else:
-        assert res["inliers"] == 0 and np.array_equal(res["T"], [0, 0, 0, 1, 0, 0, 0]) and res["scale"] == 1.0
-    # ground truth
-    if c["noise_px"] == 0.0 and kb >= 0 and not c["outlier"][H["triplets"][kb]].any():
-        assert res["mask"][~c["outlier"]].all()
-        assert dist(res["T"], res["scale"], c["R"], c["t"], c["s"]) <= S.transform_tolerance()
+    """The comparison is sim3_numpy.check_device_against_restatement, shared with tests/test_sim3_edges_gpu.py."""
+    S.check_device_against_restatement(c, restated[c["name"]], *solver.debug_hypotheses(**setup(solver, c)))
 
 
 def test_ground_truth_check_applies_to_the_clean_and_30_percent_cases(restated):

@@ -1,13 +1,19 @@
 """CPU: the numpy restatement of "snk-sim3 v1" (tests/sim3_numpy.py) against an independent closed form (Umeyama by
 numpy.linalg.svd), against ground truth and against itself: the transform of random triplets agrees with the SVD form within the
 recorded floor, noise-free scenes give back their transform, the iteration count is pinned, the case grid is the stated one with
-seeds that qualify, and the restatement's own borderline share stays within the cap of the GPU test on every case that test uses."""
+seeds that qualify, and the restatement's own borderline share stays within the cap of the GPU test on every case that test uses.
+The edge cases of tests/test_sim3_edges_gpu.py (sim3_numpy.edge_cases()) are held to the same with half the cap: their seeds are the
+first that show the stated property, and the numbers of sim3.hip they are built on are read from the source."""
+import re
+from pathlib import Path
+
 import numpy as np
 import pytest
 
 import sim3_numpy as S
 
 CASES = S.gpu_cases()
+EDGES = S.edge_cases()
 
 
 @pytest.fixture(scope="module")
@@ -20,12 +26,14 @@ def test_transform_tolerance_is_the_measured_floor():
     """transform_tolerance() = 10 x TRANSFORM_FLOOR, and TRANSFORM_FLOOR is what this test measures: the largest disagreement (largest
     entry of the rotation difference, translation difference relative to max(1, |t|), relative scale difference) between the
     restatement and Umeyama's SVD form over 20 000 random triplets (a random similarity plus 1 mm of noise, half with the scale
-    estimated) that are not ill-conditioned by the borderline marks.  Measured 4.19e-6, kept as 4.5e-6.  The figure is set by the few
-    triplets whose two largest eigenvalues are just over 1e-6 apart (relative): Newton's root of the quartic carries eps / gap there
-    and the adjugate column eps / gap^2; the median over the same triplets is printed."""
+    estimated) that are not ill-conditioned by the borderline marks, and over the triplets of every valid hypothesis that is not
+    borderline of edge_cases().  Measured 4.19e-6 on the former, 6.72e-8 on the latter, kept as 4.5e-6.  The figure is set
+    by the few triplets whose two largest eigenvalues are just over 1e-6 apart (relative): Newton's root of the quartic carries
+    eps / gap there and the adjugate column eps / gap^2; the median over the same triplets is printed."""
     floor = S.measure_transform_floor()
-    print(f"restatement vs SVD form: {floor:.3e}")
-    assert 0.5 * S.TRANSFORM_FLOOR <= floor <= S.TRANSFORM_FLOOR
+    edge = S.measure_case_floor(EDGES)
+    print(f"restatement vs SVD form: {floor:.3e} on random triplets, {edge:.3e} on edge_cases()")
+    assert 0.5 * S.TRANSFORM_FLOOR <= max(floor, edge) <= S.TRANSFORM_FLOOR
     assert S.transform_tolerance() == 10.0 * S.TRANSFORM_FLOOR
 
 
@@ -123,3 +131,42 @@ def test_corrected_pose_maps_world_points_like_the_sim3_chain():
     pw = rng.normal(size=(10, 3))
     want = pw @ R2.T @ R + ((t2 - t) @ R) / s
     assert np.abs(S.view_points(cp, pw) - want).max() < 1e-12
+
+
+# ------------------------------------------------------------------ the edge cases ------------
+def test_edge_grid_is_the_stated_one():
+    got = [(len(c["P1"]), c["outlier_share"], c["noise_px"], c["compute_scale"], c["iterations"], c["property"]) for c in EDGES]
+    assert got == S.edge_grid() and len({c["name"] for c in EDGES}) == len(EDGES) == 10
+    assert [(g[0], g[3], g[4]) for g in got[:8]] == [(n, cs, 300) for n in (1023, 1024, 1025, 1280) for cs in (True, False)]
+    assert got[8][0] <= 200 and got[8][1:3] == (0.9, 0.0) and got[8][4:] == (1024, "late") and got[9][4:] == (1024, "cross_tie")
+    assert S.LDS_PAIRS == 1024 and S.MAX_PAIRS == 2048
+
+
+def test_edge_seeds_are_the_first_that_qualify_and_borderline_share_is_at_most_half_the_cap():
+    for j, (g, seed, c) in enumerate(zip(S.edge_grid(), S.EDGE_SEEDS, EDGES)):
+        assert seed == S.first_edge_seed(j, g), (g, seed)
+        r = S.ransac(c["P1"], c["P2"], c["ip1"], c["ip2"], c["iterations"], c["threshold"], c["compute_scale"], c["seed"])
+        share = float(r["hyp"]["borderline"].mean())
+        print(f"{c['name']}: borderline share {share:.4f}, winner {r['best']}, {r['inliers']} inliers, groups at the best count {S.groups_at_best(r)}")
+        assert share <= 0.5 * S.BORDERLINE_CAP, (c["name"], share)
+        if g[5] in ("late", "cross_tie"):
+            assert r["best"] >= S.GROUP and S.winner_is_exact(r)
+        if g[5] == "cross_tie":
+            assert len(S.groups_at_best(r)) >= 2 and S.groups_at_best(r)[0] == r["best"] // S.GROUP
+
+
+def test_pinned_limits_of_the_kernel():
+    """The numbers the edge cases are built on, read from snake_slam_amd/csrc/sim3.hip: a moved carve fails here instead of leaving an
+    edge untested."""
+    src = (Path(__file__).resolve().parent.parent / "snake_slam_amd" / "csrc" / "sim3.hip").read_text()
+    one = lambda pattern: (lambda m: (len(m) == 1 and m[0]) or pytest.fail(f"{pattern}: {m}"))(re.findall(pattern, src))  # noqa: E731
+    assert int(one(r"constexpr int SIM3_MAX_PAIRS\s*=\s*(\d+);")) == S.MAX_PAIRS
+    assert int(one(r"constexpr int SIM3_LDS_PAIRS\s*=\s*(\d+);")) == S.LDS_PAIRS
+    assert int(one(r"for \(int k0 = 0; k0 < iterations; k0 \+= (\d+)\)")) == S.GROUP
+    assert int(one(r"__launch_bounds__\((\d+)\) void sim3_ransac_kernel")) == S.GROUP
+    per_pair, per_index = one(r"return \(size_t\)lds_pairs \* (\d+) \+ \(size_t\)idx_pairs \* (\d+);")
+    assert (int(per_pair), int(per_index)) == (S.BYTES_PER_PAIR, 8)
+    # the slab: ten doubles a pair, one slab_cap per problem
+    assert len(re.findall(r"slab \+ \(size_t\)b \* \(size_t\)slab_cap \* 10", src)) == 1
+    assert len(re.findall(r"\(size_t\)slab_cap \* 80 \+ 64", src)) == 2
+    assert "pairs per problem outside [0, 2048]" in src and "pairs_cap outside [1, 2048]" in src
