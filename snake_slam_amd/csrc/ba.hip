@@ -2124,7 +2124,6 @@ __global__ __launch_bounds__(256, SNK_BA_UC_WAVES) void update_cost(Arrays A, Op
 // A wavefront takes SUM_NB consecutive blocks of the window and walks their lists side by side (round 5: one block per wavefront was a
 // chain of three dependent memory round trips -- list bounds, list, partial sums -- for a handful of additions, 370 000 wavefronts per
 // launch of 1024 windows, half of them lower-triangle blocks that left at once).  The additions of a block keep the order of its list.
-constexpr int SUM_NB = 4;  // measured per 1024 windows: 1 block per wavefront 118 us, 4: 90 us, 8: 151 us (profiles/r05/r05Q_, r05R_)
 __global__ __launch_bounds__(256) void schur_sum(Arrays A, int nbx, int B)
 {
     int pb, bx;
@@ -2849,7 +2848,6 @@ __global__ __launch_bounds__(PCG_THREADS, 2) void pcg_small(Arrays A, Opt O)
 // per-workgroup partial sums combined in fixed order by every workgroup that needs them (deterministic,
 // no atomics).  One PCG iteration = 4 launches (matvec, combine, update, direction); convergence is
 // re-derived from the partial sums by every workgroup, the last launch of an iteration latches it.
-constexpr int PERSIST_WGS_MAX = 1024;
 // the grid barrier's words (grid_barrier_xcd); pcgl_init zeroes all BAR_WORDS of them before every PCG
 constexpr int BAR_PER_XCD = PERSIST_WGS_MAX / 8;      // arrival flags of group x at bar[x * BAR_PER_XCD + (workgroup >> 3)]
 constexpr int BAR_XFLAG   = PERSIST_WGS_MAX;          // the eight group flags, one 32-byte run
@@ -3163,8 +3161,6 @@ __device__ __forceinline__ double sum_partials_wave(const double* a, int n, int 
     return wave_sum64(t);
 }
 
-constexpr int PERSIST_THREADS = 256;
-constexpr int PERSIST_CAMS    = PERSIST_THREADS / 6;  // 42 cameras (252 elements) per workgroup in the update phase
 
 __global__ __launch_bounds__(PERSIST_THREADS) void pcgl_persist(Arrays A, Opt O, PcgLarge W)
 {
@@ -3536,7 +3532,6 @@ __global__ __launch_bounds__(PERSIST_THREADS) void pcgl_persist1(Arrays A, Opt O
 // r.r / r.z 0.7 us = 7.1 (pcgl_persist1: 15.3).  Also built and dropped: no barrier at all, exchange buffers whose entries validate
 // themselves (a NaN pattern = "not written yet", three buffers in turn) -- every workgroup then polls 15 KB at the memory side and
 // the wait costs what barrier + exchange cost (profiles/NOTES.md).
-constexpr int PREG_MAX_N6 = 2048;
 template <int R>
 __global__ __launch_bounds__(PERSIST_THREADS) void pcgl_persist_reg(Arrays A, Opt O, PcgLarge W)
 {
@@ -4106,7 +4101,6 @@ __global__ __launch_bounds__(64) void imp_latch(Arrays A, Opt O, PcgLarge W, int
 // the one-launch form (cooperative: all workgroups resident): the phases of an iteration separated by grid barriers, every
 // workgroup re-deriving the stop decisions from the same partial sums (pcgl_persist's scheme); a wavefront stands for one
 // 64-thread block of the multi-launch kernels
-constexpr int IMP_THREADS = 256;
 __global__ __launch_bounds__(IMP_THREADS) void imp_persist(Arrays A, Opt O, PcgLarge W)
 {
     const Prob pr  = A.prob[0];
@@ -4351,8 +4345,7 @@ Opt make_opt(const snk_ba_options& o)
 {
     Opt d;
     d.max_pcg      = o.max_pcg_iterations;
-    static const bool pcg_general = getenv("SNK_BA_PCG_GENERAL") != nullptr;
-    d.pcg_general  = pcg_general ? 1 : 0;
+    d.pcg_general  = ba_switches().pcg_general ? 1 : 0;
     d.pcg_tol      = o.pcg_tol;
     d.huber_mono   = o.huber_mono;
     d.huber_stereo = o.huber_stereo;
@@ -4446,164 +4439,131 @@ namespace snk
 {
 namespace ba
 {
-// Will the LM sequence of this problem set run the point-major kernels (schur_fused / schur_mfma + update_cost over the camera-set work
-// items)?  Decided by the hand-over's results and by switches that are read once per process: the hand-over asks too, because the
-// camera-pair block entries are only read by the block-major pass (schur_pass) -- building them for a 1024-window batch that never
-// runs it was 1.4 ms of device time behind every hand-over (block_entries_count 0.40 + block_entries_fill 1.03 ms, round 6 trace).
-bool ba_sets_will_run(const snk_ba* h)
+// Will the LM sequence of this problem set run the point-major kernels?  The rule is dispatch.hpp's ba_sets_will_run; the hand-over
+// asks through this, because it leaves out the camera-pair block entries on the same answer.
+bool ba_sets_will_run(const snk_ba* h) { return snk::ba_sets_will_run(ba_shape(h), ba_switches()); }
+
+namespace
 {
-    static const bool no_wave       = getenv("SNK_BA_NO_POINT_WAVE") != nullptr;
-    static const bool no_set        = getenv("SNK_BA_NO_SCHUR_SET") != nullptr;
-    static const long long set_min  = getenv("SNK_BA_SCHUR_SET_MIN_ITEMS") ? atoll(getenv("SNK_BA_SCHUR_SET_MIN_ITEMS")) : 256;
-    return h->max_nfc > 0 && h->point_wave_ok && !no_wave && h->set_ok && !no_set && (long long)h->max_set_items * h->count >= set_min;
+// Hands out arrays of doubles from one buffer in the order they are asked for; with a null base it only counts.  ba_plan_pcg walks
+// ONE field list twice with it -- to size d_pcgw, then to place the arrays -- so the byte count cannot drift from the pointers.
+struct Carver
+{
+    double* base;
+    size_t at = 0;
+    double* take(size_t n)
+    {
+        double* p = base ? base + at : nullptr;
+        at += n;
+        return p;
+    }
+};
+
+// The work arrays of the multi-workgroup PCG (dense) or of the implicit form's PCG: the vectors, the preconditioner blocks, ps (dense:
+// partial products; implicit: per-camera p.Ap), the partial sums of 64 cameras each, then the one-launch dense form's arrays or the
+// implicit point phase's y, and the grid barrier's words -- implicit: O(observations + keyframes), nothing (free cameras)^2.
+void carve_pcg(PcgLarge& W, Carver& c, bool imp, size_t nv, size_t n_cam, size_t n_ps, size_t ng, size_t n_scal, size_t npt)
+{
+    W.r    = c.take(nv);
+    W.z    = c.take(nv);
+    W.p    = c.take(nv);
+    W.Ap   = c.take(nv);
+    W.Minv = c.take(n_cam * 36);
+    W.ps   = c.take(n_ps);
+    W.prr  = c.take(2 * ng);
+    W.prz  = c.take(2 * ng);
+    W.ppap = c.take(ng);
+    W.scal = c.take(n_scal);
+    if (imp)
+        W.y = c.take(npt * 3);
+    else
+    {
+        W.p2   = c.take(nv);
+        W.wrr  = c.take(2 * (size_t)PERSIST_WGS_MAX);
+        W.wrz  = c.take(2 * (size_t)PERSIST_WGS_MAX);
+        W.wpap = c.take((size_t)PERSIST_WGS_MAX);
+    }
+    W.bar = reinterpret_cast<unsigned*>(c.take((size_t)PERSIST_WGS_MAX + 8));  // 2064 words >= BAR_WORDS
 }
 
+// The compute units of the handle's device when it offers cooperative launches, 0 when it does not.
+int cooperative_compute_units(const snk_ba* h)
+{
+    hipDeviceProp_t prop;
+    int coop = 0;
+    if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, h->device) != hipSuccess || !coop) return 0;
+    return prop.multiProcessorCount;
+}
+
+// Workgroups of `kernel` the runtime holds resident per compute unit with `lds` bytes of dynamic LDS (its limit raised to the persistent
+// forms' first when raise_lds); 0 when it refuses.  All workgroups of a cooperative launch must be resident at once (grid barriers
+// inside): asked of the runtime for this kernel's registers and THIS problem's LDS instead of assuming one (round-5 advisor) -- other
+// CU / LDS configurations, partitioned devices.
+int resident_per_cu(const void* kernel, int threads, size_t lds, bool raise_lds)
+{
+    int resident = 0;
+    if (raise_lds && set_max_lds_once(kernel, BA_PERSIST_LDS_MAX) != SNK_OK) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kernel, threads, lds) != hipSuccess) return 0;
+    return std::max(resident, 0);
+}
+}  // namespace
+
 // The PCG form of a problem set and its work arrays (the hand-over calls this once the set's totals are in the handle; it lives here,
-// beside the kernels whose occupancy it asks the runtime for).
+// beside the kernels whose occupancy it asks the runtime for).  The choice itself is dispatch.hpp's (ba_pcg_is_large, ba_persist_*).
 int ba_plan_pcg(snk_ba* h)
 {
-    const int count = h->count, max_n6 = h->max_n6, max_nfc = h->max_nfc, max_np = h->max_np, vec_off = h->tot_vec, cam_off = h->tot_cam;
-    const bool imp   = h->implicit;
-    const size_t npt = (size_t)std::max(h->tot_pt, 1);
+    const BaSwitches& sw = ba_switches();
+    const int count = h->count, max_n6 = h->max_n6, max_nfc = h->max_nfc;
+    const bool imp = h->implicit;
+    h->pcg_large   = ba_pcg_is_large(max_n6, max_nfc, imp);
+    PcgLarge& W    = h->pcgw;
+    W              = PcgLarge{};
     int rc;
-    const size_t pcg_lds = (size_t)max_n6 * 9 * 8 + (size_t)max_nfc * 36 * 8;
-    // S (and the vectors) of the largest problem fit one workgroup's LDS -> one workgroup per problem;
-    // otherwise the multi-workgroup PCG (measured: 120 keyframes 38 ms -> 9 ms, 600 keyframes 21 ms)
-    h->pcg_large = !imp && pcg_lds + (size_t)max_n6 * max_n6 * 8 > 158 * 1024;
-    if (h->pcg_large)
-    {
-        PcgLarge& W = h->pcgw;
-        W.G         = std::max(1, ceil_div(max_nfc, 64));
-        W.B         = count;
-        W.tot_vec   = vec_off;
-        // enough (row chunk x column part) workgroups to fill 256 CUs a few times over
-        const int rowchunks = std::max(1, ceil_div(max_n6, 256));
-        W.parts             = std::min(64, std::max(1, ceil_div(1024, rowchunks * count)));
-        const size_t nv = (size_t)std::max(vec_off, 1), ng = (size_t)count * W.G;
-        const size_t doubles = 4 * nv + (size_t)std::max(cam_off, 1) * 36 + (size_t)std::max(W.parts, PERSIST_WGS_MAX / rowchunks + 1) * nv + 5 * ng + (size_t)count * 4 +
-                               nv + 6 * (size_t)PERSIST_WGS_MAX + 8;
-        if ((rc = h->d_pcgw.reserve(doubles * 8)) != SNK_OK) return rc;
-        double* w = h->d_pcgw.as<double>();
-        W.r = w;            w += nv;
-        W.z = w;            w += nv;
-        W.p = w;            w += nv;
-        W.Ap = w;           w += nv;
-        W.Minv = w;         w += (size_t)std::max(cam_off, 1) * 36;
-        W.ps = w;           w += (size_t)std::max(W.parts, PERSIST_WGS_MAX / rowchunks + 1) * nv;
-        W.prr = w;          w += 2 * ng;
-        W.prz = w;          w += 2 * ng;
-        W.ppap = w;         w += ng;
-        W.scal = w;         w += (size_t)count * 4;
-        W.p2 = w;           w += nv;
-        W.wrr = w;          w += 2 * (size_t)PERSIST_WGS_MAX;
-        W.wrz = w;          w += 2 * (size_t)PERSIST_WGS_MAX;
-        W.wpap = w;         w += (size_t)PERSIST_WGS_MAX;
-        W.bar = reinterpret_cast<unsigned*>(w);  // (PERSIST_WGS_MAX + 8) doubles = 2064 words >= BAR_WORDS
-        W.bar_flat = getenv("SNK_BA_FLAT_BARRIER") != nullptr ? 1 : 0;
-        W.timing   = getenv("SNK_BA_PCG_TIMING") != nullptr ? 1 : 0;
-        // one problem, a cooperative launch the device can hold: two workgroups per compute unit (SNK_BA_PCGL_LAUNCHES=1: the
-        // multi-launch form, A/B and the fallback for batches of large problems)
-        W.persist_wgs = 0;
-        static const bool launches_env = getenv("SNK_BA_PCGL_LAUNCHES") != nullptr;
-        if (count == 1 && !launches_env)
-        {
-            hipDeviceProp_t prop;
-            int coop = 0, per_cu = 0;
-            if (hipGetDeviceProperties(&prop, h->device) == hipSuccess &&
-                hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, h->device) == hipSuccess && coop &&
-                (per_cu = 1) >= 1)
-            {
-                // one workgroup per compute unit: the barrier's cost grows with the participants (measured 7.0 ms per FullBA(4) with 256, 10.4 with 512)
-                // workgroups: a dozen rows of S each, at most one per compute unit -- the barrier's cost grows with the participants (FullBA(4) on 300
-                // keyframes, n6 = 1794: 5.0 / 4.6 / 5.9 / 5.0 ms with 256 / 128 / 64 / 32 workgroups, 10.4 with 512 in the three-barrier form)
-                const int wgs = std::min(PERSIST_WGS_MAX, snk_env_int("SNK_BA_PERSIST_WGS", std::min(prop.multiProcessorCount, std::max(16, ceil_div(max_n6, 12)))));
-                const bool fits = (size_t)max_n6 * 8 <= 150 * 1024 && ceil_div(max_nfc, PERSIST_CAMS) <= PERSIST_WGS_MAX;  // p in LDS; partial-sum slots
-                if (wgs >= 1 && fits && set_max_lds_once(reinterpret_cast<const void*>(pcgl_persist), 150 * 1024) == SNK_OK)
-                {
-                    // all workgroups must be resident at once (grid barriers inside): ask the runtime what this kernel's registers and THIS
-                    // problem's LDS allow per compute unit instead of assuming one (round-5 advisor) -- other CU / LDS configurations,
-                    // partitioned devices
-                    int resident = 0;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, reinterpret_cast<const void*>(pcgl_persist), PERSIST_THREADS, (size_t)max_n6 * 8) == hipSuccess &&
-                        resident >= 1)
-                        W.persist_wgs = std::min(wgs, resident * prop.multiProcessorCount);
-                    // the one-barrier form needs 3 n6 doubles of LDS (SNK_BA_PERSIST_TWO_BARRIERS=1: A/B, the round-5 form)
-                    W.persist_one = 0;
-                    if (W.persist_wgs > 0 && (size_t)max_n6 * 24 <= 150 * 1024 && getenv("SNK_BA_PERSIST_TWO_BARRIERS") == nullptr &&
-                        set_max_lds_once(reinterpret_cast<const void*>(pcgl_persist1), 150 * 1024) == SNK_OK &&
-                        hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, reinterpret_cast<const void*>(pcgl_persist1), PERSIST_THREADS, (size_t)max_n6 * 24) == hipSuccess &&
-                        resident >= 1 && resident * prop.multiProcessorCount >= W.persist_wgs)
-                        W.persist_one = 1;
-                    // ... and with S in registers when the system is small enough (8 rows x 2048 columns per workgroup, one workgroup per 8 rows)
-                    // 16 rows per workgroup above 512 unknowns (the barrier and the exchange of A p grow with the workgroups: 225 against 113
-                    // for 300 keyframes: 9.4 -> 7.1 us per PCG iteration; 90 against 45 for 120 keyframes: 6.45 -> 5.7), 8 below; SNK_BA_PERSIST_REG_ROWS / _THREADS: A/B
-                    static const int rows_env = snk_env_int("SNK_BA_PERSIST_REG_ROWS", 0);
-                    const int reg_rows     = rows_env == 8 || rows_env == 16 ? rows_env : (max_n6 > 512 ? 16 : 8);
-                    const void* reg_kernel = persist_reg_kernel(reg_rows);
-                    const int wgs_reg = ceil_div(std::max(max_n6, 1), reg_rows);
-                    if (W.persist_one == 1 && max_n6 <= PREG_MAX_N6 && getenv("SNK_BA_PERSIST_STREAM") == nullptr && getenv("SNK_BA_PERSIST_WGS") == nullptr &&
-                        set_max_lds_once(reg_kernel, 150 * 1024) == SNK_OK &&
-                        hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, reg_kernel, PERSIST_THREADS, (size_t)max_n6 * 16) == hipSuccess &&
-                        resident >= 1 && resident * prop.multiProcessorCount >= wgs_reg && wgs_reg <= PERSIST_WGS_MAX)
-                    {
-                        W.persist_rows = reg_rows;
-                        W.persist_one = 2;
-                        W.persist_wgs = wgs_reg;
-                    }
-                }
-            }
-            (void)hipGetLastError();
-        }
-    }
-    else if (imp)
-    {
-        // the implicit form's PCG (imp_*): the vectors, the preconditioner blocks, the point phase's y, per-camera p.Ap, the
-        // partial sums of 64 cameras each and the grid barrier's words -- O(observations + keyframes), nothing (free cameras)^2
-        PcgLarge& W = h->pcgw;
-        W         = PcgLarge{};
-        W.G       = std::max(1, ceil_div(max_nfc, 64));
-        W.B       = 1;
-        W.parts   = 1;
-        W.tot_vec = vec_off;
-        const size_t nv = (size_t)std::max(vec_off, 1), ng = (size_t)W.G;
-        const size_t doubles = 4 * nv + (size_t)std::max(cam_off, 1) * 36 + (size_t)std::max(cam_off, 1) + 5 * ng + 4 + npt * 3 +
-                               (size_t)PERSIST_WGS_MAX + 8;
-        if ((rc = h->d_pcgw.reserve(doubles * 8)) != SNK_OK) return rc;
-        double* w = h->d_pcgw.as<double>();
-        W.r = w;     w += nv;
-        W.z = w;     w += nv;
-        W.p = w;     w += nv;
-        W.Ap = w;    w += nv;
-        W.Minv = w;  w += (size_t)std::max(cam_off, 1) * 36;
-        W.ps = w;    w += (size_t)std::max(cam_off, 1);
-        W.prr = w;   w += 2 * ng;
-        W.prz = w;   w += 2 * ng;
-        W.ppap = w;  w += ng;
-        W.scal = w;  w += 4;
-        W.y = w;     w += npt * 3;
-        W.bar = reinterpret_cast<unsigned*>(w);  // (PERSIST_WGS_MAX + 8) doubles = 2064 words >= BAR_WORDS
-        // one cooperative launch when every workgroup can be resident (SNK_BA_PCGL_LAUNCHES=1 or a refused launch: the multi-launch form);
-        // enough workgroups for a point per thread or a camera per wavefront, at most one per compute unit (the barrier's cost grows with them)
-        W.persist_wgs = 0;
-        static const bool launches_env = getenv("SNK_BA_PCGL_LAUNCHES") != nullptr;
-        hipDeviceProp_t prop;
-        int coop = 0, resident = 0;
-        if (!launches_env && max_nfc > 0 && hipGetDeviceProperties(&prop, h->device) == hipSuccess &&
-            hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, h->device) == hipSuccess && coop &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, reinterpret_cast<const void*>(imp_persist), IMP_THREADS, 0) == hipSuccess && resident >= 1)
-        {
-            const int want = std::max(16, std::max(ceil_div(max_np, IMP_THREADS), ceil_div(max_nfc, IMP_THREADS / 64)));
-            const int wgs  = std::min(PERSIST_WGS_MAX, snk_env_int("SNK_BA_PERSIST_WGS", std::min(prop.multiProcessorCount, want)));
-            W.persist_wgs  = std::min(wgs, resident * prop.multiProcessorCount);
-        }
-        (void)hipGetLastError();
-    }
     if (!h->pcg_large)
     {
-        // process-wide, once, to the most the kernels can use (enqueue_lm keeps S in LDS only when it fits 158 KB)
-        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pcg_solve<true>), 158 * 1024)) != SNK_OK) return rc;
-        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pcg_solve<false>), 158 * 1024)) != SNK_OK) return rc;
+        // process-wide, once, to the most the kernels can use (S stays in LDS only when it fits BA_PCG_LDS_MAX)
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pcg_solve<true>), BA_PCG_LDS_MAX)) != SNK_OK) return rc;
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pcg_solve<false>), BA_PCG_LDS_MAX)) != SNK_OK) return rc;
+        if (!imp) return SNK_OK;  // one workgroup per problem: no work arrays
     }
+    W.G       = std::max(1, ceil_div(max_nfc, 64));
+    W.B       = imp ? 1 : count;
+    W.tot_vec = h->tot_vec;
+    // dense: enough (row chunk x column part) workgroups to fill 256 CUs a few times over
+    const int rowchunks = std::max(1, ceil_div(max_n6, 256));
+    W.parts             = imp ? 1 : std::min(64, std::max(1, ceil_div(1024, rowchunks * count)));
+    const size_t nv = (size_t)std::max(h->tot_vec, 1), n_cam = (size_t)std::max(h->tot_cam, 1), ng = (size_t)W.B * W.G;
+    const size_t n_ps = imp ? n_cam : (size_t)std::max(W.parts, PERSIST_WGS_MAX / rowchunks + 1) * nv;
+    const size_t n_scal = (size_t)W.B * 4, npt = (size_t)std::max(h->tot_pt, 1);
+    Carver sizing{nullptr};
+    carve_pcg(W, sizing, imp, nv, n_cam, n_ps, ng, n_scal, npt);
+    if ((rc = h->d_pcgw.reserve(sizing.at * 8)) != SNK_OK) return rc;
+    Carver placing{h->d_pcgw.as<double>()};
+    carve_pcg(W, placing, imp, nv, n_cam, n_ps, ng, n_scal, npt);
+    // One cooperative launch when every workgroup can be resident (SNK_BA_PCGL_LAUNCHES=1, a batch of large problems or a refused
+    // launch: the multi-launch form).  The runtime is asked only what the sizes leave open.
+    const bool tried = imp ? !sw.pcgl_launches && max_nfc > 0 : ba_persist_tried(count, sw);
+    const int n_cu   = tried ? cooperative_compute_units(h) : 0;
+    BaPersist P;
+    if (imp)
+    {
+        const int res = n_cu > 0 ? resident_per_cu(reinterpret_cast<const void*>(imp_persist), IMP_THREADS, 0, false) : 0;
+        P             = ba_persist_implicit(h->max_np, max_nfc, n_cu > 0, n_cu, res, sw);
+    }
+    else
+    {
+        W.bar_flat = sw.flat_barrier ? 1 : 0;
+        W.timing   = sw.pcg_timing ? 1 : 0;
+        const void* reg_kernel = persist_reg_kernel(ba_persist_reg_rows(max_n6, sw));
+        int res0 = 0, res1 = 0, res2 = 0;
+        if (n_cu > 0 && ba_persist_fits(max_n6, max_nfc)) res0 = resident_per_cu(reinterpret_cast<const void*>(pcgl_persist), PERSIST_THREADS, (size_t)max_n6 * 8, true);
+        if (res0 >= 1 && ba_persist1_fits(max_n6, sw)) res1 = resident_per_cu(reinterpret_cast<const void*>(pcgl_persist1), PERSIST_THREADS, (size_t)max_n6 * 24, true);
+        if (res1 >= 1 && ba_persist_reg_fits(max_n6, sw)) res2 = resident_per_cu(reg_kernel, PERSIST_THREADS, (size_t)max_n6 * 16, true);
+        P = ba_persist_dense(count, max_n6, max_nfc, n_cu > 0, n_cu, res0, res1, res2, sw);
+    }
+    if (tried || imp) (void)hipGetLastError();
+    W.persist_wgs = P.wgs, W.persist_one = P.one, W.persist_rows = P.rows;
     return SNK_OK;
 }
 }  // namespace ba
@@ -4671,20 +4631,19 @@ int snk_ba_pcg_form(const snk_ba* h, int* form, int* workgroups)
 {
     SNK_REQUIRE(h != nullptr && form != nullptr && workgroups != nullptr, "bad arguments");
     SNK_REQUIRE(h->count > 0, "no problem set");
-    const PcgLarge& W = h->pcgw;
-    if (h->implicit)
+    const BaPcgForm f = ba_pcg_form(ba::ba_shape(h), ba::ba_switches(), false);
+    switch (f)
     {
-        if (W.persist_wgs > 0)
-            *form = SNK_BA_PCG_IMPLICIT, *workgroups = W.persist_wgs;
-        else
-            *form = SNK_BA_PCG_IMPLICIT_LAUNCHES, *workgroups = 0;
+    case BaPcgForm::imp_persist: *form = SNK_BA_PCG_IMPLICIT; break;
+    case BaPcgForm::imp_launches: *form = SNK_BA_PCG_IMPLICIT_LAUNCHES; break;
+    case BaPcgForm::launches: *form = SNK_BA_PCG_LAUNCHES; break;
+    case BaPcgForm::persist_reg16:
+    case BaPcgForm::persist_reg8: *form = SNK_BA_PCG_PERSIST_REG; break;
+    case BaPcgForm::persist1: *form = SNK_BA_PCG_PERSIST1; break;
+    case BaPcgForm::persist: *form = SNK_BA_PCG_PERSIST; break;
+    default: *form = SNK_BA_PCG_PER_PROBLEM; break;  // pcg_small, pcg_solve
     }
-    else if (!h->pcg_large)
-        *form = SNK_BA_PCG_PER_PROBLEM, *workgroups = 0;
-    else if (W.persist_wgs <= 0 || h->count != 1)
-        *form = SNK_BA_PCG_LAUNCHES, *workgroups = 0;
-    else
-        *form = W.persist_one == 2 ? SNK_BA_PCG_PERSIST_REG : W.persist_one == 1 ? SNK_BA_PCG_PERSIST1 : SNK_BA_PCG_PERSIST, *workgroups = W.persist_wgs;
+    *workgroups = ba_pcg_is_cooperative(f) ? h->pcgw.persist_wgs : 0;
     return SNK_OK;
 }
 
@@ -4720,13 +4679,211 @@ int snk_ba_reset(snk_ba* h)
     return SNK_OK;
 }
 
-constexpr int BA_GRAPH_CHAINS = 1;  // chains a recorded batch sequence is split into by default (measured: see enqueue_lm)
+// ---- the LM launch sequence.  Which kernel form each stage takes is dispatch.hpp's ba_lm_plan; the stage functions below switch over
+// the plan and do nothing but launch. ----
+// What a stage needs: the handle, the launcher, the plan, and the arrays and window count of the chain it launches for.
+struct LmStage
+{
+    snk_ba* h;
+    Launcher& L;
+    const BaSwitches& sw;
+    const Opt& O;
+    const BaLmPlan& P;
+    Arrays A;
+    int B;
+    dim3 grid_sets() const { return dim3(P.nsx * 8 * ceil_div(B, 8)); }  // the point-major kernels: windows of an XCD side by side
+    dim3 grid_points() const { return dim3(std::max(1, ceil_div(h->max_np, 128)), B); }
+};
+
+static void lm_linearise(const LmStage& c)
+{
+    Launcher& L = c.L;
+    switch (c.P.lin)
+    {
+    // linearisation + Schur products in one kernel (W stays in LDS); it writes what point_wave writes per point
+    case BaLinForm::fused3_sums: LAUNCH((schur_fused<3, true>), c.grid_sets(), dim3(256), 0, c.A, c.O, c.P.nsx, c.B); break;
+    case BaLinForm::fused3: LAUNCH((schur_fused<3, false>), c.grid_sets(), dim3(256), 0, c.A, c.O, c.P.nsx, c.B); break;
+    case BaLinForm::fused4: LAUNCH((schur_fused<4, false>), c.grid_sets(), dim3(256), 0, c.A, c.O, c.P.nsx, c.B); break;
+    case BaLinForm::point_wave: LAUNCH(point_wave, dim3(c.h->max_wv, c.B), dim3(64), 0, c.A, c.O); break;
+    case BaLinForm::point_pass: LAUNCH(point_pass<0>, c.grid_points(), dim3(128), 0, c.A, c.O); break;
+    }
+}
+
+static void lm_camera_pass(const LmStage& c)
+{
+    Launcher& L      = c.L;
+    const snk_ba* h  = c.h;
+    if (c.P.cam != BaCamForm::none && h->max_rpc > 0) LAUNCH(rpc_pass, dim3(ceil_div(h->max_rpc, 64), c.B), dim3(64), 0, c.A, 0);
+    switch (c.P.cam)
+    {
+    case BaCamForm::none: break;
+    case BaCamForm::cam_sum: LAUNCH(cam_sum, dim3(h->max_nfc, c.B), dim3(64), 0, c.A); break;
+    case BaCamForm::cam64_xcd: LAUNCH(cam_pass<64>, dim3(8 * h->max_nfc * ceil_div(c.B, 8)), dim3(64), 0, c.A, c.O, h->max_nfc, c.B); break;
+    case BaCamForm::cam64_2d: LAUNCH(cam_pass<64>, dim3(h->max_nfc, c.B), dim3(64), 0, c.A, c.O, 0, c.B); break;
+    case BaCamForm::cam256: LAUNCH(cam_pass<256>, dim3(h->max_nfc, c.B), dim3(256), 0, c.A, c.O, 0, c.B); break;
+    }
+}
+
+static void lm_schur(const LmStage& c)
+{
+    Launcher& L      = c.L;
+    const BaLmPlan& P = c.P;
+    const int nb     = c.h->max_nfc * c.h->max_nfc;
+    const int zr     = P.zero_rows ? 1 : 0;
+    switch (P.schur)
+    {
+    case BaSchurForm::none: return;      // no S: the implicit PCG works from W, V^-1 and U
+    case BaSchurForm::in_fused: break;   // the partial sums are there already
+    case BaSchurForm::mfma32: LAUNCH((schur_mfma<3, 2>), c.grid_sets(), dim3(256), 0, c.A, P.nsx, c.B); break;
+    case BaSchurForm::mfma33: LAUNCH((schur_mfma<3, 3>), c.grid_sets(), dim3(256), 0, c.A, P.nsx, c.B); break;
+    case BaSchurForm::mfma43: LAUNCH((schur_mfma<4, 3>), c.grid_sets(), dim3(256), 0, c.A, P.nsx, c.B); break;
+    case BaSchurForm::set42: LAUNCH((schur_set<4, 2>), c.grid_sets(), dim3(256), 0, c.A, P.nsx, c.B); break;
+    case BaSchurForm::set63: LAUNCH((schur_set<6, 3>), c.grid_sets(), dim3(256), 0, c.A, P.nsx, c.B); break;
+    case BaSchurForm::pass4: LAUNCH(schur_pass<4>, dim3(nb * c.B), dim3(256), 0, c.A, zr, nb, c.B); return;
+    case BaSchurForm::pass1: LAUNCH(schur_pass<1>, dim3(P.nbx * 8 * ceil_div(c.B, 8)), dim3(256), 0, c.A, zr, P.nbx, c.B); return;
+    }
+    LAUNCH(schur_sum, dim3(P.nbs * 8 * ceil_div(c.B, 8)), dim3(256), 0, c.A, P.nbs, c.B);  // the point-major forms leave partial sums
+}
+
+// What the PCG forms of a family share and launch first: the preconditioner and the start vectors.
+static void lm_pcg_init(const LmStage& c, const PcgLarge& W)
+{
+    Launcher& L = c.L;
+    switch (c.P.pcg)
+    {
+    case BaPcgForm::imp_persist:
+    case BaPcgForm::imp_launches:
+        LAUNCH(imp_precond, dim3(c.h->max_nfc), dim3(64), 0, c.A, W);
+        LAUNCH(imp_init, dim3(W.G), dim3(64), 0, c.A, c.O, W);
+        break;
+    case BaPcgForm::persist_reg16:
+    case BaPcgForm::persist_reg8:
+    case BaPcgForm::persist1:
+    case BaPcgForm::persist:
+    case BaPcgForm::launches: LAUNCH(pcgl_init, dim3(W.G, c.B), dim3(64), 0, c.A, c.O, W); break;
+    default: break;
+    }
+}
+
+static void lm_pcg_solve(const LmStage& c, const PcgLarge& W)
+{
+    Launcher& L      = c.L;
+    const snk_ba* h  = c.h;
+    const size_t lds = c.P.pcg_lds;
+    const dim3 gcam(W.G, c.B);
+    switch (c.P.pcg)
+    {
+    case BaPcgForm::none: break;
+    case BaPcgForm::small: LAUNCH(pcg_small, dim3(c.B), dim3(PCG_THREADS), lds, c.A, c.O); break;
+    case BaPcgForm::solve_lds: LAUNCH(pcg_solve<true>, dim3(c.B), dim3(PCG_THREADS), lds, c.A, c.O); break;
+    case BaPcgForm::solve_global: LAUNCH(pcg_solve<false>, dim3(c.B), dim3(PCG_THREADS), lds, c.A, c.O); break;
+    case BaPcgForm::persist_reg16: LAUNCH(pcgl_persist_reg<16>, dim3(W.persist_wgs), dim3(PERSIST_THREADS), lds, c.A, c.O, W); break;
+    case BaPcgForm::persist_reg8: LAUNCH(pcgl_persist_reg<8>, dim3(W.persist_wgs), dim3(PERSIST_THREADS), lds, c.A, c.O, W); break;
+    case BaPcgForm::persist1: LAUNCH(pcgl_persist1, dim3(W.persist_wgs), dim3(PERSIST_THREADS), lds, c.A, c.O, W); break;
+    case BaPcgForm::persist: LAUNCH(pcgl_persist, dim3(W.persist_wgs), dim3(PERSIST_THREADS), lds, c.A, c.O, W); break;
+    case BaPcgForm::imp_persist: LAUNCH(imp_persist, dim3(W.persist_wgs), dim3(IMP_THREADS), lds, c.A, c.O, W); break;
+    case BaPcgForm::launches:
+        for (int k = 0; k < c.O.max_pcg; ++k)
+        {
+            LAUNCH(pcgl_matvec, dim3(ceil_div(h->max_n6, 256) * W.parts, c.B), dim3(256), 0, c.A, c.O, W, k);
+            LAUNCH(pcgl_combine, gcam, dim3(64), 0, c.A, c.O, W, k);
+            LAUNCH(pcgl_update, gcam, dim3(64), 0, c.A, c.O, W, k);
+            LAUNCH(pcgl_direction, gcam, dim3(64), 0, c.A, c.O, W, k);
+            LAUNCH(pcgl_latch, dim3(ceil_div(c.B, 64)), dim3(64), 0, c.A, c.O, W, k);
+        }
+        break;
+    case BaPcgForm::imp_launches:
+        for (int k = 0; k < c.O.max_pcg; ++k)
+        {
+            LAUNCH(imp_point, dim3(std::max(1, ceil_div(h->max_np, 256))), dim3(256), 0, c.A, c.O, W, k);
+            LAUNCH(imp_cam, dim3(h->max_nfc), dim3(64), 0, c.A, c.O, W, k);
+            LAUNCH(imp_update, dim3(W.G), dim3(64), 0, c.A, c.O, W, k);
+            LAUNCH(imp_direction, dim3(W.G), dim3(64), 0, c.A, c.O, W, k);
+            LAUNCH(imp_latch, dim3(1), dim3(64), 0, c.A, c.O, W, k);
+        }
+        break;
+    }
+}
+
+// Tries the plan's cooperative PCG launch, dense or implicit (SNK_BA_PERSIST_FAIL=1, tests: as if the runtime refused it).  False: the
+// runtime refused -- co-residency under another CU / LDS configuration, a partitioned device, a driver without cooperative queues.
+// Nothing ran then, and the state the init kernels left is what the multi-launch sequence starts from too; the error is cleared and
+// the handle remembers: the rest of this solve and every later one takes the multi-launch form.
+static bool lm_try_cooperative(const LmStage& c, const PcgLarge& W)
+{
+    Launcher& L = c.L;
+    if (L.err != hipSuccess) return false;  // an earlier launch failed: nothing more is issued, enqueue_lm reports it
+    if (c.sw.persist_fail)
+        L.err = hipErrorCooperativeLaunchTooLarge;
+    else
+    {
+        L.cooperative = true;
+        lm_pcg_solve(c, W);
+    }
+    if (L.err == hipSuccess) return true;
+    if (c.sw.debug)
+        fprintf(stderr, "snake_hip: cooperative %sPCG launch refused (%s); multi-launch PCG\n", c.h->implicit ? "implicit " : "", hipGetErrorString(L.err));
+    (void)hipGetLastError();
+    L.err                  = hipSuccess;
+    c.h->pcgw.persist_wgs = 0;
+    return false;
+}
+
+static void lm_update_and_cost(const LmStage& c)
+{
+    Launcher& L     = c.L;
+    const snk_ba* h = c.h;
+    const int gwv   = ceil_div(h->max_wv, 4);
+    switch (c.P.update)
+    {
+    case BaUpdateForm::update_cost:
+        // the work items of the set cover every point that has observations (schur_fused's linearisation-only items included)
+        LAUNCH(update_pass, dim3(std::max(1, ceil_div(h->max_ni, 128)), c.B), dim3(128), 0, c.A, 1);
+        LAUNCH(update_cost, c.grid_sets(), dim3(256), 0, c.A, c.O, c.P.nsx, c.B);
+        break;
+    case BaUpdateForm::update_wave:
+        LAUNCH(update_wave, dim3(gwv + std::max(1, ceil_div(h->max_ni, 256)), c.B), dim3(256), 0, c.A, c.O, gwv);
+        LAUNCH(cost_wave, dim3(gwv, c.B), dim3(256), 0, c.A, c.O);
+        break;
+    case BaUpdateForm::update_point:
+        LAUNCH(update_pass, dim3(std::max(1, ceil_div(h->max_np + h->max_ni, 128)), c.B), dim3(128), 0, c.A, 0);
+        LAUNCH(point_pass<1>, c.grid_points(), dim3(128), 0, c.A, c.O);
+        break;
+    }
+    if (h->max_rpc > 0 && h->max_nfc > 0) LAUNCH(rpc_pass, dim3(ceil_div(h->max_rpc, 64), c.B), dim3(64), 0, c.A, 1);
+}
+
+static void lm_accept(const LmStage& c, int cond)
+{
+    Launcher& L     = c.L;
+    const snk_ba* h = c.h;
+    const int split = c.P.split_copy ? 1 : 0;  // the copy of the accepted state on its own workgroups (one workgroup per problem otherwise)
+    LAUNCH(accept_pass, dim3(c.B), dim3(ACC_THREADS), split ? 2 * ACC_TILE * sizeof(double) : 0, c.A, cond, split, split);
+    if (split) LAUNCH(accept_copy, dim3(std::min(128, ceil_div(h->max_np * 3 + h->max_ni * 7, 512)), c.B), dim3(256), 0, c.A, cond);
+}
+
 static int enqueue_lm(snk_ba* h, int iterations, Launcher& L, bool only_marked = false)
 {
     const Opt O = make_opt(h->opt);
+    BaSwitches sw = ba::ba_switches();
+    sw.debug      = getenv("SNK_DEBUG") != nullptr;  // read at every call: a test switches it on inside its process
+    const bool recording = L.graph != nullptr;
+    BaShape S  = ba::ba_shape(h);
+    BaLmPlan P = ba_lm_plan(S, sw, recording);  // once per call; only a refused cooperative launch re-plans (the PCG stage)
+    if (sw.debug)
+        fprintf(stderr, "snake_hip: ba lm B=%d imp=%d n6=%d nfc=%d np=%d ni=%d wv=%d rpc=%d items=%d set_ok=%d small=%d k=%d run=%d wave_ok=%d sums_ok=%d blk=%d "
+                        "pwgs=%d pone=%d prows=%d rec=%d lin=%s cam=%s schur=%s pcg=%s update=%s chains=%d\n",
+                S.count, (int)S.implicit, S.max_n6, S.max_nfc, S.max_np, S.max_ni, S.max_wv, S.max_rpc, S.max_set_items, (int)S.set_ok, (int)S.set_small,
+                S.set_k_max, S.set_run_max, (int)S.point_wave_ok, (int)S.cam_sums_ok, (int)S.blk_built, S.persist_wgs, S.persist_one, S.persist_rows,
+                (int)recording, ba_name(P.lin), ba_name(P.cam), ba_name(P.schur), ba_name(P.pcg), ba_name(P.update), P.n_chain);
+    if (P.no_block_lists && iterations > 0)
+    {
+        set_error("bundle adjustment: the block-major pass was chosen but the hand-over did not build its lists (internal)");
+        return SNK_ERR_HIP;
+    }
     const int B_all = h->count;
     Arrays A_all    = h->arr;
-    const int cond = only_marked ? 1 : 0;
+    const int cond  = only_marked ? 1 : 0;
     if (only_marked)
     {
         int rc = h->d_probcond.reserve((size_t)B_all * sizeof(Prob));
@@ -4735,239 +4892,47 @@ static int enqueue_lm(snk_ba* h, int iterations, Launcher& L, bool only_marked =
                O.lambda_init);
         A_all.prob = h->d_probcond.as<Prob>();
     }
-    else if (h->state_fresh && L.graph == nullptr)
+    else if (h->state_fresh && !recording)
         ;  // the first solve after a hand-over: the uploaded state IS what begin_solve writes (one launch less on the keyframe path)
     else
         LAUNCH(begin_solve, dim3(ceil_div(B_all, 64)), dim3(64), 0, h->d_state.as<State>(), B_all, O.lambda_init, 0);
-    if (L.graph == nullptr) h->state_fresh = false;
+    if (!recording) h->state_fresh = false;
     // A recorded sequence of a big batch is recorded as SEVERAL chains over disjoint ranges of the windows (windows are independent; a
     // kernel finds its window through A.prob / A.state only, so a range is those two pointers moved): the graph's branches run side by
     // side, and the latency-bound kernels of one range (pcg_small: one workgroup per window walking its PCG iterations; schur_sum; accept_pass)
     // fill the issue slots the bandwidth-bound ones of another leave.  Same kernels, same arithmetic per window.  SNK_BA_GRAPH_CHAINS=n.
-    static const int chains_env = getenv("SNK_BA_GRAPH_CHAINS") ? atoi(getenv("SNK_BA_GRAPH_CHAINS")) : 0;
-    int n_chain = 1;
-    if (L.graph != nullptr && !h->pcg_large && B_all >= 128) n_chain = chains_env > 0 ? std::min(chains_env, B_all / 64) : BA_GRAPH_CHAINS;
     hipGraphNode_t const root = L.last;
-    for (int chain = 0; chain < n_chain; ++chain)
+    for (int chain = 0; chain < P.n_chain; ++chain)
     {
-    const int b_lo = chain == 0 ? 0 : ((int)((long long)B_all * chain / n_chain) & ~7);
-    const int b_hi = chain == n_chain - 1 ? B_all : ((int)((long long)B_all * (chain + 1) / n_chain) & ~7);
-    const int B    = b_hi - b_lo;
-    Arrays A       = A_all;
-    A.prob += b_lo;
-    A.state += b_lo;
-    L.last = root;
-    const dim3 gpt(std::max(1, ceil_div(h->max_np, 128)), B);
-    size_t pcg_lds        = (size_t)h->max_n6 * 9 * 8 + (size_t)h->max_nfc * 36 * 8;
-    const size_t s_bytes  = (size_t)h->max_n6 * h->max_n6 * 8;
-    // + 128 doubles read padding behind S (rows lane and lane + 64 are read unmasked) + [2][4][128] partial products
-    const int s_in_lds    = pcg_lds + s_bytes + 1024 + 8192 <= 158 * 1024 ? 1 : 0;
-    if (s_in_lds) pcg_lds += s_bytes + 1024 + 8192;
-    for (int it = 0; it < iterations; ++it)
-    {
-        static const bool no_wave = getenv("SNK_BA_NO_POINT_WAVE") != nullptr;
-        // (SNK_BA_NO_SCHUR_SET, SNK_BA_SCHUR_SET_MIN_ITEMS: ba_sets_will_run -- a single small window has too few work items to fill the
-        // chip, the block-major pass is quicker there)
-        static const bool no_mfma  = getenv("SNK_BA_NO_SCHUR_MFMA") != nullptr;   // A/B: the vector-ALU form (schur_set)
-        static const bool no_fused = getenv("SNK_BA_NO_SCHUR_FUSED") != nullptr;  // A/B: point_wave + schur_mfma through W in HBM
-        // (the whole batch decides, not the range of a chain: the hand-over left out the block entries on the same answer)
-        const bool use_set = !h->implicit && ba_sets_will_run(h);
-        if (!use_set && !h->blk_built && !h->implicit)
+        const int b_lo = chain == 0 ? 0 : ((int)((long long)B_all * chain / P.n_chain) & ~7);
+        const int b_hi = chain == P.n_chain - 1 ? B_all : ((int)((long long)B_all * (chain + 1) / P.n_chain) & ~7);
+        LmStage c{h, L, sw, O, P, A_all, b_hi - b_lo};
+        c.A.prob += b_lo;
+        c.A.state += b_lo;
+        L.last = root;
+        for (int it = 0; it < iterations; ++it)
         {
-            set_error("bundle adjustment: the block-major pass was chosen but the hand-over did not build its lists (internal)");
-            return SNK_ERR_HIP;
-        }
-        // points with 9 or 10 free observations need a fourth tile row: 260 registers, one wavefront per SIMD -- there the
-        // linearisation stays in point_wave and schur_mfma<4> reads W (measured on the 300-keyframe global BA: 14.7 vs 15.5 ms);
-        // SNK_BA_FUSED_K10=1 forces the fused form (tests)
-        static const bool fused_k10 = getenv("SNK_BA_FUSED_K10") != nullptr;
-        const bool fused   = use_set && !no_mfma && !no_fused && (h->set_k_max <= 8 || fused_k10);
-        const int nsx      = ceil_div(std::max(h->max_set_items, 1), 4);
-        // SNK_BA_CAM_SUMS=1: the camera pass as per-item partial sums out of schur_fused<3, true> + cam_sum instead of cam_pass.
-        // Built because cam_pass linearises every observation a second time (294 us per 1024 windows); measured: schur_fused
-        // 1127 -> 1437 us for the five passes through the contribution buffer, cam_sum 29 us -- 46 us SLOWER per LM iteration
-        // (profiles/r03/r03aa_*).  Kept selectable and tested, not the default.
-        static const bool want_cam_sums = getenv("SNK_BA_CAM_SUMS") != nullptr;
-        const bool cam_sums = fused && h->set_k_max <= 8 && h->cam_sums_ok && want_cam_sums;
-        if (fused)
-        {
-            // linearisation + Schur products in one kernel (W stays in LDS); it writes what point_wave writes per point
-            if (h->set_k_max <= 8 && cam_sums)
-                LAUNCH((schur_fused<3, true>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, O, nsx, B);
-            else if (h->set_k_max <= 8)
-                LAUNCH((schur_fused<3, false>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, O, nsx, B);
-            else
-                LAUNCH((schur_fused<4, false>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, O, nsx, B);
-        }
-        else if (h->point_wave_ok && !no_wave)
-            LAUNCH(point_wave, dim3(h->max_wv, B), dim3(64), 0, A, O);
-        else
-            LAUNCH(point_pass<0>, gpt, dim3(128), 0, A, O);
-        if (h->max_nfc > 0)
-        {
-            if (h->max_rpc > 0) LAUNCH(rpc_pass, dim3(ceil_div(h->max_rpc, 64), B), dim3(64), 0, A, 0);
-            if (cam_sums)
-                LAUNCH(cam_sum, dim3(h->max_nfc, B), dim3(64), 0, A);
-            else if (B >= 16)
-            {
-                static const bool cam_2d = getenv("SNK_BA_CAM_GRID_2D") != nullptr;  // A/B: the round-1..4 grid (cameras of a window over all XCDs)
-                if (cam_2d) LAUNCH(cam_pass<64>, dim3(h->max_nfc, B), dim3(64), 0, A, O, 0, B);
-                else LAUNCH(cam_pass<64>, dim3(8 * h->max_nfc * ceil_div(B, 8)), dim3(64), 0, A, O, h->max_nfc, B);
-            }
-            else
-                LAUNCH(cam_pass<256>, dim3(h->max_nfc, B), dim3(256), 0, A, O, 0, B);
-            if (h->implicit)
-                ;  // no S: the implicit PCG below works from W, V^-1 and U
-            else
-            {
-                const int nbx = ceil_div(h->max_nfc * h->max_nfc, 4);  // schur_pass: a block per wavefront
-                const int nbs = ceil_div(h->max_nfc * h->max_nfc, 4 * SUM_NB);  // schur_sum: SUM_NB blocks per wavefront
-                if (use_set)
-                {
-                    const bool q2 = h->set_run_max * 9 + 3 <= 2 * 64;
-                    if (fused)
-                        ;  // the partial sums are there already
-                    else if (!no_mfma && h->set_k_max <= 8)
-                    {
-                        if (q2) LAUNCH((schur_mfma<3, 2>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, nsx, B);
-                        else LAUNCH((schur_mfma<3, 3>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, nsx, B);
-                    }
-                    else if (!no_mfma)
-                        LAUNCH((schur_mfma<4, 3>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, nsx, B);
-                    else if (h->set_small)
-                        LAUNCH((schur_set<4, 2>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, nsx, B);
-                    else
-                        LAUNCH((schur_set<6, 3>), dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, nsx, B);
-                    LAUNCH(schur_sum, dim3(nbs * 8 * ceil_div(B, 8)), dim3(256), 0, A, nbs, B);
-                }
-                else
-                {
-                    static const bool wide_off = getenv("SNK_BA_NO_SCHUR_WIDE") != nullptr;  // A/B
-                    const int nb = h->max_nfc * h->max_nfc;
-                    if (B < 16 && (long long)nb * B <= 8192 && !wide_off)
-                        LAUNCH(schur_pass<4>, dim3(nb * B), dim3(256), 0, A, h->point_wave_ok && !no_wave ? 1 : 0, nb, B);
-                    else
-                        LAUNCH(schur_pass<1>, dim3(nbx * 8 * ceil_div(B, 8)), dim3(256), 0, A,
-                                           h->point_wave_ok && !no_wave ? 1 : 0, nbx, B);
-                }
-            }
-            static const bool pcg_in_lds = getenv("SNK_BA_PCG_LDS") != nullptr;  // A/B: S in LDS (pcg_solve<true>) also for local-BA sizes
-            if (h->implicit)
+            lm_linearise(c);
+            lm_camera_pass(c);
+            lm_schur(c);
+            if (P.pcg != BaPcgForm::none)
             {
                 PcgLarge W  = h->pcgw;
-                W.zero_rows = h->point_wave_ok && !no_wave ? 1 : 0;
-                LAUNCH(imp_precond, dim3(h->max_nfc), dim3(64), 0, A, W);
-                LAUNCH(imp_init, dim3(W.G), dim3(64), 0, A, O, W);
-                bool persisted = false;
-                if (W.persist_wgs > 0 && L.graph == nullptr && L.err == hipSuccess)
+                W.zero_rows = h->implicit && P.zero_rows ? 1 : 0;
+                lm_pcg_init(c, W);
+                if (ba_pcg_is_cooperative(P.pcg) && !lm_try_cooperative(c, W))
                 {
-                    static const bool fail_hook = getenv("SNK_BA_PERSIST_FAIL") != nullptr;  // tests: the runtime refuses the cooperative launch
-                    L.cooperative = true;
-                    if (fail_hook)
-                        L.cooperative = false, L.err = hipErrorCooperativeLaunchTooLarge;
-                    else
-                        LAUNCH(imp_persist, dim3(W.persist_wgs), dim3(IMP_THREADS), 0, A, O, W);
-                    persisted = L.err == hipSuccess;
-                    if (!persisted)
-                    {
-                        // refused (see the dense forms below): nothing ran, imp_init's state is where the launch sequence starts from too
-                        if (getenv("SNK_DEBUG")) fprintf(stderr, "snake_hip: cooperative implicit PCG launch refused (%s); multi-launch PCG\n", hipGetErrorString(L.err));
-                        (void)hipGetLastError();
-                        L.err               = hipSuccess;
-                        h->pcgw.persist_wgs = 0;
-                    }
+                    S.persist_wgs = h->pcgw.persist_wgs;
+                    ba_plan_pcg_stage(P, S, sw, recording);  // refused: the multi-launch form from here on
                 }
-                static const bool debug = getenv("SNK_DEBUG") != nullptr;  // tests: which form an LM iteration enqueued (or recorded)
-                if (debug) fprintf(stderr, "snake_hip: implicit PCG %s\n", persisted ? "cooperative" : L.graph ? "multi-launch (graph)" : "multi-launch");
-                if (!persisted)
-                    for (int k = 0; k < O.max_pcg; ++k)
-                    {
-                        LAUNCH(imp_point, dim3(std::max(1, ceil_div(h->max_np, 256))), dim3(256), 0, A, O, W, k);
-                        LAUNCH(imp_cam, dim3(h->max_nfc), dim3(64), 0, A, O, W, k);
-                        LAUNCH(imp_update, dim3(W.G), dim3(64), 0, A, O, W, k);
-                        LAUNCH(imp_direction, dim3(W.G), dim3(64), 0, A, O, W, k);
-                        LAUNCH(imp_latch, dim3(1), dim3(64), 0, A, O, W, k);
-                    }
+                if (sw.debug && h->implicit)  // tests: which form an LM iteration enqueued (or recorded)
+                    fprintf(stderr, "snake_hip: implicit PCG %s\n", ba_pcg_is_cooperative(P.pcg) ? "cooperative" : recording ? "multi-launch (graph)" : "multi-launch");
+                if (!ba_pcg_is_cooperative(P.pcg)) lm_pcg_solve(c, W);
             }
-            else if (!h->pcg_large && h->max_n6 <= 128 && !O.pcg_general && !pcg_in_lds)
-                LAUNCH(pcg_small, dim3(B), dim3(PCG_THREADS), ((size_t)h->max_n6 * 9 + (size_t)h->max_nfc * 72) * 8 + 8192, A, O);
-            else if (!h->pcg_large)
-                if (s_in_lds)
-                    LAUNCH(pcg_solve<true>, dim3(B), dim3(PCG_THREADS), pcg_lds, A, O);
-                else
-                    LAUNCH(pcg_solve<false>, dim3(B), dim3(PCG_THREADS), pcg_lds, A, O);
-            else
-            {
-                const PcgLarge& W = h->pcgw;
-                const dim3 gcam(W.G, B);
-                const dim3 gmv(ceil_div(h->max_n6, 256) * W.parts, B);
-                LAUNCH(pcgl_init, gcam, dim3(64), 0, A, O, W);
-                bool persisted = false;
-                if (W.persist_wgs > 0 && B == 1 && L.graph == nullptr && L.err == hipSuccess)
-                {
-                    static const bool fail_hook = getenv("SNK_BA_PERSIST_FAIL") != nullptr;  // tests: the runtime refuses the cooperative launch
-                    L.cooperative = true;
-                    if (fail_hook)
-                        L.cooperative = false, L.err = hipErrorCooperativeLaunchTooLarge;
-                    else
-                    {
-                        if (W.persist_one == 2 && W.persist_rows == 16)
-                            LAUNCH(pcgl_persist_reg<16>, dim3(W.persist_wgs), dim3(PERSIST_THREADS), (size_t)h->max_n6 * 16, A, O, W);
-                        else if (W.persist_one == 2)
-                            LAUNCH(pcgl_persist_reg<8>, dim3(W.persist_wgs), dim3(PERSIST_THREADS), (size_t)h->max_n6 * 16, A, O, W);
-                        else if (W.persist_one)
-                            LAUNCH(pcgl_persist1, dim3(W.persist_wgs), dim3(PERSIST_THREADS), (size_t)h->max_n6 * 24, A, O, W);
-                        else
-                            LAUNCH(pcgl_persist, dim3(W.persist_wgs), dim3(PERSIST_THREADS), (size_t)h->max_n6 * 8, A, O, W);
-                    }
-                    persisted = L.err == hipSuccess;
-                    if (!persisted)
-                    {
-                        // the runtime refused the cooperative launch (co-residency under another CU / LDS configuration, a partitioned device, a
-                        // driver without cooperative queues): nothing ran, pcgl_init's state is what the launch sequence below starts from too --
-                        // this handle uses that sequence from now on
-                        if (getenv("SNK_DEBUG")) fprintf(stderr, "snake_hip: cooperative PCG launch refused (%s); multi-launch PCG\n", hipGetErrorString(L.err));
-                        (void)hipGetLastError();
-                        L.err               = hipSuccess;
-                        h->pcgw.persist_wgs = 0;
-                    }
-                }
-                if (!persisted)
-                for (int k = 0; k < O.max_pcg; ++k)
-                {
-                    LAUNCH(pcgl_matvec, gmv, dim3(256), 0, A, O, W, k);
-                    LAUNCH(pcgl_combine, gcam, dim3(64), 0, A, O, W, k);
-                    LAUNCH(pcgl_update, gcam, dim3(64), 0, A, O, W, k);
-                    LAUNCH(pcgl_direction, gcam, dim3(64), 0, A, O, W, k);
-                    LAUNCH(pcgl_latch, dim3(ceil_div(B, 64)), dim3(64), 0, A, O, W, k);
-                }
-            }
+            lm_update_and_cost(c);
+            lm_accept(c, cond);
         }
-        static const bool no_uc = getenv("SNK_BA_NO_UPDATE_COST") != nullptr;  // A/B: update_wave + cost_wave
-        if (use_set && !no_uc)
-        {
-            // the work items of the set cover every point that has observations (schur_fused's linearisation-only items included)
-            LAUNCH(update_pass, dim3(std::max(1, ceil_div(h->max_ni, 128)), B), dim3(128), 0, A, 1);
-            LAUNCH(update_cost, dim3(nsx * 8 * ceil_div(B, 8)), dim3(256), 0, A, O, nsx, B);
-        }
-        else if (h->point_wave_ok && !no_wave)
-        {
-            const dim3 gwv(ceil_div(h->max_wv, 4), B);
-            LAUNCH(update_wave, dim3(gwv.x + std::max(1, ceil_div(h->max_ni, 256)), B), dim3(256), 0, A, O, (int)gwv.x);
-            LAUNCH(cost_wave, gwv, dim3(256), 0, A, O);
-        }
-        else
-        {
-            LAUNCH(update_pass, dim3(std::max(1, ceil_div(h->max_np + h->max_ni, 128)), B), dim3(128), 0, A, 0);
-            LAUNCH(point_pass<1>, gpt, dim3(128), 0, A, O);
-        }
-        if (h->max_rpc > 0 && h->max_nfc > 0) LAUNCH(rpc_pass, dim3(ceil_div(h->max_rpc, 64), B), dim3(64), 0, A, 1);
-        // big problems in small numbers: the copy of the accepted state on its own workgroups (one workgroup per problem otherwise)
-        const bool split_copy = B <= 4 && h->max_np >= 4096;
-        LAUNCH(accept_pass, dim3(B), dim3(ACC_THREADS), split_copy ? 2 * ACC_TILE * sizeof(double) : 0, A, cond, split_copy ? 1 : 0, split_copy ? 1 : 0);
-        if (split_copy) LAUNCH(accept_copy, dim3(std::min(128, ceil_div(h->max_np * 3 + h->max_ni * 7, 512)), B), dim3(256), 0, A, cond);
     }
-    }  // chain
     if (L.err != hipSuccess)
     {
         set_error("bundle adjustment launch failed: %s (%s:%d)", hipGetErrorString(L.err), __FILE__, L.line);
@@ -4982,24 +4947,20 @@ static int enqueue_lm(snk_ba* h, int iterations, Launcher& L, bool only_marked =
 // pattern is a NEW scene per keyframe solved once or twice (LocalBundleAdjustment.cpp:353-413), where building and
 // instantiating a graph costs more than it saves: the first solve with a given iteration count after set_problems
 // uses plain launches, a repeat builds the graph (measured: DESIGN.md section 4).  SNK_BA_NO_GRAPH=1: never,
-// SNK_BA_GRAPH_FIRST=1: already on the first use.
+// SNK_BA_GRAPH_FIRST=1: already on the first use.  The rule: dispatch.hpp, ba_solve_plain / ba_first_solve_plain.
 int snk_ba_solve_async(snk_ba* h, int iterations)
 {
     SNK_REQUIRE(h != nullptr && h->count > 0, "no problem set");
     SNK_REQUIRE(iterations >= 0, "negative iteration count");
     SNK_HIP_CHECK(hipSetDevice(h->device));
-    static const bool no_graph    = getenv("SNK_BA_NO_GRAPH") != nullptr;
-    static const bool graph_first = getenv("SNK_BA_GRAPH_FIRST") != nullptr;
+    const BaSwitches& sw = ba::ba_switches();
     Launcher direct;
     direct.st = h->stream;
-    // a cooperative launch is not a graph node: scenes solved by a one-launch PCG (global BA, dense or implicit) always take plain
-    // launches -- seven per LM iteration there, against milliseconds of work
-    if (no_graph || iterations == 0 || ((h->pcg_large || h->implicit) && h->pcgw.persist_wgs > 0 && h->count == 1))
-        return enqueue_lm(h, iterations, direct);
+    if (ba_solve_plain(ba::ba_shape(h), sw, iterations)) return enqueue_lm(h, iterations, direct);
     auto it = h->graphs.find(iterations);
     if (it == h->graphs.end())
     {
-        if (!graph_first && h->plain_runs[iterations]++ == 0) return enqueue_lm(h, iterations, direct);
+        if (ba_first_solve_plain(sw, h->plain_runs[iterations]++)) return enqueue_lm(h, iterations, direct);
         Launcher rec;
         rec.st = h->stream;
         if (hipGraphCreate(&rec.graph, 0) != hipSuccess)
@@ -5023,6 +4984,7 @@ int snk_ba_solve_async(snk_ba* h, int iterations)
     SNK_HIP_CHECK(hipGraphLaunch(it->second, h->stream));
     return SNK_OK;
 }
+
 
 int snk_ba_solve(snk_ba* h, int iterations, double* cost_initial, double* cost_final)
 {
@@ -5081,8 +5043,7 @@ int snk_ba_solve_local_scene(snk_ba* h, int problem, double chi2_mono, double ch
     // The extra iteration(s) (:399-410) run for the problems that had something marked.  Default: enqueued right behind the
     // pass, conditional on the device (select_marked) -- the whole call is ONE synchronisation.  SNK_BA_LOCAL_SYNC=1 (A/B), and
     // scenes on the multi-workgroup PCG (whose launch sequence sizes itself on the host): read the count back and decide here.
-    static const bool sync_env = getenv("SNK_BA_LOCAL_SYNC") != nullptr;
-    const bool on_device       = !sync_env && !h->pcg_large;
+    const bool on_device = !ba::ba_switches().local_sync && !h->pcg_large;
     State st{};
     bool have_state = false;
     if (extra_iterations > 0 && on_device)

@@ -355,11 +355,12 @@ struct Totals
     int max_be_waves = 0;
 };
 
-// Every environment switch the hand-over reads (SNK_BA_*; the PCG plan's are read in ba_plan_pcg, the kernel choice's in
-// ba_sets_will_run).  All but the last are read once per process, at the first hand-over.
+// Every environment switch of the hand-over's own (SNK_BA_*; the solver's path switches are BaSwitches in dispatch.hpp, read by
+// ba_switches() in ba.hip, and the hand-over takes what it needs of them from there).  All but the last are read once per process,
+// at the first hand-over.
 struct Switches
 {
-    bool alt_paths;     // NO_SCHUR_FUSED, NO_SCHUR_MFMA, NO_UPDATE_COST, FUSED_K10, NO_SCHUR_SET, NO_POINT_WAVE, NO_BIG_ITEMS: any of them set
+    bool alt_paths;     // BaSwitches::any_alt_path() or NO_BIG_ITEMS: work items stay at <= 64 points
     bool sets_forced;   // SCHUR_SET_MIN_ITEMS is set: the point-major lists are built whatever the size of the call (tests)
     bool profile;       // PROFILE_CREATE: host-side cost of a hand-over on stderr, in microseconds
     int host_threads;   // HOST_THREADS: threads of the threaded passes (0: by the host's size)
@@ -374,9 +375,7 @@ struct Switches
         static const Switches once = []
         {
             Switches s{};
-            s.alt_paths = getenv("SNK_BA_NO_SCHUR_FUSED") || getenv("SNK_BA_NO_SCHUR_MFMA") || getenv("SNK_BA_NO_UPDATE_COST") ||
-                          getenv("SNK_BA_FUSED_K10") || getenv("SNK_BA_NO_SCHUR_SET") || getenv("SNK_BA_NO_POINT_WAVE") ||
-                          getenv("SNK_BA_NO_BIG_ITEMS");
+            s.alt_paths    = ba_switches().any_alt_path() || getenv("SNK_BA_NO_BIG_ITEMS");
             s.sets_forced  = getenv("SNK_BA_SCHUR_SET_MIN_ITEMS") != nullptr;
             s.profile      = getenv("SNK_BA_PROFILE_CREATE") != nullptr;
             s.host_threads = getenv("SNK_BA_HOST_THREADS") ? atoi(getenv("SNK_BA_HOST_THREADS")) : 0;

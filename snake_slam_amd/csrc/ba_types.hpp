@@ -5,6 +5,7 @@
 // type in each).
 #pragma once
 #include "common.hpp"
+#include "dispatch.hpp"
 
 #include <algorithm>
 #include <condition_variable>
@@ -209,11 +210,6 @@ struct PcgLarge
     double* y;        // implicit Schur form: [tot_pt][3] V^-1 W^T p of the point phase (ps[c] then holds p_c . (S p)_c)
     int zero_rows;    // implicit Schur form: point_wave linearised (inactive observations have zero W rows, o_r is not written)
 };
-static inline int snk_env_int(const char* name, int dflt)
-{
-    const char* e = getenv(name);
-    return e && atoi(e) > 0 ? atoi(e) : dflt;
-}
 
 // The lists a scene hand-over builds on the host live in PINNED vectors that belong to the handle and keep their capacity from call to
 // call: hipMemcpyAsync from pageable memory stages and synchronises (33 uploads cost 0.23 ms per local-BA scene), from pinned memory
@@ -412,7 +408,57 @@ namespace ba
 {
 // ---- ba.hip, called by the hand-over ----
 Opt make_opt(const snk_ba_options& o);
-// Will the LM sequence of this problem set run the point-major kernels?  (see the definition)
+// The ONE reader of the solver's switches (BaSwitches in dispatch.hpp names each), filled at the first use in a process.
+inline const BaSwitches& ba_switches()
+{
+    static const BaSwitches once = []
+    {
+        const auto on  = [](const char* name) { return getenv(name) != nullptr; };
+        const auto num = [](const char* name) { const char* e = getenv(name); return e && atoi(e) > 0 ? atoi(e) : 0; };
+        BaSwitches s;
+        s.pcg_general          = on("SNK_BA_PCG_GENERAL");
+        s.no_point_wave        = on("SNK_BA_NO_POINT_WAVE");
+        s.no_schur_set         = on("SNK_BA_NO_SCHUR_SET");
+        if (const char* e = getenv("SNK_BA_SCHUR_SET_MIN_ITEMS")) s.set_min_items = atoll(e);
+        s.no_schur_mfma        = on("SNK_BA_NO_SCHUR_MFMA");
+        s.no_schur_fused       = on("SNK_BA_NO_SCHUR_FUSED");
+        s.fused_k10            = on("SNK_BA_FUSED_K10");
+        s.cam_sums             = on("SNK_BA_CAM_SUMS");
+        s.cam_grid_2d          = on("SNK_BA_CAM_GRID_2D");
+        s.no_schur_wide        = on("SNK_BA_NO_SCHUR_WIDE");
+        s.pcg_lds              = on("SNK_BA_PCG_LDS");
+        s.no_update_cost       = on("SNK_BA_NO_UPDATE_COST");
+        s.flat_barrier         = on("SNK_BA_FLAT_BARRIER");
+        s.pcg_timing           = on("SNK_BA_PCG_TIMING");
+        s.pcgl_launches        = on("SNK_BA_PCGL_LAUNCHES");
+        s.persist_two_barriers = on("SNK_BA_PERSIST_TWO_BARRIERS");
+        s.persist_stream       = on("SNK_BA_PERSIST_STREAM");
+        s.persist_wgs          = on("SNK_BA_PERSIST_WGS") ? num("SNK_BA_PERSIST_WGS") : -1;
+        s.persist_reg_rows     = num("SNK_BA_PERSIST_REG_ROWS");
+        s.persist_fail         = on("SNK_BA_PERSIST_FAIL");
+        s.graph_chains         = num("SNK_BA_GRAPH_CHAINS");
+        s.no_graph             = on("SNK_BA_NO_GRAPH");
+        s.graph_first          = on("SNK_BA_GRAPH_FIRST");
+        s.local_sync           = on("SNK_BA_LOCAL_SYNC");
+        s.debug                = on("SNK_DEBUG");
+        return s;
+    }();
+    return once;
+}
+// The totals of the handle's problem set that dispatch.hpp's rules decide on
+inline BaShape ba_shape(const snk_ba* h)
+{
+    BaShape s;
+    s.count = h->count, s.implicit = h->implicit;
+    s.max_n6 = h->max_n6, s.max_nfc = h->max_nfc, s.max_np = h->max_np, s.max_ni = h->max_ni, s.max_wv = h->max_wv, s.max_rpc = h->max_rpc;
+    s.max_set_items = h->max_set_items;
+    s.set_ok = h->set_ok, s.set_small = h->set_small, s.set_k_max = h->set_k_max, s.set_run_max = h->set_run_max;
+    s.point_wave_ok = h->point_wave_ok, s.cam_sums_ok = h->cam_sums_ok, s.blk_built = h->blk_built;
+    s.persist_wgs = h->pcgw.persist_wgs, s.persist_one = h->pcgw.persist_one, s.persist_rows = h->pcgw.persist_rows;
+    return s;
+}
+// Will the LM sequence of this problem set run the point-major kernels?  dispatch.hpp's ba_sets_will_run on the handle's shape and
+// the process's switches: the hand-over leaves out the block entries on the answer the solver will plan by
 bool ba_sets_will_run(const snk_ba* h);
 // The PCG form of the problem set and its work arrays.  Called by the hand-over once the totals of the set are in the handle
 // (count, implicit, max_n6, max_nfc, max_np, tot_vec, tot_cam, tot_pt): sets pcg_large and pcgw, reserves d_pcgw.

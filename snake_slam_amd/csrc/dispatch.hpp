@@ -1,7 +1,8 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip and pose.hip live.  Host-only and free
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip and ba.hip live.  Host-only and free
 // of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every shape of the GPU
-// tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine and
-// refine_batch_impl call these functions and keep no copy of the conditions; the environment switches are read there and passed in.
+// tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
+// refine_batch_impl and the BA solver (ba_plan_pcg, enqueue_lm) call these functions and keep no copy of the conditions; the
+// environment switches are read there and passed in.
 #pragma once
 #include <cstddef>
 
@@ -117,5 +118,325 @@ inline int pose_batch_carve(int stride, int batch, int lds_env, bool two_waves)
     else if (batch > POSE_TWO_PER_CU_BATCH && lds_matches > pose_two_per_cu()) lds_matches = pose_two_per_cu();
     if ((size_t)lds_matches * POSE_MATCH_BYTES > (size_t)pose_dyn_max()) lds_matches = pose_dyn_max() / POSE_MATCH_BYTES;
     return lds_matches;
+}
+
+// ---- bundle adjustment (ba.hip: ba_plan_pcg, enqueue_lm, snk_ba_solve_async, snk_ba_pcg_form; the hand-over asks ba_sets_will_run) --
+constexpr int BA_SET_MIN_ITEMS = 256;  // a single small window has too few work items to fill the chip, the block-major pass is quicker there
+
+// Every SNK_BA_* switch that selects a code path of the solver, and SNK_DEBUG.  ba.hip fills one per process (ba_switches()); the
+// hand-over's own host-side switches stay in ba_handover.hip.  Integer fields: 0 = unset where not said otherwise.
+struct BaSwitches
+{
+    bool pcg_general          = false;  // PCG_GENERAL: the 256-thread PCG loop for every size (A/B against the replicated one)
+    bool no_point_wave        = false;  // NO_POINT_WAVE: thread-per-point linearisation, update and cost
+    bool no_schur_set         = false;  // NO_SCHUR_SET: never the point-major Schur pass
+    long long set_min_items   = BA_SET_MIN_ITEMS;  // SCHUR_SET_MIN_ITEMS: work items of a call from which the point-major pass runs
+    bool no_schur_mfma        = false;  // NO_SCHUR_MFMA: A/B: the vector-ALU form (schur_set)
+    bool no_schur_fused       = false;  // NO_SCHUR_FUSED: A/B: point_wave + schur_mfma through W in HBM
+    bool fused_k10            = false;  // FUSED_K10: schur_fused<4> also where points have 9-10 free observations (tests)
+    bool cam_sums             = false;  // CAM_SUMS: schur_fused<3, true> + cam_sum instead of cam_pass
+    bool cam_grid_2d          = false;  // CAM_GRID_2D: A/B: the round-1..4 grid (cameras of a window over all XCDs)
+    bool no_schur_wide        = false;  // NO_SCHUR_WIDE: A/B: schur_pass<1> also for single windows
+    bool pcg_lds              = false;  // PCG_LDS: A/B: S in LDS (pcg_solve<true>) also for local-BA sizes
+    bool no_update_cost       = false;  // NO_UPDATE_COST: A/B: update_wave + cost_wave
+    bool flat_barrier         = false;  // FLAT_BARRIER: every workgroup polls every flag (the round-5 grid barrier)
+    bool pcg_timing           = false;  // PCG_TIMING (diagnostic): pcgl_persist_reg's cycles per phase on stderr
+    bool pcgl_launches        = false;  // PCGL_LAUNCHES: the multi-launch PCG instead of the one cooperative launch
+    bool persist_two_barriers = false;  // PERSIST_TWO_BARRIERS: A/B: pcgl_persist (the round-5 form) instead of pcgl_persist1
+    bool persist_stream       = false;  // PERSIST_STREAM: pcgl_persist1 streams its rows of S instead of pcgl_persist_reg's registers
+    int persist_wgs           = -1;     // PERSIST_WGS: workgroups of the cooperative launch (-1: unset; <= 0: by the problem's size)
+    int persist_reg_rows      = 0;      // PERSIST_REG_ROWS: 8 or 16 rows of S per workgroup of pcgl_persist_reg (0: by the size)
+    bool persist_fail         = false;  // PERSIST_FAIL (tests): the runtime refuses the cooperative launch
+    int graph_chains          = 0;      // GRAPH_CHAINS: chains a recorded batch sequence is split into (0: BA_GRAPH_CHAINS)
+    bool no_graph             = false;  // NO_GRAPH: plain launches always
+    bool graph_first          = false;  // GRAPH_FIRST: the graph already at the first solve of a problem set
+    bool local_sync           = false;  // LOCAL_SYNC: A/B: snk_ba_solve_local_scene decides about the extra iteration on the host
+    bool debug                = false;  // SNK_DEBUG: which forms a solve enqueued, on stderr
+
+    // a switch that takes the point-major pass off its default kernels (schur_fused + update_cost): the hand-over then keeps work
+    // items of <= 64 points, the only ones the alternative kernels walk (SET_CHUNK_BIG in ba_types.hpp)
+    bool any_alt_path() const { return no_schur_fused || no_schur_mfma || no_update_cost || fused_k10 || no_schur_set || no_point_wave; }
+};
+
+// The totals of a problem set that the decisions depend on (fields of ba::Handle and of its PCG plan).
+struct BaShape
+{
+    int count = 0;  // problems of the set
+    bool implicit = false;
+    int max_n6 = 0, max_nfc = 0, max_np = 0, max_ni = 0, max_wv = 0, max_rpc = 0, max_set_items = 0;
+    bool set_ok = false, set_small = false;
+    int set_k_max = 0, set_run_max = 0;
+    bool point_wave_ok = false, cam_sums_ok = false, blk_built = true;
+    int persist_wgs = 0, persist_one = 0, persist_rows = 0;  // ba_plan_pcg's answer (BaPersist); a refused cooperative launch zeroes persist_wgs
+};
+
+// points with 9 or 10 free observations need a fourth tile row: 260 registers, one wavefront per SIMD -- there the linearisation
+// stays in point_wave and schur_mfma<4> reads W (measured on the 300-keyframe global BA: 14.7 vs 15.5 ms)
+constexpr int BA_FUSED3_MAX_K           = 8;
+constexpr int BA_CAM64_MIN_BATCH        = 16;    // windows from which a camera gets one wavefront (cam_pass<64>), not a workgroup of four
+constexpr int BA_SCHUR_WIDE_BATCH_END   = 16;    // fewer windows than this and ...
+constexpr int BA_SCHUR_WIDE_MAX_BLOCKS  = 8192;  // ... at most this many camera-pair blocks: a workgroup per block (schur_pass<4>)
+constexpr int BA_PCG_SMALL_MAX_N6       = 128;   // unknowns up to which pcg_small keeps its quarter of S in registers
+constexpr int BA_PCG_LDS_MAX            = 158 * 1024;  // LDS of pcg_solve / pcg_small: S (and the vectors) of the largest problem fit -> one workgroup per problem
+constexpr int BA_PERSIST_LDS_MAX        = 150 * 1024;  // LDS of the persistent PCG forms (p; r, z, p in the one-barrier form)
+constexpr int PREG_MAX_N6               = 2048;  // pcgl_persist_reg: 8 rows x 2048 columns of S in a workgroup's registers
+// 16 rows per workgroup above 512 unknowns (the barrier and the exchange of A p grow with the workgroups: 225 against 113 for 300
+// keyframes: 9.4 -> 7.1 us per PCG iteration; 90 against 45 for 120 keyframes: 6.45 -> 5.7), 8 below
+constexpr int BA_PREG_ROWS16_ABOVE_N6   = 512;
+constexpr int BA_SPLIT_COPY_MAX_BATCH   = 4;     // big problems in small numbers: the copy of the accepted state on its own workgroups
+constexpr int BA_SPLIT_COPY_MIN_POINTS  = 4096;
+constexpr int BA_GRAPH_CHAINS           = 1;     // chains a recorded batch sequence is split into by default (measured +1 % with 2, -6 % with 4)
+constexpr int BA_GRAPH_CHAINS_MIN_BATCH = 128;   // windows from which a recorded sequence may be split at all ...
+constexpr int BA_GRAPH_CHAIN_MIN        = 64;    // ... into chains of at least this many
+constexpr int SUM_NB          = 4;  // schur_sum, measured per 1024 windows: 1 block per wavefront 118 us, 4: 90 us, 8: 151 us (profiles/r05/r05Q_, r05R_)
+constexpr int PERSIST_WGS_MAX = 1024;
+constexpr int PERSIST_THREADS = 256;
+constexpr int PERSIST_CAMS    = PERSIST_THREADS / 6;  // 42 cameras (252 elements) per workgroup in the update phase
+constexpr int IMP_THREADS     = 256;
+constexpr int PERSIST_MIN_WGS = 16;  // the fewest workgroups a cooperative PCG launch asks for
+constexpr int PERSIST_ROWS_PER_WG = 12;  // pcgl_persist / pcgl_persist1: a dozen rows of S per workgroup (FullBA(4), n6 = 1794: 5.0 / 4.6 / 5.9 / 5.0 ms with 256 / 128 / 64 / 32)
+
+constexpr int ba_ceil_div(int a, int b) { return (a + b - 1) / b; }
+constexpr int ba_max(int a, int b) { return a > b ? a : b; }
+constexpr int ba_min(int a, int b) { return a < b ? a : b; }
+
+// Will the LM sequence of this problem set run the point-major kernels (schur_fused / schur_mfma + update_cost over the camera-set work
+// items)?  The hand-over asks too, because the camera-pair block entries are only read by the block-major pass (schur_pass) -- building
+// them for a 1024-window batch that never runs it was 1.4 ms of device time behind every hand-over (block_entries_count 0.40 +
+// block_entries_fill 1.03 ms, round 6 trace).
+inline bool ba_sets_will_run(const BaShape& s, const BaSwitches& sw)
+{
+    return s.max_nfc > 0 && s.point_wave_ok && !sw.no_point_wave && s.set_ok && !sw.no_schur_set && (long long)s.max_set_items * s.count >= sw.set_min_items;
+}
+
+// LDS of the per-problem PCG without S: nine n6-vectors and the preconditioner blocks
+constexpr size_t ba_pcg_vec_lds(int max_n6, int max_nfc) { return (size_t)max_n6 * 9 * 8 + (size_t)max_nfc * 36 * 8; }
+// S (and the vectors) of the largest problem fit one workgroup's LDS -> one workgroup per problem; otherwise the multi-workgroup
+// PCG (measured: 120 keyframes 38 ms -> 9 ms, 600 keyframes 21 ms)
+constexpr bool ba_pcg_is_large(int max_n6, int max_nfc, bool implicit)
+{
+    return !implicit && ba_pcg_vec_lds(max_n6, max_nfc) + (size_t)max_n6 * max_n6 * 8 > (size_t)BA_PCG_LDS_MAX;
+}
+
+// A recorded sequence of a big batch may be split into chains over disjoint ranges of the windows (enqueue_lm).
+inline int ba_graph_chains(int count, bool recording, bool pcg_large, int chains_env)
+{
+    if (!recording || pcg_large || count < BA_GRAPH_CHAINS_MIN_BATCH) return 1;
+    return chains_env > 0 ? ba_min(chains_env, count / BA_GRAPH_CHAIN_MIN) : BA_GRAPH_CHAINS;
+}
+
+// ---- the cooperative (one-launch) PCG forms: what ba_plan_pcg asks the runtime, and what it makes of the answers --------------------
+struct BaPersist
+{
+    int wgs = 0, one = 0, rows = 0;  // workgroups (0: multi-launch); 0 pcgl_persist, 1 pcgl_persist1, 2 pcgl_persist_reg<rows>
+};
+// SNK_BA_PERSIST_WGS or `natural`, at most one per compute unit and PERSIST_WGS_MAX: the barrier's cost grows with the participants
+// (measured 7.0 ms per FullBA(4) with 256, 10.4 with 512)
+inline int ba_persist_wgs_wanted(int natural, int n_cu, const BaSwitches& sw)
+{
+    return ba_min(PERSIST_WGS_MAX, sw.persist_wgs > 0 ? sw.persist_wgs : ba_min(n_cu, ba_max(PERSIST_MIN_WGS, natural)));
+}
+inline bool ba_persist_tried(int count, const BaSwitches& sw) { return count == 1 && !sw.pcgl_launches; }
+// p in LDS; partial-sum slots
+inline bool ba_persist_fits(int max_n6, int max_nfc) { return (size_t)max_n6 * 8 <= (size_t)BA_PERSIST_LDS_MAX && ba_ceil_div(max_nfc, PERSIST_CAMS) <= PERSIST_WGS_MAX; }
+// the one-barrier form needs 3 n6 doubles of LDS
+inline bool ba_persist1_fits(int max_n6, const BaSwitches& sw) { return (size_t)max_n6 * 24 <= (size_t)BA_PERSIST_LDS_MAX && !sw.persist_two_barriers; }
+// the register-row rule of pcgl_persist_reg
+inline int ba_persist_reg_rows(int max_n6, const BaSwitches& sw)
+{
+    return sw.persist_reg_rows == 8 || sw.persist_reg_rows == 16 ? sw.persist_reg_rows : (max_n6 > BA_PREG_ROWS16_ABOVE_N6 ? 16 : 8);
+}
+inline bool ba_persist_reg_fits(int max_n6, const BaSwitches& sw)
+{
+    return max_n6 <= PREG_MAX_N6 && !sw.persist_stream && sw.persist_wgs < 0 &&
+           ba_ceil_div(ba_max(max_n6, 1), ba_persist_reg_rows(max_n6, sw)) <= PERSIST_WGS_MAX;
+}
+// The dense form.  coop: cooperative launch is available; res_*: resident workgroups per compute unit the runtime reports for
+// pcgl_persist (n6 doubles of LDS), pcgl_persist1 (3 n6) and pcgl_persist_reg<rows> (2 n6) -- 0: refused or not asked.  All
+// workgroups must be resident at once (grid barriers inside).
+inline BaPersist ba_persist_dense(int count, int max_n6, int max_nfc, bool coop, int n_cu, int res_persist, int res_persist1, int res_reg,
+                                  const BaSwitches& sw)
+{
+    BaPersist P;
+    if (!ba_persist_tried(count, sw) || !coop || !ba_persist_fits(max_n6, max_nfc) || res_persist < 1) return P;
+    const int wgs = ba_persist_wgs_wanted(ba_ceil_div(max_n6, PERSIST_ROWS_PER_WG), n_cu, sw);
+    if (wgs < 1) return P;
+    P.wgs = ba_min(wgs, res_persist * n_cu);
+    if (ba_persist1_fits(max_n6, sw) && res_persist1 >= 1 && res_persist1 * n_cu >= P.wgs) P.one = 1;
+    // ... and with S in registers when the system is small enough (one workgroup per 8 or 16 rows)
+    const int rows = ba_persist_reg_rows(max_n6, sw), wgs_reg = ba_ceil_div(ba_max(max_n6, 1), rows);
+    if (P.one == 1 && ba_persist_reg_fits(max_n6, sw) && res_reg >= 1 && res_reg * n_cu >= wgs_reg) P.one = 2, P.rows = rows, P.wgs = wgs_reg;
+    return P;
+}
+// The implicit form (imp_persist): enough workgroups for a point per thread or a camera per wavefront
+inline BaPersist ba_persist_implicit(int max_np, int max_nfc, bool coop, int n_cu, int res_imp, const BaSwitches& sw)
+{
+    BaPersist P;
+    if (sw.pcgl_launches || max_nfc <= 0 || !coop || res_imp < 1) return P;
+    const int want = ba_max(ba_ceil_div(max_np, IMP_THREADS), ba_ceil_div(max_nfc, IMP_THREADS / 64));
+    P.wgs = ba_min(ba_persist_wgs_wanted(want, n_cu, sw), res_imp * n_cu);
+    return P;
+}
+
+// ---- one LM iteration: a kernel form per stage ---------------------------------------------------------------------------------------
+// linearisation: schur_fused<3, false> | <3, true> | <4, false> (with the Schur products), point_wave, point_pass<0>
+enum class BaLinForm { fused3, fused3_sums, fused4, point_wave, point_pass };
+// camera pass: none without free cameras; cam_sum, cam_pass<64> on the per-XCD grid | the 2-D grid, cam_pass<256>
+enum class BaCamForm { none, cam_sum, cam64_xcd, cam64_2d, cam256 };
+// Schur complement: none (implicit form, no free cameras), inside schur_fused, schur_mfma<3, 2> | <3, 3> | <4, 3>, schur_set<4, 2> | <6, 3>
+// (each followed by schur_sum), schur_pass<4> | <1>
+enum class BaSchurForm { none, in_fused, mfma32, mfma33, mfma43, set42, set63, pass4, pass1 };
+// PCG: none without free cameras; pcg_small, pcg_solve<true> | <false>, pcgl_persist_reg<16> | <8>, pcgl_persist1, pcgl_persist, the
+// dense multi-launch sequence (pcgl_*), imp_persist, the implicit multi-launch sequence (imp_*)
+enum class BaPcgForm { none, small, solve_lds, solve_global, persist_reg16, persist_reg8, persist1, persist, launches, imp_persist, imp_launches };
+// update and cost: update_pass + update_cost, update_wave + cost_wave, update_pass + point_pass<1>
+enum class BaUpdateForm { update_cost, update_wave, update_point };
+
+// the names of the forms, in the order of the enums: the plan line of enqueue_lm (SNK_DEBUG) and tests/cpp/dispatch_driver.cpp print them
+inline const char* ba_name(BaLinForm f)
+{
+    static const char* const n[] = {"fused3", "fused3_sums", "fused4", "point_wave", "point_pass"};
+    return n[(int)f];
+}
+inline const char* ba_name(BaCamForm f)
+{
+    static const char* const n[] = {"none", "cam_sum", "cam64_xcd", "cam64_2d", "cam256"};
+    return n[(int)f];
+}
+inline const char* ba_name(BaSchurForm f)
+{
+    static const char* const n[] = {"none", "in_fused", "mfma32", "mfma33", "mfma43", "set42", "set63", "pass4", "pass1"};
+    return n[(int)f];
+}
+inline const char* ba_name(BaPcgForm f)
+{
+    static const char* const n[] = {"none", "small", "solve_lds", "solve_global", "persist_reg16", "persist_reg8", "persist1", "persist", "launches",
+                                    "imp_persist", "imp_launches"};
+    return n[(int)f];
+}
+inline const char* ba_name(BaUpdateForm f)
+{
+    static const char* const n[] = {"update_cost", "update_wave", "update_point"};
+    return n[(int)f];
+}
+
+inline bool ba_pcg_is_cooperative(BaPcgForm f)
+{
+    return f == BaPcgForm::persist_reg16 || f == BaPcgForm::persist_reg8 || f == BaPcgForm::persist1 || f == BaPcgForm::persist || f == BaPcgForm::imp_persist;
+}
+
+// The PCG form of a problem set (with free cameras) and its dynamic LDS.  recording: the sequence becomes graph nodes, and a
+// cooperative launch is not a graph node.
+inline BaPcgForm ba_pcg_form(const BaShape& s, const BaSwitches& sw, bool recording, size_t* lds = nullptr)
+{
+    size_t bytes  = 0;
+    BaPcgForm f   = BaPcgForm::launches;
+    const bool co = s.persist_wgs > 0 && !recording;
+    if (s.implicit)
+        f = co ? BaPcgForm::imp_persist : BaPcgForm::imp_launches;
+    else if (!ba_pcg_is_large(s.max_n6, s.max_nfc, false))
+    {
+        bytes = ba_pcg_vec_lds(s.max_n6, s.max_nfc);
+        // + 128 doubles read padding behind S (rows lane and lane + 64 are read unmasked) + [2][4][128] partial products
+        const size_t with_s = bytes + (size_t)s.max_n6 * s.max_n6 * 8 + 1024 + 8192;
+        if (s.max_n6 <= BA_PCG_SMALL_MAX_N6 && !sw.pcg_general && !sw.pcg_lds)
+            f = BaPcgForm::small, bytes = ((size_t)s.max_n6 * 9 + (size_t)s.max_nfc * 72) * 8 + 8192;
+        else if (with_s <= (size_t)BA_PCG_LDS_MAX)
+            f = BaPcgForm::solve_lds, bytes = with_s;
+        else
+            f = BaPcgForm::solve_global;
+    }
+    else if (co && s.count == 1)
+    {
+        if (s.persist_one == 2) f = s.persist_rows == 16 ? BaPcgForm::persist_reg16 : BaPcgForm::persist_reg8, bytes = (size_t)s.max_n6 * 16;
+        else if (s.persist_one) f = BaPcgForm::persist1, bytes = (size_t)s.max_n6 * 24;
+        else f = BaPcgForm::persist, bytes = (size_t)s.max_n6 * 8;
+    }
+    if (lds) *lds = bytes;
+    return f;
+}
+
+// "Graph or plain launches" of snk_ba_solve_async.  A cooperative launch is not a graph node: scenes solved by a one-launch PCG (global
+// BA, dense or implicit) always take plain launches -- seven per LM iteration there, against milliseconds of work.  Otherwise the first
+// solve with an iteration count after a hand-over uses plain launches and a repeat builds the graph (plain_runs: plain solves so far).
+inline bool ba_solve_plain(const BaShape& s, const BaSwitches& sw, int iterations)
+{
+    return sw.no_graph || iterations == 0 || ba_pcg_is_cooperative(ba_pcg_form(s, sw, false));  // (the implicit form takes one problem)
+}
+inline bool ba_first_solve_plain(const BaSwitches& sw, int plain_runs) { return !sw.graph_first && plain_runs == 0; }
+
+struct BaLmPlan
+{
+    BaLinForm lin       = BaLinForm::point_pass;
+    BaCamForm cam       = BaCamForm::none;
+    BaSchurForm schur   = BaSchurForm::none;
+    BaPcgForm pcg       = BaPcgForm::none;
+    BaUpdateForm update = BaUpdateForm::update_point;
+    bool use_set    = false;  // the point-major kernels run (the whole batch decides, not the range of a chain: the hand-over left out the block entries on the same answer)
+    bool zero_rows  = false;  // point_wave linearises: inactive observations have zero W rows (the implicit PCG's and schur_pass's flag)
+    bool split_copy = false;  // accept_copy behind accept_pass
+    bool no_block_lists = false;  // internal error: the block-major pass was chosen but the hand-over did not build its lists
+    int n_chain = 1;
+    int nsx = 0;   // work-item groups of the point-major kernels: four items per workgroup
+    int nbx = 0;   // schur_pass<1>: a block per wavefront
+    int nbs = 0;   // schur_sum: SUM_NB blocks per wavefront
+    size_t pcg_lds = 0;
+};
+
+// Re-planning after a refused cooperative launch: the shape with persist_wgs = 0.
+inline void ba_plan_pcg_stage(BaLmPlan& P, const BaShape& s, const BaSwitches& sw, bool recording)
+{
+    P.pcg = s.max_nfc > 0 ? ba_pcg_form(s, sw, recording, &P.pcg_lds) : BaPcgForm::none;
+}
+
+// The thresholds on the batch see B, the windows of one launch: the whole set, or the first chain's share of it (every chain of a
+// split sequence has >= BA_GRAPH_CHAIN_MIN - 7 windows, beyond all of them).
+inline BaLmPlan ba_lm_plan(const BaShape& s, const BaSwitches& sw, bool recording)
+{
+    BaLmPlan P;
+    const bool large = ba_pcg_is_large(s.max_n6, s.max_nfc, s.implicit);
+    P.n_chain        = ba_graph_chains(s.count, recording, large, sw.graph_chains);
+    const int B      = P.n_chain == 1 ? s.count : ((int)((long long)s.count / P.n_chain) & ~7);
+    P.use_set        = !s.implicit && ba_sets_will_run(s, sw);
+    P.no_block_lists = !P.use_set && !s.blk_built && !s.implicit;
+    P.zero_rows           = s.point_wave_ok && !sw.no_point_wave;
+    P.nsx            = ba_ceil_div(ba_max(s.max_set_items, 1), 4);
+    P.nbx            = ba_ceil_div(s.max_nfc * s.max_nfc, 4);
+    P.nbs            = ba_ceil_div(s.max_nfc * s.max_nfc, 4 * SUM_NB);
+    P.split_copy     = B <= BA_SPLIT_COPY_MAX_BATCH && s.max_np >= BA_SPLIT_COPY_MIN_POINTS;
+
+    const bool k8    = s.set_k_max <= BA_FUSED3_MAX_K;
+    const bool fused = P.use_set && !sw.no_schur_mfma && !sw.no_schur_fused && (k8 || sw.fused_k10);
+    // the camera pass as per-item partial sums out of schur_fused<3, true> + cam_sum instead of cam_pass.  Built because cam_pass
+    // linearises every observation a second time (294 us per 1024 windows); measured: schur_fused 1127 -> 1437 us for the five passes
+    // through the contribution buffer, cam_sum 29 us -- 46 us SLOWER per LM iteration (profiles/r03/r03aa_*).  Kept selectable and
+    // tested, not the default.
+    const bool cam_sums = fused && k8 && s.cam_sums_ok && sw.cam_sums;
+    if (fused) P.lin = cam_sums ? BaLinForm::fused3_sums : k8 ? BaLinForm::fused3 : BaLinForm::fused4;
+    else P.lin = P.zero_rows ? BaLinForm::point_wave : BaLinForm::point_pass;
+
+    if (P.use_set && !sw.no_update_cost) P.update = BaUpdateForm::update_cost;
+    else P.update = P.zero_rows ? BaUpdateForm::update_wave : BaUpdateForm::update_point;
+
+    if (s.max_nfc <= 0) return P;
+    if (cam_sums) P.cam = BaCamForm::cam_sum;
+    else if (B >= BA_CAM64_MIN_BATCH) P.cam = sw.cam_grid_2d ? BaCamForm::cam64_2d : BaCamForm::cam64_xcd;
+    else P.cam = BaCamForm::cam256;
+
+    if (s.implicit) P.schur = BaSchurForm::none;  // no S: the implicit PCG works from W, V^-1 and U
+    else if (fused) P.schur = BaSchurForm::in_fused;
+    else if (P.use_set)
+    {
+        const bool q2 = s.set_run_max * 9 + 3 <= 2 * 64;  // the rows of a point's run fit two register tiles
+        if (!sw.no_schur_mfma) P.schur = !k8 ? BaSchurForm::mfma43 : q2 ? BaSchurForm::mfma32 : BaSchurForm::mfma33;
+        else P.schur = s.set_small ? BaSchurForm::set42 : BaSchurForm::set63;
+    }
+    else
+    {
+        const long long nb = (long long)s.max_nfc * s.max_nfc;
+        P.schur = B < BA_SCHUR_WIDE_BATCH_END && nb * B <= BA_SCHUR_WIDE_MAX_BLOCKS && !sw.no_schur_wide ? BaSchurForm::pass4 : BaSchurForm::pass1;
+    }
+    ba_plan_pcg_stage(P, s, sw, recording);
+    return P;
 }
 }  // namespace snk

@@ -5,6 +5,15 @@
 //   stereo_batch:nr_cap:batch:no_frame_kernel:sort_network
 //   pose_host:total:n_problems:no_lds             pose_host_carve:n_max:n_problems
 //   pose_batch:stride:batch:n_cu:waves_env:no_lds pose_batch_carve:stride:batch:lds_env:two_waves
+//   ba_lm:<shape>:recording:switches              the five forms of an LM iteration, "lin/cam/schur/pcg/update"
+//   ba_lm_nums:<shape>:recording:switches         "use_set,nsx,nbs,nbx,pcg_lds,zero_rows,split_copy,no_block_lists,chains"
+//   ba_plain:<shape>:iterations:switches          1: snk_ba_solve_async issues plain launches whatever the history
+//     <shape> = count:implicit:n6:nfc:np:ni:wv:rpc:items:set_ok:set_small:k:run:wave_ok:sums_ok:blk:pwgs:pone:prows (BaShape)
+//     switches = comma-separated NAME=VALUE, the names of BaSwitches' comments (SNK_BA_ left off; DEBUG), or empty
+//   ba_pcg_large:n6:nfc:implicit                  ba_chains:count:recording:pcg_large:chains_env
+//   ba_reg_rows:n6:switches                       ba_sets:<shape>:switches
+//   ba_persist:count:n6:nfc:coop:n_cu:res_persist:res_persist1:res_reg:switches    "wgs,one,rows"
+//   ba_persist_imp:np:nfc:coop:n_cu:res:switches                                    "wgs,one,rows"
 //   const:NAME
 // Exit status 2 on an argument it cannot read.
 #include <cstdio>
@@ -48,6 +57,61 @@ static const char* name(snk::PoseForm f)
     return "?";
 }
 
+// "NO_POINT_WAVE=1,SCHUR_SET_MIN_ITEMS=1" -> BaSwitches, by the rules of ba_switches() in ba.hip: a flag is on when it is named
+static bool read_switches(const std::string& list, snk::BaSwitches& s)
+{
+    size_t p = 0;
+    while (p < list.size())
+    {
+        size_t q = list.find(',', p);
+        if (q == std::string::npos) q = list.size();
+        const std::string item = list.substr(p, q - p);
+        p                      = q + 1;
+        const size_t eq        = item.find('=');
+        const std::string k    = item.substr(0, eq);
+        const long long v      = eq == std::string::npos ? 1 : std::atoll(item.c_str() + eq + 1);
+        const int pos          = v > 0 ? (int)v : 0;
+        if (k == "PCG_GENERAL") s.pcg_general = true;
+        else if (k == "NO_POINT_WAVE") s.no_point_wave = true;
+        else if (k == "NO_SCHUR_SET") s.no_schur_set = true;
+        else if (k == "SCHUR_SET_MIN_ITEMS") s.set_min_items = v;
+        else if (k == "NO_SCHUR_MFMA") s.no_schur_mfma = true;
+        else if (k == "NO_SCHUR_FUSED") s.no_schur_fused = true;
+        else if (k == "FUSED_K10") s.fused_k10 = true;
+        else if (k == "CAM_SUMS") s.cam_sums = true;
+        else if (k == "CAM_GRID_2D") s.cam_grid_2d = true;
+        else if (k == "NO_SCHUR_WIDE") s.no_schur_wide = true;
+        else if (k == "PCG_LDS") s.pcg_lds = true;
+        else if (k == "NO_UPDATE_COST") s.no_update_cost = true;
+        else if (k == "FLAT_BARRIER") s.flat_barrier = true;
+        else if (k == "PCG_TIMING") s.pcg_timing = true;
+        else if (k == "PCGL_LAUNCHES") s.pcgl_launches = true;
+        else if (k == "PERSIST_TWO_BARRIERS") s.persist_two_barriers = true;
+        else if (k == "PERSIST_STREAM") s.persist_stream = true;
+        else if (k == "PERSIST_WGS") s.persist_wgs = pos;
+        else if (k == "PERSIST_REG_ROWS") s.persist_reg_rows = pos;
+        else if (k == "PERSIST_FAIL") s.persist_fail = true;
+        else if (k == "GRAPH_CHAINS") s.graph_chains = pos;
+        else if (k == "NO_GRAPH") s.no_graph = true;
+        else if (k == "GRAPH_FIRST") s.graph_first = true;
+        else if (k == "LOCAL_SYNC") s.local_sync = true;
+        else if (k == "DEBUG") s.debug = true;
+        else return false;
+    }
+    return true;
+}
+
+constexpr size_t BA_SHAPE_ARGS = 19;
+static snk::BaShape read_shape(const std::vector<long long>& v)
+{
+    snk::BaShape s;
+    s.count = (int)v[0], s.implicit = v[1] != 0, s.max_n6 = (int)v[2], s.max_nfc = (int)v[3], s.max_np = (int)v[4], s.max_ni = (int)v[5];
+    s.max_wv = (int)v[6], s.max_rpc = (int)v[7], s.max_set_items = (int)v[8], s.set_ok = v[9] != 0, s.set_small = v[10] != 0;
+    s.set_k_max = (int)v[11], s.set_run_max = (int)v[12], s.point_wave_ok = v[13] != 0, s.cam_sums_ok = v[14] != 0, s.blk_built = v[15] != 0;
+    s.persist_wgs = (int)v[16], s.persist_one = (int)v[17], s.persist_rows = (int)v[18];
+    return s;
+}
+
 int main(int argc, char** argv)
 {
     for (int a = 1; a < argc; ++a)
@@ -61,10 +125,43 @@ int main(int argc, char** argv)
         }
         const std::string& e = f[0];
         std::vector<long long> v;
+        snk::BaSwitches sw;
+        const bool ba = e.compare(0, 3, "ba_") == 0 && e != "ba_pcg_large" && e != "ba_chains";  // the last field: the switches
+        if (ba && (f.size() < 2 || !read_switches(f.back(), sw)))
+        {
+            std::fprintf(stderr, "dispatch_driver: cannot read the switches of %s\n", argv[a]);
+            return 2;
+        }
         if (e != "const")
-            for (size_t i = 1; i < f.size(); ++i) v.push_back(std::atoll(f[i].c_str()));
+            for (size_t i = 1; i + (ba ? 1 : 0) < f.size(); ++i) v.push_back(std::atoll(f[i].c_str()));
         const size_t n = v.size();
-        if (e == "knn2" && n == 4) std::printf("%s\n", name(snk::knn2_form((int)v[0], (int)v[1], (int)v[2], v[3] != 0)));
+        if (e == "ba_lm" && n == BA_SHAPE_ARGS + 1)
+        {
+            const snk::BaLmPlan P = snk::ba_lm_plan(read_shape(v), sw, v[BA_SHAPE_ARGS] != 0);
+            std::printf("%s/%s/%s/%s/%s\n", snk::ba_name(P.lin), snk::ba_name(P.cam), snk::ba_name(P.schur), snk::ba_name(P.pcg), snk::ba_name(P.update));
+        }
+        else if (e == "ba_lm_nums" && n == BA_SHAPE_ARGS + 1)
+        {
+            const snk::BaLmPlan P = snk::ba_lm_plan(read_shape(v), sw, v[BA_SHAPE_ARGS] != 0);
+            std::printf("%d,%d,%d,%d,%zu,%d,%d,%d,%d\n", (int)P.use_set, P.nsx, P.nbs, P.nbx, P.pcg_lds, (int)P.zero_rows, (int)P.split_copy,
+                        (int)P.no_block_lists, P.n_chain);
+        }
+        else if (e == "ba_plain" && n == BA_SHAPE_ARGS + 1) std::printf("%d\n", (int)snk::ba_solve_plain(read_shape(v), sw, (int)v[BA_SHAPE_ARGS]));
+        else if (e == "ba_sets" && n == BA_SHAPE_ARGS) std::printf("%d\n", (int)snk::ba_sets_will_run(read_shape(v), sw));
+        else if (e == "ba_pcg_large" && n == 3) std::printf("%d\n", (int)snk::ba_pcg_is_large((int)v[0], (int)v[1], v[2] != 0));
+        else if (e == "ba_chains" && n == 4) std::printf("%d\n", snk::ba_graph_chains((int)v[0], v[1] != 0, v[2] != 0, (int)v[3]));
+        else if (e == "ba_reg_rows" && n == 1) std::printf("%d\n", snk::ba_persist_reg_rows((int)v[0], sw));
+        else if (e == "ba_persist" && n == 8)
+        {
+            const snk::BaPersist P = snk::ba_persist_dense((int)v[0], (int)v[1], (int)v[2], v[3] != 0, (int)v[4], (int)v[5], (int)v[6], (int)v[7], sw);
+            std::printf("%d,%d,%d\n", P.wgs, P.one, P.rows);
+        }
+        else if (e == "ba_persist_imp" && n == 5)
+        {
+            const snk::BaPersist P = snk::ba_persist_implicit((int)v[0], (int)v[1], v[2] != 0, (int)v[3], (int)v[4], sw);
+            std::printf("%d,%d,%d\n", P.wgs, P.one, P.rows);
+        }
+        else if (e == "knn2" && n == 4) std::printf("%s\n", name(snk::knn2_form((int)v[0], (int)v[1], (int)v[2], v[3] != 0)));
         else if (e == "stereo_host" && n == 2) std::printf("%s\n", name(snk::stereo_host_form((int)v[0], v[1] != 0)));
         else if (e == "stereo_batch" && n == 4) std::printf("%s\n", name(snk::stereo_batch_form((int)v[0], (int)v[1], v[2] != 0, v[3] != 0)));
         else if (e == "pose_host" && n == 3) std::printf("%s\n", name(snk::pose_host_form((size_t)v[0], (int)v[1], v[2] != 0)));
@@ -84,6 +181,23 @@ int main(int argc, char** argv)
             else if (c == "POSE_HOST_WAVE4_MEAN") val = snk::POSE_HOST_WAVE4_MEAN;
             else if (c == "POSE_BATCH_WAVE4_MIN") val = snk::POSE_BATCH_WAVE4_MIN;
             else if (c == "POSE_SLOTS_PER_WAVE") val = snk::POSE_SLOTS_PER_WAVE;
+            else if (c == "BA_SET_MIN_ITEMS") val = snk::BA_SET_MIN_ITEMS;
+            else if (c == "BA_FUSED3_MAX_K") val = snk::BA_FUSED3_MAX_K;
+            else if (c == "BA_CAM64_MIN_BATCH") val = snk::BA_CAM64_MIN_BATCH;
+            else if (c == "BA_SCHUR_WIDE_BATCH_END") val = snk::BA_SCHUR_WIDE_BATCH_END;
+            else if (c == "BA_SCHUR_WIDE_MAX_BLOCKS") val = snk::BA_SCHUR_WIDE_MAX_BLOCKS;
+            else if (c == "BA_PCG_SMALL_MAX_N6") val = snk::BA_PCG_SMALL_MAX_N6;
+            else if (c == "BA_PCG_LDS_MAX") val = snk::BA_PCG_LDS_MAX;
+            else if (c == "BA_PERSIST_LDS_MAX") val = snk::BA_PERSIST_LDS_MAX;
+            else if (c == "PREG_MAX_N6") val = snk::PREG_MAX_N6;
+            else if (c == "BA_PREG_ROWS16_ABOVE_N6") val = snk::BA_PREG_ROWS16_ABOVE_N6;
+            else if (c == "BA_SPLIT_COPY_MAX_BATCH") val = snk::BA_SPLIT_COPY_MAX_BATCH;
+            else if (c == "BA_SPLIT_COPY_MIN_POINTS") val = snk::BA_SPLIT_COPY_MIN_POINTS;
+            else if (c == "BA_GRAPH_CHAINS") val = snk::BA_GRAPH_CHAINS;
+            else if (c == "BA_GRAPH_CHAINS_MIN_BATCH") val = snk::BA_GRAPH_CHAINS_MIN_BATCH;
+            else if (c == "BA_GRAPH_CHAIN_MIN") val = snk::BA_GRAPH_CHAIN_MIN;
+            else if (c == "SUM_NB") val = snk::SUM_NB;
+            else if (c == "PERSIST_WGS_MAX") val = snk::PERSIST_WGS_MAX;
             else
             {
                 std::fprintf(stderr, "dispatch_driver: no constant %s\n", c.c_str());

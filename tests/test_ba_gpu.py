@@ -707,3 +707,67 @@ def test_refused_hand_over_arguments_leave_no_problem_set():
     ba.close()
     for k, (x, y) in enumerate(zip(again, want)):
         assert np.array_equal(x, y), f"output {k} after the refused hand-overs differs from a fresh handle's"
+
+
+# The default path of the five scenes of the test below, in its order: linearisation / camera pass / Schur complement / PCG / update.
+LM_DEFAULT_FORMS = [
+    "point_wave/cam256/pass4/small/update_wave",         # one window of 3 keyframes x 10 points
+    "point_wave/cam256/pass4/small/update_wave",         # one window of 20 keyframes
+    "point_wave/cam64_xcd/pass1/small/update_wave",      # 16 windows: too few work items for the point-major pass
+    "fused3/cam64_xcd/in_fused/small/update_cost",       # 256 windows: the point-major pass
+    "point_wave/cam256/pass4/persist_reg8/update_wave",  # 30 keyframes: the multi-workgroup PCG, one cooperative launch
+]
+# The rows of tests/test_zy_ba_variants_gpu.py whose comment names a kernel, by the row's SNK_BA_* environment: (stage, form) pairs that
+# must occur on at least one plan line of the five scenes ("refused": the line of the refused cooperative launch instead).
+# Left out, "switch set, form not reached" on these scenes: FUSED_K10 (schur_fused<4> needs a point with 9 or 10 free observations).
+LM_VARIANT_FORMS = {
+    ("SCHUR_SET_MIN_ITEMS",): [("lin", "fused3"), ("schur", "in_fused"), ("update", "update_cost")],
+    ("NO_SCHUR_SET",): [("schur", "pass1"), ("schur", "pass4")],
+    ("NO_POINT_WAVE",): [("lin", "point_pass"), ("update", "update_point")],
+    ("PCG_GENERAL",): [("pcg", "solve_lds")],
+    ("NO_SCHUR_FUSED", "SCHUR_SET_MIN_ITEMS"): [("lin", "point_wave"), ("schur", "mfma32")],
+    ("NO_SCHUR_MFMA", "SCHUR_SET_MIN_ITEMS"): [("lin", "point_wave"), ("schur", "set42")],
+    ("CAM_SUMS", "SCHUR_SET_MIN_ITEMS"): [("lin", "fused3_sums"), ("cam", "cam_sum")],
+    ("PCG_LDS",): [("pcg", "solve_lds")],
+    ("NO_SCHUR_SET", "NO_SCHUR_WIDE"): [("schur", "pass1")],
+    ("PCGL_LAUNCHES",): [("pcg", "launches")],
+    ("PERSIST_STREAM",): [("pcg", "persist1")],
+    ("PERSIST_REG_ROWS",): [("pcg", "persist_reg16")],
+    ("PERSIST_TWO_BARRIERS",): [("pcg", "persist")],
+    ("PERSIST_FAIL",): [("pcg", "persist_reg8"), ("refused", "")],
+}
+
+
+def test_lm_plan_lines_name_the_forms_that_ran(tmp_path, capfd, monkeypatch):
+    """Which kernel form each stage of an LM iteration took is observed, not trusted: under SNK_DEBUG every enqueue_lm call prints its
+    plan.  Every line must carry the forms dispatch.hpp gives for the shape on that line under this process's switches (asked of the CPU
+    driver); without switches they are the default path written down above; and under a row of the variants matrix (this file runs again
+    under each) the kernel the row names is among them."""
+    import forms
+    from snake_slam_amd import synth
+    from snake_slam_amd.ba import BARec, lba_options
+
+    monkeypatch.setenv("SNK_DEBUG", "1")
+    window = lambda k: synth.ba_scene(n_kf=3, n_pt=10, obs_per_pt=2, seed=700 + k)[0]
+    scenes = [window(0), synth.ba_scene(n_kf=20, n_pt=400, obs_per_pt=5, seed=720)[0], [window(k) for k in range(16)],
+              [window(k % 8) for k in range(256)], synth.ba_scene(n_kf=30, n_pt=900, obs_per_pt=5, seed=31, outlier_frac=0.05)[0]]
+    ba = BARec(lba_options())
+    capfd.readouterr()
+    for sc in scenes:
+        ba.create(sc)
+        ba.solve(2)
+    ba.close()
+    err = capfd.readouterr().err
+    lines = forms.ba_plan_lines(err)
+    print(err)
+    assert len(lines) == len(scenes) and "implicit PCG" not in err
+    switches = forms.ba_env_switches(os.environ)
+    want = forms.ask(forms.build_driver(tmp_path), [("ba_lm", shape + (switches,)) for shape, _ in lines])
+    assert [f for _, f in lines] == want
+    stages = ("lin", "cam", "schur", "pcg", "update")
+    seen = {(st, v) for _, f in lines for st, v in zip(stages, f.split("/"))} | ({("refused", "")} if "PCG launch refused" in err else set())
+    row = tuple(sorted(k[len("SNK_BA_"):] for k in os.environ if k.startswith("SNK_BA_")))
+    if not row:
+        assert [f for _, f in lines] == LM_DEFAULT_FORMS
+    for named in LM_VARIANT_FORMS.get(row, []):
+        assert named in seen, (row, named, sorted(seen))

@@ -8,7 +8,8 @@ import pytest
 import forms
 from forms import ENUM_OF, ENUMS, ENV_ONLY, FORMS
 
-SWITCH_ARGS = {"knn2": [3], "stereo_host": [1], "stereo_batch": [2, 3], "pose_host": [2], "pose_batch": [3, 4]}  # environment switches in a shape
+SWITCH_ARGS = {"knn2": [3], "stereo_host": [1], "stereo_batch": [2, 3], "pose_host": [2], "pose_batch": [3, 4],
+               "ba_lm": [len(forms.BA_FIELDS)]}  # environment switches in a shape
 
 
 @pytest.fixture(scope="module")
@@ -23,7 +24,7 @@ def answers(driver):
 
 @pytest.mark.parametrize("entry,shape,form", FORMS, ids=[f"{e}{s}".replace(" ", "") for e, s, _ in FORMS])
 def test_every_row_of_the_table(answers, entry, shape, form):
-    assert form in ENUMS[ENUM_OF[entry]]
+    assert all(value in ENUMS[enum] for enum, value in forms.parts(entry, form))
     assert answers[(entry, shape)] == form
 
 
@@ -32,7 +33,7 @@ def test_the_table_names_every_form():
     for enum, values in ENUMS.items():
         m = re.search(r"enum class %s\s*\{([^}]*)\}" % enum, header)
         assert m and [v.strip() for v in m.group(1).split(",")] == values, f"tests/forms.py does not list {enum} as dispatch.hpp has it"
-        named = {f for e, sh, f in FORMS if ENUM_OF[e] == enum and not any(sh[i] for i in SWITCH_ARGS[e])}  # selected by shape alone
+        named = {v for e, sh, f in FORMS if not any(sh[i] for i in SWITCH_ARGS[e]) for en, v in forms.parts(e, f) if en == enum}  # selected by shape alone
         for v in values:
             if (enum, v) not in ENV_ONLY:
                 assert v in named, f"no shape of the table selects {enum}::{v}"
@@ -72,3 +73,122 @@ def test_lds_carves(driver):
          ("pose_batch_carve", (9000, 5, 8000, 1))]
     want = [1500, two_per_cu, 900, dyn_max, 700, two_per_cu, 1500, 100, 50, dyn_max, four_per_cu, 300, 100, dyn_max]
     assert [int(v) for v in forms.ask(driver, q)] == want
+
+
+BA_CONSTANTS = {"BA_SET_MIN_ITEMS": 256, "BA_FUSED3_MAX_K": 8, "BA_CAM64_MIN_BATCH": 16, "BA_SCHUR_WIDE_BATCH_END": 16, "BA_SCHUR_WIDE_MAX_BLOCKS": 8192,
+                "BA_PCG_SMALL_MAX_N6": 128, "BA_PCG_LDS_MAX": 158 * 1024, "BA_PERSIST_LDS_MAX": 150 * 1024, "PREG_MAX_N6": 2048,
+                "BA_PREG_ROWS16_ABOVE_N6": 512, "BA_SPLIT_COPY_MAX_BATCH": 4, "BA_SPLIT_COPY_MIN_POINTS": 4096, "BA_GRAPH_CHAINS": 1,
+                "BA_GRAPH_CHAINS_MIN_BATCH": 128, "BA_GRAPH_CHAIN_MIN": 64, "SUM_NB": 4, "PERSIST_WGS_MAX": 1024}
+
+
+def test_ba_constants(driver):
+    names = list(BA_CONSTANTS)
+    assert dict(zip(names, map(int, forms.ask(driver, [("const", (n,)) for n in names])))) == BA_CONSTANTS
+
+
+def test_ba_thresholds_from_both_sides(driver):
+    """Both neighbours of every threshold of ba_lm_plan: the form of a stage changes exactly there."""
+    ba, SETS = forms.ba, forms.SETS
+    stage = {"lin": 0, "cam": 1, "schur": 2, "pcg": 3, "update": 4}
+    cases = [  # (shape, stage, form)
+        # 256 work items in the call: max_set_items * B
+        (ba(B=128, set_ok=1, items=2), "lin", "fused3"), (ba(B=127, set_ok=1, items=2), "lin", "point_wave"),
+        (ba(B=85, set_ok=1, items=3), "update", "update_wave"), (ba(B=86, set_ok=1, items=3), "update", "update_cost"),
+        (ba(B=128, set_ok=0, items=2), "lin", "point_wave"),
+        # set_k_max <= 8: three tile rows
+        (ba(B=256, k=8, run=10, **SETS), "lin", "fused3"), (ba(B=256, k=9, run=10, **SETS), "lin", "point_wave"),
+        (ba(B=256, k=9, run=10, **SETS), "schur", "mfma43"),
+        (ba("NO_SCHUR_FUSED", B=256, k=8, run=10, **SETS), "schur", "mfma32"), (ba("NO_SCHUR_FUSED", B=256, k=9, run=10, **SETS), "schur", "mfma43"),
+        (ba("CAM_SUMS,FUSED_K10", B=256, k=9, run=10, **SETS), "lin", "fused4"), (ba("CAM_SUMS,FUSED_K10", B=256, k=9, run=10, **SETS), "cam", "cam64_xcd"),
+        # set_run_max * 9 + 3 <= 128: two register tiles up to 13 rows
+        (ba("NO_SCHUR_FUSED", B=256, run=13, **SETS), "schur", "mfma32"), (ba("NO_SCHUR_FUSED", B=256, run=14, **SETS), "schur", "mfma33"),
+        # B >= 16: a wavefront per camera
+        (ba(B=15), "cam", "cam256"), (ba(B=16), "cam", "cam64_xcd"),
+        # B < 16 and nb * B <= 8192: a workgroup per block
+        (ba(B=15, nfc=3), "schur", "pass4"), (ba(B=16, nfc=3), "schur", "pass1"),
+        (ba(B=2, nfc=64, pwgs=0), "schur", "pass4"), (ba(B=2, nfc=65, pwgs=0), "schur", "pass1"),   # 2 * 4096 = 8192, 2 * 4225
+        (ba(B=1, nfc=90), "schur", "pass4"), (ba(B=1, nfc=91), "schur", "pass1"),                   # 8100, 8281
+        # max_n6 <= 128, and the 21 / 22 / 23 free-camera window of the per-problem PCG
+        (ba(nfc=21), "pcg", "small"), (ba(nfc=22), "pcg", "solve_global"), (ba(nfc=23), "pcg", "launches"),
+        (ba(nfc=21, n6=128), "pcg", "small"), (ba(nfc=21, n6=129), "pcg", "solve_lds"),   # (the hand-over gives n6 = 6 nfc: 126 and 132 are the real neighbours)
+        (ba("PCG_LDS", nfc=21), "pcg", "solve_lds"), (ba("PCG_GENERAL", nfc=21), "pcg", "solve_lds"), (ba("PCG_LDS", nfc=22), "pcg", "solve_global"),
+        # the cooperative forms as ba_plan_pcg left them; recorded sequences and batches take the launches
+        (ba(nfc=23, pwgs=18, pone=2, prows=8), "pcg", "persist_reg8"), (ba(nfc=23, pwgs=9, pone=2, prows=16), "pcg", "persist_reg16"),
+        (ba(nfc=23, pwgs=18, pone=2, prows=8, rec=1), "pcg", "launches"), (ba(B=2, nfc=23, pwgs=18, pone=2, prows=8), "pcg", "launches"),
+        # B <= 4 and max_np >= 4096: the copy of the accepted state on its own workgroups -- see the numbers below
+    ]
+    got = forms.ask(driver, [("ba_lm", sh) for sh, _, _ in cases])
+    for (sh, st, want), g in zip(cases, got):
+        assert g.split("/")[stage[st]] == want, (sh, st, g)
+    # the derived numbers: use_set, nsx, nbs, nbx, pcg_lds, zero_rows, split_copy, no_block_lists, chains
+    nums = lambda *shapes: [tuple(int(x) for x in a.split(",")) for a in forms.ask(driver, [("ba_lm_nums", sh) for sh in shapes])]
+    a, b, c, d = nums(ba(B=4, np=4096), ba(B=4, np=4095), ba(B=5, np=4096), ba(B=1, np=1 << 20))
+    assert (a[6], b[6], c[6], d[6]) == (1, 0, 0, 1)
+    # nsx = ceil(items / 4); nbx = ceil(nfc^2 / 4); nbs = ceil(nfc^2 / 16); the LDS of pcg_small, pcg_solve<false>, pcg_solve<true>
+    a, b, c = nums(ba(B=256, nfc=5, set_ok=1, items=9), ba(nfc=22), ba("PCG_LDS", nfc=21))
+    assert a[:4] == (1, 3, 2, 7) and a[4] == (30 * 9 + 5 * 72) * 8 + 8192 and a[5] == 1
+    assert b[4] == 132 * 72 + 22 * 288 and c[4] == 126 * 72 + 21 * 288 + 126 * 126 * 8 + 1024 + 8192 <= 158 * 1024
+    # the LDS of the cooperative forms: 2, 3 and 1 vectors of n6 doubles
+    a, b, c = nums(ba(nfc=23, pwgs=18, pone=2, prows=8), ba(nfc=23, pwgs=18, pone=1), ba(nfc=23, pwgs=18, pone=0))
+    assert (a[4], b[4], c[4]) == (138 * 16, 138 * 24, 138 * 8)
+    # the block-major pass without its lists is an internal error, as a value; NO_POINT_WAVE clears zero_rows
+    a, b, c = nums(ba(blk=0), ba(B=256, blk=0, **SETS), ba("NO_POINT_WAVE"))
+    assert (a[7], b[7], c[7]) == (1, 0, 0) and (a[5], c[5]) == (1, 0)
+    a, = nums(ba(imp=1, blk=0, pwgs=8))
+    assert a[7] == 0
+
+
+def test_ba_pcg_sizes_chains_and_persistent_forms(driver):
+    """ba_pcg_is_large, ba_graph_chains, the register-row rule and what ba_plan_pcg makes of the runtime's answers."""
+    ask = lambda *q: forms.ask(driver, list(q))
+    assert ask(("ba_pcg_large", (126, 21, 0)), ("ba_pcg_large", (132, 22, 0)), ("ba_pcg_large", (138, 23, 0)), ("ba_pcg_large", (1794, 299, 1))) == \
+        ["0", "0", "1", "0"]
+    # chains: recorded sequences of >= 128 per-problem windows only; SNK_BA_GRAPH_CHAINS at most one chain per 64 windows
+    assert ask(("ba_chains", (256, 1, 0, 0)), ("ba_chains", (256, 1, 0, 2)), ("ba_chains", (256, 0, 0, 2)), ("ba_chains", (127, 1, 0, 2)),
+               ("ba_chains", (128, 1, 0, 2)), ("ba_chains", (128, 1, 0, 4)), ("ba_chains", (256, 1, 1, 2))) == ["1", "2", "1", "1", "2", "2", "1"]
+    assert [int(a.split(",")[8]) for a in ask(("ba_lm_nums", forms.ba("GRAPH_CHAINS=2", B=256, rec=1)), ("ba_lm_nums", forms.ba("GRAPH_CHAINS=2", B=256)))] == [2, 1]
+    # 16 register rows above 512 unknowns; SNK_BA_PERSIST_REG_ROWS forces 8 or 16 and nothing else
+    assert ask(("ba_reg_rows", (512, "")), ("ba_reg_rows", (513, "")), ("ba_reg_rows", (100, "PERSIST_REG_ROWS=16")),
+               ("ba_reg_rows", (1000, "PERSIST_REG_ROWS=8")), ("ba_reg_rows", (1000, "PERSIST_REG_ROWS=12"))) == ["8", "16", "16", "8", "16"]
+    # count, n6, nfc, cooperative launch, CUs, resident workgroups per CU of pcgl_persist / pcgl_persist1 / pcgl_persist_reg
+    q = [(1, 1794, 299, 1, 256, 1, 1, 1, ""),                       # FullBA on 300 keyframes: 113 workgroups of 16 rows in registers
+         (1, 174, 29, 1, 256, 1, 1, 1, ""),                         # 30 keyframes: 22 workgroups of 8 rows
+         (1, 2048, 342, 1, 256, 1, 1, 1, ""), (1, 2052, 342, 1, 256, 1, 1, 1, ""),   # PREG_MAX_N6: beyond, pcgl_persist1 with n6 / 12 workgroups
+         (1, 1794, 299, 1, 256, 1, 1, 1, "PERSIST_STREAM"), (1, 1794, 299, 1, 256, 1, 1, 1, "PERSIST_TWO_BARRIERS"),
+         (1, 1794, 299, 1, 256, 1, 1, 1, "PERSIST_WGS=32"), (1, 1794, 299, 1, 256, 1, 1, 1, "PCGL_LAUNCHES"),
+         (2, 1794, 299, 1, 256, 1, 1, 1, ""), (1, 1794, 299, 0, 256, 1, 1, 1, ""), (1, 1794, 299, 1, 256, 0, 1, 1, ""),
+         (1, 1794, 299, 1, 256, 1, 0, 1, ""), (1, 1794, 299, 1, 256, 1, 1, 0, ""), (1, 1794, 299, 1, 64, 1, 1, 1, ""),
+         (1, 6402, 1067, 1, 256, 1, 1, 1, ""), (1, 19206, 3201, 1, 256, 1, 1, 1, "")]   # 3 n6 doubles past 150 KB: two barriers; n6 doubles past it: none
+    want = ["113,2,16", "22,2,8", "128,2,16", "171,1,0", "150,1,0", "150,0,0", "32,1,0", "0,0,0", "0,0,0", "0,0,0", "0,0,0", "150,0,0", "150,1,0",
+            "64,1,0", "256,0,0", "0,0,0"]
+    assert ask(*[("ba_persist", a) for a in q]) == want
+    # implicit form: a point per thread or a camera per wavefront, at least 16 workgroups, at most one per CU
+    assert ask(("ba_persist_imp", (9000, 299, 1, 256, 2, "")), ("ba_persist_imp", (100, 10, 1, 256, 2, "")), ("ba_persist_imp", (10**6, 299, 1, 256, 2, "")),
+               ("ba_persist_imp", (9000, 299, 1, 256, 2, "PCGL_LAUNCHES")), ("ba_persist_imp", (9000, 0, 1, 256, 2, "")),
+               ("ba_persist_imp", (9000, 299, 1, 256, 2, "PERSIST_WGS=600"))) == ["75,0,0", "16,0,0", "256,0,0", "0,0,0", "0,0,0", "512,0,0"]
+    # graph or plain launches: cooperative forms, SNK_BA_NO_GRAPH and zero iterations are always plain
+    assert ask(("ba_plain", forms.ba(nfc=23, pwgs=18, pone=2, prows=8)[:19] + (5, "")), ("ba_plain", forms.ba()[:19] + (5, "")),
+               ("ba_plain", forms.ba()[:19] + (0, "")), ("ba_plain", forms.ba()[:19] + (5, "NO_GRAPH")),
+               ("ba_plain", forms.ba(nfc=23, pwgs=0)[:19] + (5, "")), ("ba_plain", forms.ba(imp=1, pwgs=8)[:19] + (5, ""))) == ["1", "0", "1", "1", "0", "1"]
+    assert ask(("ba_sets", forms.ba(B=128, set_ok=1, items=2)[:19] + ("",)), ("ba_sets", forms.ba(B=127, set_ok=1, items=2)[:19] + ("",)),
+               ("ba_sets", forms.ba(B=1, set_ok=1, items=1)[:19] + ("SCHUR_SET_MIN_ITEMS=1",)), ("ba_sets", forms.ba(B=128, nfc=0, set_ok=1, items=2)[:19] + ("",))) == \
+        ["1", "0", "1", "0"]
+
+
+def test_ba_switch_lists_agree():
+    """BaSwitches (dispatch.hpp), its reader (ba_types.hpp), the driver's parser, tests/forms.py and the README name the same switches;
+    ba.hip reads none itself but SNK_DEBUG, and the hand-over none of the solver's path switches."""
+    csrc = forms.ROOT / "snake_slam_amd" / "csrc"
+    struct = re.search(r"struct BaSwitches\s*\{(.*?)\n\};", (csrc / "dispatch.hpp").read_text(), re.S).group(1)
+    fields = re.findall(r"^\s+(?:bool|int|long long) \w+\s*=[^;]*;\s*// (\w+)", struct, re.M)
+    assert fields == forms.BA_SWITCHES + ["SNK_DEBUG"]
+    reader = (csrc / "ba_types.hpp").read_text()
+    assert sorted(set(re.findall(r'"SNK_BA_(\w+)"', reader))) == sorted(forms.BA_SWITCHES) and '"SNK_DEBUG"' in reader
+    driver = (forms.ROOT / "tests" / "cpp" / "dispatch_driver.cpp").read_text()
+    assert sorted(re.findall(r'k == "(\w+)"', driver)) == sorted(forms.BA_SWITCHES + ["DEBUG"])
+    readme = (forms.ROOT / "README.md").read_text()
+    assert all(f"SNK_BA_{n}" in readme for n in forms.BA_SWITCHES)
+    assert re.findall(r'getenv\("(\w+)"\)', (csrc / "ba.hip").read_text()) == ["SNK_DEBUG"]
+    handover = set(re.findall(r'"SNK_BA_(\w+)"', (csrc / "ba_handover.hip").read_text()))
+    assert handover == {"NO_BIG_ITEMS", "SCHUR_SET_MIN_ITEMS", "PROFILE_CREATE", "HOST_THREADS", "NO_HOST_POOL", "FILL_CHUNKS", "HOST_ENTRIES",
+                        "BECNT_BUDGET", "CHECK_LISTS"}
