@@ -702,6 +702,74 @@ SNK_API int snk_triangulate_neighbours(snk_matcher* m, const snk_camera* cam, co
                                        snk_new_point* out, int32_t* out_start, int* n_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Map-point refresh: descriptor, normal, reference depth (semantics "snk-mp v1")
+ * ------------------------------------------------------------------------------------------ */
+
+#define SNK_MP_MAX_OBS 4096 /* observations of one point: 128 KiB of descriptors in a workgroup's LDS (160 KiB per CU) */
+
+#define SNK_MP_MEDIAN 0 /* m(i) = element (N - 1) / 2 of row i of the distance matrix, sorted ascending: the ORB-SLAM rule */
+#define SNK_MP_SUM 1    /* m(i) = sum of row i */
+
+#define SNK_MP_DESCRIPTOR 1 /* MapPoint::ComputeDistinctiveDescriptors, Snake/Map/MapPoint.cpp:60-81 */
+#define SNK_MP_NORMAL 2     /* MapPoint::UpdateNormal, :120-135 */
+#define SNK_MP_DEPTH 4      /* MapPoint::UpdateDepth, :154-166 */
+
+#define SNK_MP_OK 0
+#define SNK_MP_BAD_INDEX 1 /* device form: a (kf_slot, feature), a ref_obs or an obs_start outside its range */
+#define SNK_MP_TOO_MANY 2  /* device form: more than SNK_MP_MAX_OBS observations */
+
+typedef struct snk_mp_params
+{
+    int32_t rule; /* SNK_MP_MEDIAN / SNK_MP_SUM */
+    int32_t what; /* SNK_MP_DESCRIPTOR | SNK_MP_NORMAL | SNK_MP_DEPTH */
+} snk_mp_params;
+
+/* One refreshed point.  A part that `what` does not select, or that the rules leave untouched, has best = -1 and desc = 0
+ * (descriptor), normal = (0, 0, 0), ref_level = -1 and ref_depth = 0; n_valid is always the number of valid observations.
+ * status != SNK_MP_OK (device form only): every other field has those values and n_valid = 0. */
+typedef struct snk_mp_result
+{
+    int32_t best;      /* bestId of MapPoint.cpp:79 as an index into the point's full list (invalid entries included); -1: none */
+    int32_t n_valid;   /* N */
+    int32_t ref_level; /* reference_scale_level, :165 */
+    int32_t status;
+    double normal[3];  /* :134 */
+    double ref_depth;  /* reference_depth, :162 */
+    uint64_t desc[4];  /* descriptor, :80 */
+} snk_mp_result;
+
+/* MapPoint::ComputeDistinctiveDescriptors, UpdateNormal and UpdateDepth — Snake/Map/MapPoint.cpp:60-81, :120-135, :154-166 —
+ * for n_points map points in one call, as the reference's loops gather them (Triangulator.cpp:94-97, LocalMapping.cpp:179,215,
+ * NeighbourSearch.cpp:218-219, LocalBundleAdjustment.cpp:497, ...).  Point p owns the observations obs_start[p] ..
+ * obs_start[p + 1] - 1 (obs_start[0] = 0) in the order of mObservations; per observation: desc = frame->descriptors[obs.second]
+ * (:72), cam_pose = obs.first->Pose() (qx qy qz qw tx ty tz, world -> camera; CameraPosition() = -R^T t, :128), octave =
+ * undistorted_keypoints[obs.second].octave (:165), valid != 0 <=> !obs.first->isBad() (:71, :127).  Per point: position and
+ * ref_obs = indexInternal(referenceKF) as an index into the point's list (-1: UpdateDepth is not run for it).  out[n_points].
+ * The rules are [DEFINED] (Saiga::MeanMatcher and Eigen are absent): invalid observations are skipped; the descriptor is the first
+ * valid observation in list order whose row of Hamming distances to all valid ones (itself included) has the smallest median
+ * (element (N - 1) / 2 of the sorted row) or sum; the normal is the sum in list order of the unit vectors towards the camera
+ * centres, normalised (a zero vector stays zero), all in fp64 without contraction; ref_depth = |position - C_ref|.  The results
+ * do not depend on the kernel form (SNK_MP_FORM=packed|wide forces one, read once).
+ * A NULL array with a non-zero count, a non-monotone obs_start, a ref_obs outside [-1, k), a point with more than SNK_MP_MAX_OBS
+ * observations, an unknown rule or `what` bit: SNK_ERR_INVALID_ARG, nothing is launched.  n_points == 0 and points with k = 0 are
+ * valid. */
+SNK_API int snk_mappoint_refresh(snk_matcher* m, const snk_mp_params* params, int n_points, const int32_t* obs_start,
+                                 const uint64_t (*desc)[4], const double (*cam_pose)[7], const int32_t* octave, const uint8_t* valid,
+                                 const double (*position)[3], const int32_t* ref_obs, snk_mp_result* out);
+
+/* The same refresh (MapPoint.cpp:60-81, :120-135, :154-166) with everything resident on the device: the keyframes are the slots
+ * of `frames` (desc and kps [batch][cap] as the batched front-end leaves them; right_points / taken / cell_start are not read)
+ * with poses_dev [batch][7]; observation o is obs_dev[o] = (kf_slot, feature) with valid_dev[o]; obs_start_dev [n_points + 1]
+ * indexes obs_dev [n_obs]; position_dev [n_points][3], ref_obs_dev [n_points]; out_dev [n_points].  Asynchronous on the handle's
+ * stream, no host round trip.  Nothing can be checked on the host, so the kernels check: a point with an obs_start outside
+ * [0, n_obs] or decreasing, a ref_obs outside [-1, k), or a valid (or reference) observation outside [0, batch) x [0, n[slot]) gets
+ * status = SNK_MP_BAD_INDEX, one with k > SNK_MP_MAX_OBS gets SNK_MP_TOO_MANY, and nothing outside those ranges is read. */
+SNK_API int snk_mappoint_refresh_batch_dev(snk_matcher* m, const snk_mp_params* params, const snk_frames_dev* frames,
+                                           const double* poses_dev, int n_points, const int32_t* obs_start_dev, int n_obs,
+                                           const int32_t (*obs_dev)[2], const uint8_t* valid_dev, const double* position_dev,
+                                           const int32_t* ref_obs_dev, snk_mp_result* out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Pose refinement (the step after every projection matcher)
  * ------------------------------------------------------------------------------------------ */
 

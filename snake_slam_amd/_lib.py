@@ -74,6 +74,8 @@ SIGNATURES = {
     "snk_match_relink": (i32, [vp, vp, vp, vp, vp, i32, f32, f64, i32, vp, vp, C.POINTER(i32)]),
     "snk_triangulate_pairs": (i32, [vp, vp, vp, vp, vp, f32, vp, i32, vp, i32, vp, C.POINTER(i32)]),
     "snk_triangulate_neighbours": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(i32)]),
+    "snk_mappoint_refresh": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "snk_mappoint_refresh_batch_dev": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "snk_p3p_ransac": (i32, [vp, vp, vp, i32]),
     "snk_p3p_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "snk_p3p_ransac_frame_batch_dev": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),

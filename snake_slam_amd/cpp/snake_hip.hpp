@@ -742,6 +742,76 @@ class Triangulator
     bool mono_;
 };
 
+// MapPoint::ComputeDistinctiveDescriptors / UpdateNormal / UpdateDepth (reference Snake/Map/MapPoint.cpp:60-81, :120-135, :154-166)
+// for a batch of points, semantics "snk-mp v1": the loops that call them per point (Triangulator.cpp:94-97, LocalMapping.cpp:179,215,
+// NeighbourSearch.cpp:218-219, LocalBundleAdjustment.cpp:497, GlobalBundleAdjustment.cpp:502, ...) collect a PointView per point and
+// make one call after the loop.  The list surgery (AddObservation, Replace, SetBadFlag) stays on the Snake side.
+class MapPointRefresher
+{
+   public:
+    // one entry of mObservations: obs.first->Pose(), obs.first->frame->descriptors[obs.second],
+    // undistorted_keypoints[obs.second].octave, !obs.first->isBad().  The pose and the descriptor must outlive the call.
+    struct Observation
+    {
+        const double* pose               = nullptr;  // qx qy qz qw tx ty tz
+        const DescriptorORB* descriptor  = nullptr;
+        int octave                       = 0;
+        bool valid                       = true;
+    };
+    struct PointView
+    {
+        std::vector<Observation> observations;  // in the order of mObservations
+        double position[3] = {0, 0, 0};
+        int ref_obs        = -1;  // indexInternal(referenceKF) as an index into observations; -1: UpdateDepth leaves the point alone
+    };
+
+    explicit MapPointRefresher(int rule = SNK_MP_MEDIAN, int device = 0) : rule_(rule) { check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create"); }
+    ~MapPointRefresher() { snk_matcher_destroy(h_); }
+    MapPointRefresher(const MapPointRefresher&)            = delete;
+    MapPointRefresher& operator=(const MapPointRefresher&) = delete;
+
+    // the three updates of every point in one call; result[p].best = -1 leaves the descriptor as it was (MapPoint.cpp:75)
+    std::vector<snk_mp_result> Refresh(const std::vector<PointView>& points, int what = SNK_MP_DESCRIPTOR | SNK_MP_NORMAL | SNK_MP_DEPTH)
+    {
+        std::vector<int32_t> start{0}, octave, ref;
+        std::vector<DescriptorORB> desc;
+        std::vector<std::array<double, 7>> pose;
+        std::vector<std::array<double, 3>> position;
+        std::vector<uint8_t> valid;
+        for (const PointView& p : points)
+        {
+            for (const Observation& o : p.observations)
+            {
+                if (!o.pose || !o.descriptor) throw std::invalid_argument("MapPointRefresher: observation without pose / descriptor");
+                std::array<double, 7> q;
+                std::memcpy(q.data(), o.pose, sizeof(q));
+                pose.push_back(q);
+                desc.push_back(*o.descriptor);
+                octave.push_back(o.octave);
+                valid.push_back(o.valid ? 1 : 0);
+            }
+            start.push_back((int32_t)desc.size());
+            position.push_back({p.position[0], p.position[1], p.position[2]});
+            ref.push_back(p.ref_obs);
+        }
+        std::vector<snk_mp_result> out(points.size());
+        const snk_mp_params par{rule_, what};
+        check(snk_mappoint_refresh(h_, &par, (int)points.size(), start.data(), reinterpret_cast<const uint64_t(*)[4]>(desc.data()),
+                                   reinterpret_cast<const double(*)[7]>(pose.data()), octave.data(), valid.data(),
+                                   reinterpret_cast<const double(*)[3]>(position.data()), ref.data(), out.data()),
+              "snk_mappoint_refresh");
+        return out;
+    }
+    // after a replacement only the descriptor is wanted (MapPoint.cpp:244), after BA only the normal (LocalBundleAdjustment.cpp:497)
+    std::vector<snk_mp_result> ComputeDistinctiveDescriptors(const std::vector<PointView>& points) { return Refresh(points, SNK_MP_DESCRIPTOR); }
+    std::vector<snk_mp_result> UpdateNormal(const std::vector<PointView>& points) { return Refresh(points, SNK_MP_NORMAL); }
+    std::vector<snk_mp_result> UpdateDepth(const std::vector<PointView>& points) { return Refresh(points, SNK_MP_DEPTH); }
+
+   private:
+    snk_matcher* h_ = nullptr;
+    int rule_;
+};
+
 // Saiga::P3PRansac as Tracking::TrackBruteForce uses it -- Snake/Tracking/TrackingCoarse.cpp:403-440, semantics "snk-p3p v1":
 //   RansacParameters params; params.maxIterations = 250; params.residualThreshold = chi1 * chi1;
 //   P3PRansac pnp2(params);  inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask);

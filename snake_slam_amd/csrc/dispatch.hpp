@@ -1,5 +1,5 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip and ba.hip live.  Host-only and free
-// of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every shape of the GPU
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip and ba.hip
+// live.  Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every shape of the GPU
 // tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
 // refine_batch_impl and the BA solver (ba_plan_pcg, enqueue_lm) call these functions and keep no copy of the conditions; the
 // environment switches are read there and passed in.
@@ -119,6 +119,34 @@ inline int pose_batch_carve(int stride, int batch, int lds_env, bool two_waves)
     if ((size_t)lds_matches * POSE_MATCH_BYTES > (size_t)pose_dyn_max()) lds_matches = pose_dyn_max() / POSE_MATCH_BYTES;
     return lds_matches;
 }
+
+// ---- map-point refresh (mappoint.hip: snk_mappoint_refresh, snk_mappoint_refresh_batch_dev) ----------------------------------------
+// packed: mp_packed_kernel, a lane per observation row, the points of a 64-point chunk packed into wavefronts (no point straddles
+// one), the row of distances in registers;  wide: mp_wide_kernel, a workgroup per point, rows strided over its lanes.
+constexpr int MP_PACKED_MAX_K   = 32;    // observations up to which a point's rows share a wavefront: 16 registers hold its row of distances
+constexpr int MP_CHUNK_POINTS   = 64;    // points per workgroup of the packed form: one lane of its first wavefront plans each
+constexpr int MP_CHUNK_SLOTS    = 64;    // wavefront-sized row groups a chunk can need: a closed group holds more than 64 - 32 rows
+constexpr int MP_PACKED_THREADS = 256;
+constexpr int MP_WIDE_THREADS   = 1024;
+constexpr int MP_WIDE_MAX_WGS   = 1024;  // the wide form's workgroups walk the list of wide points
+constexpr int MP_WIDE_MAX_K     = 4096;  // = SNK_MP_MAX_OBS
+
+enum class MpForm { packed, wide };
+
+// form_env: SNK_MP_FORM (0 = unset, 1 = "packed": the default rule, 2 = "wide": every point on a workgroup of its own)
+constexpr MpForm mp_form(int k, int form_env) { return form_env != 2 && k <= MP_PACKED_MAX_K ? MpForm::packed : MpForm::wide; }
+
+// LDS carve of a packed workgroup whose chunk has at most `rows` packed rows: descriptors (32 B), a flag byte per row, the
+// row -> (point, observation) map of the chunk's slots, four ints per point and the slot count
+constexpr size_t mp_packed_carve(int rows)
+{
+    return (size_t)rows * 32 + (size_t)((rows + 15) & ~15) + (size_t)MP_CHUNK_SLOTS * 64 * 2 + (size_t)MP_CHUNK_POINTS * 16 + 16;
+}
+// ... of a wide workgroup for points of at most k_cap observations: descriptors (the unit vectors of the normal use the same bytes
+// before them, 24 B each), a flag byte per observation, a key per wavefront and two ints
+constexpr size_t mp_wide_carve(int k_cap) { return (size_t)k_cap * 32 + (size_t)((k_cap + 15) & ~15) + (size_t)(MP_WIDE_THREADS / 64) * 8 + 16; }
+// the device-resident entry cannot look at the lists: the largest chunk and the largest point
+constexpr int mp_packed_rows_max() { return MP_CHUNK_POINTS * MP_PACKED_MAX_K; }
 
 // ---- bundle adjustment (ba.hip: ba_plan_pcg, enqueue_lm, snk_ba_solve_async, snk_ba_pcg_form; the hand-over asks ba_sets_will_run) --
 constexpr int BA_SET_MIN_ITEMS = 256;  // a single small window has too few work items to fill the chip, the block-major pass is quicker there
