@@ -770,6 +770,99 @@ SNK_API int snk_mappoint_refresh_batch_dev(snk_matcher* m, const snk_mp_params* 
                                            const int32_t* ref_obs_dev, snk_mp_result* out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Covisibility: connection lists and the local-keyframe vote (semantics "snk-covis v1")
+ * ------------------------------------------------------------------------------------------ */
+
+#define SNK_COVIS_MAX_KF 32768 /* keyframe slots: a u32 counter per keyframe is 128 KiB of a compute unit's 160 KiB LDS */
+#define SNK_COVIS_MAX_CAP 4096 /* list entries kept per set: their ids are sorted in 16 KiB of LDS beside the counters */
+
+#define SNK_COVIS_OK 0
+#define SNK_COVIS_UNCHANGED 1 /* no keyframe touched: the reference returns and leaves the old connections (Keyframe.cpp:125-129) */
+#define SNK_COVIS_BAD_INDEX 2 /* device forms: a query, a start, a point id or an observation's keyframe outside its range */
+
+#define SNK_COVIS_PT_BAD 1 /* pt_flags bit 0: !(*mp) / mp->isBad() */
+#define SNK_COVIS_PT_FAR 2 /* pt_flags bit 1: mp->far_stereo_point */
+
+/* The map as tables, keyframe slots 0 .. n_kf - 1, point ids 0 .. n_points - 1.  Host pointers for snk_covis_update / snk_covis_vote,
+ * device pointers for the _batch_dev forms.  The two sides of the map (obs here, feat_point of the calls) are read as given. */
+typedef struct snk_covis_map
+{
+    int32_t n_kf, n_points, n_obs;
+    const uint8_t* kf_bad;      /* [n_kf] Keyframe::isBad() */
+    const int32_t* obs_start;   /* [n_points + 1], obs_start[0] = 0 */
+    const int32_t (*obs)[2];    /* [n_obs] mp->GetObservationList() in list order as (kf, feature): the layout of snk_mappoint_refresh_batch_dev */
+    const uint8_t* pt_flags;    /* [n_points] SNK_COVIS_PT_BAD | SNK_COVIS_PT_FAR */
+} snk_covis_map;
+
+typedef struct snk_covis_params
+{
+    int32_t th;     /* Keyframe.cpp:135: 15.  >= 1.  The vote has no threshold but checks the field alike */
+    float th_depth; /* Keyframe.cpp:111.  Not read by the vote */
+    int32_t cap;    /* entries of conn per set, 1 .. SNK_COVIS_MAX_CAP */
+} snk_covis_params;
+
+typedef struct snk_covis_conn
+{
+    int32_t weight;
+    int32_t kf;
+} snk_covis_conn;
+
+/* One set.  The list is ascending by (weight, kf); n_found is its full length, n_conn = min(n_found, cap) entries are in conn[set]
+ * [0 .. n_conn): the LAST n_conn of the list, still ascending (every consumer reads from the back); entries past n_conn are not
+ * written.  best_kf = the last entry (-1: empty list).  status != SNK_COVIS_OK: n_found = n_conn = 0, best_kf = -1. */
+typedef struct snk_covis_result
+{
+    int32_t n_found;
+    int32_t n_conn;
+    int32_t best_kf;
+    int32_t status;
+} snk_covis_result;
+
+/* Keyframe::UpdateConnections — Snake/Map/Keyframe.cpp:89-171 — for the n_q keyframes q[0 .. n_q) in one call, every query against
+ * the same tables (UpdateConnections changes connections, not observations; the caller applies the lists in order).  Keyframe k owns
+ * the features feat_start[k] .. feat_start[k + 1] - 1 (feat_start[n_kf + 1], feat_start[0] = 0): feat_point = observations[i] as a point
+ * id (-1: none), feat_depth = frame->depth[i].  A feature counts unless its point is bad (:107), far or deeper than th_depth (:111;
+ * equality and depths <= 0 count); every observation (k, .) of its point with k != q adds 1 to count[k] (:117-121), duplicates as
+ * often as they occur, bad keyframes included.  Nothing touched: SNK_COVIS_UNCHANGED (:125).  The list is every touched keyframe that is
+ * not bad (:141) with count >= th (:147); if none, the one with the largest count (:154), [DEFINED] the smallest id among equals; only
+ * bad ones touched: an empty list with SNK_COVIS_OK.  Order [DEFINED]: ascending by (weight, kf), the order KeyframeGraph.cpp:124
+ * keeps.  best_kf is the parent candidate of :168; GetBestCovisibilityKeyFrames(N) (KeyframeGraph.cpp:62) is the last N entries.
+ * AddConnection on the listed keyframes (:150,157) and the parent / child links (:166-170) stay with the caller.
+ * conn [n_q][cap], out [n_q].  Everything is checked before anything is launched: a NULL array with a non-zero count, a start array that
+ * does not begin at 0 or decreases, an id outside its range, n_kf > SNK_COVIS_MAX_KF, cap outside [1, SNK_COVIS_MAX_CAP], th < 1:
+ * SNK_ERR_INVALID_ARG.  n_q == 0, keyframes without features and points without observations are valid.  The results do not
+ * depend on the kernel form (SNK_COVIS_LONG_MIN=<n> moves the length from which a wavefront walks a list, read once). */
+SNK_API int snk_covis_update(snk_matcher* m, const snk_covis_map* map, const int32_t* feat_start, const int32_t* feat_point,
+                             const float* feat_depth, const snk_covis_params* params, int n_q, const int32_t* q, snk_covis_conn* conn,
+                             snk_covis_result* out);
+
+/* The same (Keyframe.cpp:89-171) with every table, q_dev, conn_dev and out_dev on the device; n_feat is the length of feat_point_dev /
+ * feat_depth_dev.  Asynchronous on the handle's stream, no host round trip.  n_kf, cap and th are checked on the host; the host
+ * cannot look at the tables, so the kernel checks: a query outside [0, n_kf), a feature range outside [0, n_feat] or decreasing, a
+ * point id >= n_points or < -1, an obs_start outside [0, n_obs] or decreasing, an observation's keyframe outside [0, n_kf) give that
+ * set status = SNK_COVIS_BAD_INDEX, and nothing outside the ranges is read. */
+SNK_API int snk_covis_update_batch_dev(snk_matcher* m, const snk_covis_map* map_dev, const int32_t* feat_start_dev, int n_feat,
+                                       const int32_t* feat_point_dev, const float* feat_depth_dev, const snk_covis_params* params, int n_q,
+                                       const int32_t* q_dev, snk_covis_conn* conn_dev, snk_covis_result* out_dev);
+
+/* The vote at the head of Tracking::UpdateLocalKeyFrames2 — Snake/Tracking/TrackingFine.cpp:230-268 — for n_sets frames: set s is
+ * the point ids set_point[set_start[s] .. set_start[s + 1]) (a frame's mvpMapPoints, -1 = none, so a padded [batch][cap] array with
+ * set_start[b] = b * cap is a valid input).  -1 and bad points are skipped (:233-239); every observation adds 1 to its keyframe
+ * (:241-251): no self exclusion, no depth gate, no threshold, bad keyframes are kept.  The list is every touched keyframe ascending by
+ * (count, id) (:267, [DEFINED] the id for the pointer), best_kf = reference_keyframe (:268); nothing touched: SNK_COVIS_UNCHANGED
+ * (:254).  Clearing the bad points of the frame (:237) and everything from :272 on stay with the caller.  Of params only cap has an
+ * effect.  Checks and errors as snk_covis_update (th < 1 included). */
+SNK_API int snk_covis_vote(snk_matcher* m, const snk_covis_map* map, int n_sets, const int32_t* set_start, const int32_t* set_point,
+                           const snk_covis_params* params, snk_covis_conn* conn, snk_covis_result* out);
+
+/* The same vote (TrackingFine.cpp:230-268) on the device; n_set_points is the length of set_point_dev.  Asynchronous, checked by the
+ * kernel as snk_covis_update_batch_dev checks: a set range outside [0, n_set_points] or decreasing, a point id, an obs_start or an
+ * observation's keyframe outside its range give status = SNK_COVIS_BAD_INDEX. */
+SNK_API int snk_covis_vote_batch_dev(snk_matcher* m, const snk_covis_map* map_dev, int n_sets, const int32_t* set_start_dev,
+                                     int n_set_points, const int32_t* set_point_dev, const snk_covis_params* params,
+                                     snk_covis_conn* conn_dev, snk_covis_result* out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Pose refinement (the step after every projection matcher)
  * ------------------------------------------------------------------------------------------ */
 

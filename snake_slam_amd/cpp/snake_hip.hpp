@@ -812,6 +812,134 @@ class MapPointRefresher
     int rule_;
 };
 
+// Keyframe::UpdateConnections (reference Snake/Map/Keyframe.cpp:89-171) for a list of keyframes and the vote at the head of
+// Tracking::UpdateLocalKeyFrames2 (Snake/Tracking/TrackingFine.cpp:230-268) for a list of frames, semantics "snk-covis v1": the
+// caller flattens the map into a MapTables (keyframe slots and point ids are indices into it), makes one call and applies the lists:
+// AddConnection(this, w) on every listed keyframe (Keyframe.cpp:150,157), connections = the list (:164), parent = list.Best() (:168).
+class CovisibilityGraph
+{
+   public:
+    struct MapTables
+    {
+        std::vector<uint8_t> kf_bad;                 // Keyframe::isBad()
+        std::vector<int32_t> obs_start{0};           // per point, into obs
+        std::vector<std::array<int32_t, 2>> obs;     // mp->GetObservationList() in list order: (keyframe slot, feature)
+        std::vector<uint8_t> pt_flags;               // SNK_COVIS_PT_BAD | SNK_COVIS_PT_FAR
+        std::vector<int32_t> feat_start{0};          // per keyframe, into feat_point / feat_depth
+        std::vector<int32_t> feat_point;             // observations[i] as a point id, -1: none
+        std::vector<float> feat_depth;               // frame->depth[i]
+
+        // the next point id: its flags and its observation list
+        int AddPoint(bool bad, bool far_stereo_point, const std::vector<std::pair<int, int>>& observations)
+        {
+            for (const auto& o : observations) obs.push_back({(int32_t)o.first, (int32_t)o.second});
+            obs_start.push_back((int32_t)obs.size());
+            pt_flags.push_back((uint8_t)((bad ? SNK_COVIS_PT_BAD : 0) | (far_stereo_point ? SNK_COVIS_PT_FAR : 0)));
+            return (int)pt_flags.size() - 1;
+        }
+        // the next keyframe slot: its features in feature order
+        int AddKeyframe(bool bad, const std::vector<int32_t>& points, const std::vector<float>& depth)
+        {
+            if (points.size() != depth.size()) throw std::invalid_argument("CovisibilityGraph: a depth per feature");
+            feat_point.insert(feat_point.end(), points.begin(), points.end());
+            feat_depth.insert(feat_depth.end(), depth.begin(), depth.end());
+            feat_start.push_back((int32_t)feat_point.size());
+            kf_bad.push_back(bad ? 1 : 0);
+            return (int)kf_bad.size() - 1;
+        }
+        snk_covis_map view() const
+        {
+            snk_covis_map m;
+            m.n_kf      = (int32_t)kf_bad.size();
+            m.n_points  = (int32_t)pt_flags.size();
+            m.n_obs     = (int32_t)obs.size();
+            m.kf_bad    = kf_bad.data();
+            m.obs_start = obs_start.data();
+            m.obs       = reinterpret_cast<const int32_t(*)[2]>(obs.data());
+            m.pt_flags  = pt_flags.data();
+            return m;
+        }
+    };
+
+    // one returned list: the last min(n_found, cap) entries of it, ascending by (weight, kf)
+    struct List
+    {
+        std::vector<snk_covis_conn> connections;
+        int n_found = 0;
+        int status  = SNK_COVIS_OK;  // SNK_COVIS_UNCHANGED: leave the old connections (Keyframe.cpp:125-129)
+
+        int Best() const { return connections.empty() ? -1 : connections.back().kf; }  // Keyframe.cpp:168, TrackingFine.cpp:268
+        // KeyframeGraph::GetBestCovisibilityKeyFrames(N), KeyframeGraph.cpp:49-63: the last N, the best last
+        std::vector<int> BestCovisibility(int N) const
+        {
+            N = std::max(0, std::min(N, (int)connections.size()));
+            std::vector<int> v;
+            for (size_t i = connections.size() - (size_t)N; i < connections.size(); ++i) v.push_back(connections[i].kf);
+            return v;
+        }
+        // KeyframeGraph::GetCovisiblesByWeight(w), KeyframeGraph.cpp:148-172
+        std::vector<int> CovisiblesByWeight(int w) const
+        {
+            std::vector<int> v;
+            for (const snk_covis_conn& c : connections)
+                if (c.weight >= w) v.push_back(c.kf);
+            return v;
+        }
+    };
+
+    explicit CovisibilityGraph(int th = 15, float th_depth = 40.0f, int cap = 256, int device = 0) : par_{th, th_depth, cap}
+    {
+        check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create");
+    }
+    ~CovisibilityGraph() { snk_matcher_destroy(h_); }
+    CovisibilityGraph(const CovisibilityGraph&)            = delete;
+    CovisibilityGraph& operator=(const CovisibilityGraph&) = delete;
+
+    // Keyframe::UpdateConnections for every keyframe of `queries`, all against the same tables
+    std::vector<List> UpdateConnections(const MapTables& map, const std::vector<int32_t>& queries)
+    {
+        const snk_covis_map m = map.view();
+        std::vector<snk_covis_conn> conn(queries.size() * (size_t)par_.cap);
+        std::vector<snk_covis_result> res(queries.size());
+        check(snk_covis_update(h_, &m, map.feat_start.data(), map.feat_point.data(), map.feat_depth.data(), &par_, (int)queries.size(), queries.data(),
+                               conn.data(), res.data()),
+              "snk_covis_update");
+        return lists(conn, res);
+    }
+
+    // the vote of UpdateLocalKeyFrames2 for every frame: frames[f] = its mvpMapPoints as point ids, -1: none; Best() = reference_keyframe
+    std::vector<List> VoteLocalKeyframes(const MapTables& map, const std::vector<std::vector<int32_t>>& frames)
+    {
+        const snk_covis_map m = map.view();
+        std::vector<int32_t> start{0}, point;
+        for (const auto& f : frames)
+        {
+            point.insert(point.end(), f.begin(), f.end());
+            start.push_back((int32_t)point.size());
+        }
+        std::vector<snk_covis_conn> conn(frames.size() * (size_t)par_.cap);
+        std::vector<snk_covis_result> res(frames.size());
+        check(snk_covis_vote(h_, &m, (int)frames.size(), start.data(), point.data(), &par_, conn.data(), res.data()), "snk_covis_vote");
+        return lists(conn, res);
+    }
+
+   private:
+    std::vector<List> lists(const std::vector<snk_covis_conn>& conn, const std::vector<snk_covis_result>& res) const
+    {
+        std::vector<List> out(res.size());
+        for (size_t s = 0; s < res.size(); ++s)
+        {
+            const snk_covis_conn* row = conn.data() + s * (size_t)par_.cap;
+            out[s].connections.assign(row, row + res[s].n_conn);
+            out[s].n_found = res[s].n_found;
+            out[s].status  = res[s].status;
+        }
+        return out;
+    }
+    snk_matcher* h_ = nullptr;
+    snk_covis_params par_;
+};
+
 // Saiga::P3PRansac as Tracking::TrackBruteForce uses it -- Snake/Tracking/TrackingCoarse.cpp:403-440, semantics "snk-p3p v1":
 //   RansacParameters params; params.maxIterations = 250; params.residualThreshold = chi1 * chi1;
 //   P3PRansac pnp2(params);  inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask);

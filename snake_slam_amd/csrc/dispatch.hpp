@@ -1,4 +1,4 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip and ba.hip
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip and ba.hip
 // live.  Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every shape of the GPU
 // tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
 // refine_batch_impl and the BA solver (ba_plan_pcg, enqueue_lm) call these functions and keep no copy of the conditions; the
@@ -147,6 +147,28 @@ constexpr size_t mp_packed_carve(int rows)
 constexpr size_t mp_wide_carve(int k_cap) { return (size_t)k_cap * 32 + (size_t)((k_cap + 15) & ~15) + (size_t)(MP_WIDE_THREADS / 64) * 8 + 16; }
 // the device-resident entry cannot look at the lists: the largest chunk and the largest point
 constexpr int mp_packed_rows_max() { return MP_CHUNK_POINTS * MP_PACKED_MAX_K; }
+
+// ---- covisibility (covis.hip: snk_covis_update, snk_covis_vote and their _batch_dev forms) ------------------------------------------
+// covis_kernel: a workgroup per set.  A lane takes a feature; a list of at most covis_long_min observations it walks itself, a longer
+// one it queues in LDS and a wavefront walks it, a lane per observation.
+constexpr int COVIS_THREADS  = 256;  // four wavefronts: several workgroups share a compute unit at the usual few thousand keyframes
+constexpr int COVIS_LONG_MIN = 32;   // observations above which a list is walked by a wavefront (a lane alone would hold its 63 neighbours up)
+constexpr int COVIS_MISC     = 32;   // u32 words of flags, sums, the fallback key and the per-wavefront partial counts
+
+// long_env: SNK_COVIS_LONG_MIN (< 0 = unset; n >= 0: lists longer than n observations are queued -- 0 queues every list)
+constexpr int covis_long_min(int long_env) { return long_env >= 0 ? long_env : COVIS_LONG_MIN; }
+// ids the in-LDS sort holds: the entries kept (at most cap, at most n_kf) rounded up to a power of two, at least four
+constexpr int covis_sort_len(int n_kf, int cap)
+{
+    int n = 4;
+    while (n < cap && n < n_kf) n <<= 1;
+    return n;
+}
+// LDS carve of a workgroup: a u32 counter per keyframe, the ids to sort, the queue of long lists (a point id per lane), the words above
+constexpr size_t covis_carve(int n_kf, int cap)
+{
+    return (size_t)((n_kf + 3) & ~3) * 4 + (size_t)covis_sort_len(n_kf, cap) * 4 + (size_t)COVIS_THREADS * 4 + (size_t)COVIS_MISC * 4;
+}
 
 // ---- bundle adjustment (ba.hip: ba_plan_pcg, enqueue_lm, snk_ba_solve_async, snk_ba_pcg_form; the hand-over asks ba_sets_will_run) --
 constexpr int BA_SET_MIN_ITEMS = 256;  // a single small window has too few work items to fill the chip, the block-major pass is quicker there
