@@ -1,10 +1,13 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip and ba.hip
-// live.  Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every shape of the GPU
-// tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
-// refine_batch_impl and the BA solver (ba_plan_pcg, enqueue_lm) call these functions and keep no copy of the conditions; the
-// environment switches are read there and passed in.
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, ba.hip,
+// orb.hip (the extractor's whole launch plan, over the geometry of orb_layout.hpp) and track.hip (the projection matchers) live.
+// Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every
+// shape of the GPU tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
+// refine_batch_impl, the BA solver (ba_plan_pcg, enqueue_lm), the extractor (snk_orb_configure, run_part, run_pipeline) and the batched
+// projection matchers call these functions and keep no copy of the conditions; the environment switches are read there and passed in.
 #pragma once
 #include <cstddef>
+
+#include "orb_layout.hpp"
 
 #ifndef SNK_POSE_RED_STEPS  // DPP steps of pose_kernel's 27 sums before they meet in LDS: 4 = rows of 16 lanes, 2 = quads (pose.hip)
 #define SNK_POSE_RED_STEPS 2
@@ -487,6 +490,358 @@ inline BaLmPlan ba_lm_plan(const BaShape& s, const BaSwitches& sw, bool recordin
         P.schur = B < BA_SCHUR_WIDE_BATCH_END && nb * B <= BA_SCHUR_WIDE_MAX_BLOCKS && !sw.no_schur_wide ? BaSchurForm::pass4 : BaSchurForm::pass1;
     }
     ba_plan_pcg_stage(P, s, sw, recording);
+    return P;
+}
+
+// ---- ORB extractor (orb.hip: snk_orb_configure, run_part, run_pipeline; the geometry is orb_layout.hpp's) ----------------------------
+// Every SNK_ORB_* switch.  orb.hip fills one per process (orb_switches()); SNK_DEBUG is read per call.
+struct OrbSwitches
+{
+    bool balanced_strips  = false;  // BALANCED_STRIPS: the round-1..4 strip layout (equal strips of a multiple of 4 columns)
+    int fast_surv_cap     = 0;      // FAST_SURV_CAP: quick-test survivors kept at a time, at least 128 (0: by the cell size; tests force the spill path)
+    int parts             = 1;      // PARTS: launch chains per batch a handle starts with, 1..4
+    int stagger           = 0;      // STAGGER: parts of the staggered schedule a handle starts with, 2..16 (0: off)
+    bool blur_in_describe = false;  // BLUR_IN_DESCRIBE: experiment (round 5): no blurred plane, describe_kernel<true> blurs its patch
+    bool blur_tiled       = false;  // BLUR_TILED: experiment (round 6): blurred planes tiled 32 x 4, see orb_blur_mode
+    bool desc_no_dma      = false;  // DESC_NO_DMA: A/B: describe_kernel's register path instead of the patch by LDS-DMA
+    bool desc_fake_on     = false;  // DESC_FAKE: timing experiments: describe_kernel leaves out a phase ...
+    int desc_fake         = 0;      // ... this one (the variable's value)
+    bool unfused          = false;  // UNFUSED: A/B: stand-alone resize_kernel + blur-only passes
+    int level_bh          = 0;      // LEVEL_BH: A/B, tests: 64 / 22 / 8 rows per band of level_kernel (anything else: by the launch size)
+    int fast_cpw          = 0;      // FAST_CPW: FAST cells per wavefront, 1..64 (anything else: by the launch size)
+    int fast_stop         = 0;      // FAST_STOP: timing experiments: fast_kernel returns after a phase
+    size_t fast_lds_wg    = 0;      // FAST_LDS_WG: experiment (round 4): fast_kernel asks for at least this much LDS per workgroup
+    bool dist_timing      = false;  // DIST_TIMING (diagnostic): distribute_kernel's cycles per phase and level on stderr
+    bool dist_key_loop    = false;  // DIST_KEY_LOOP: A/B: subdivision keys by the loop form, not from the tables
+    bool harris_per_cell  = false;  // HARRIS_PER_CELL: A/B: harris_kernel, one wavefront per cell (round 5), instead of harris_dense_kernel
+    bool one_stream       = false;  // ONE_STREAM: every batch as one launch chain, whatever the handle's schedule
+};
+
+// Layout of the blurred planes for this process (level_kernel writes it, describe_kernel reads it -- both ask here): 0 = row-major (the
+// default), 2 = tiled 32 x 4 (SNK_ORB_BLUR_TILED=1, an experiment of round 6: built, bit-exact, MEASURED SLOWER -- describe_kernel
+// 1.39 -> 1.32 ms, but level_kernel's stores, 16-byte pieces of 47 lines per row instead of two whole lines, cost 1.50 -> 1.74 ms:
+// 191.6 -> 187.9 k frames/s, profiles/r06/r06p_ab_blur_tiled_negative.txt), 1 = no blurred plane (SNK_ORB_BLUR_IN_DESCRIBE=1).
+inline int orb_blur_mode(const OrbSwitches& sw)
+{
+    return sw.blur_in_describe ? 1 : (sw.blur_tiled && !sw.desc_no_dma && !sw.desc_fake_on) ? 2 : 0;
+}
+
+constexpr int ORB_WAVE_SLOTS       = 8192;  // wavefront slots of the chip: 256 CUs x 32
+constexpr int ORB_BAND_MIN_WAVES   = 2048;  // strips x bands of a level pass from which the next taller band is taken
+constexpr int ORB_FAST_CPW_DEFAULT = 8;     // FAST cells per wavefront for big launches (measured in DESIGN.md section 5)
+constexpr int ORB_FAST_MIN_ROUNDS  = 4;     // ... that still give every wavefront slot of the chip this many wavefronts
+constexpr int ORB_XCD_MIN_BATCH    = 16;    // images from which a grid keeps an image's workgroups on one XCD (xcd_image_map)
+constexpr int ORB_DIST_ONE_MAX_WGS = 128;   // (image, level) workgroups up to which each takes the full-budget carve at once
+constexpr int ORB_DIST_LARGE_WGS   = 256;   // workgroups of the drain launch, at most
+constexpr int ORB_HARRIS_NC        = 16;    // cells whose candidates harris_dense_kernel packs into a wavefront
+constexpr int ORB_DESC_KPW         = 4;     // keypoints per wavefront of describe_kernel
+
+// level_kernel<., BH>: rows per band
+enum class OrbBandForm { bh64, bh22, bh8 };
+// fast_kernel<NQ, LOOP>: one cell per wavefront | a loop over cpw cells; 0 / 3 / 4: tile pitches from the layout | of 3 / 4 quads
+enum class OrbFastForm { single0, single3, single4, loop0, loop3, loop4 };
+// Harris response ("orb.response" = 1): harris_kernel | harris_dense_kernel
+enum class OrbHarrisForm { none, per_cell, dense };
+// distribute_kernel at the full carve alone | at the small carve alone (level_cap <= 2048) | at the small carve, then distribute_large_kernel
+enum class OrbDistForm { one_full, one_small, small_drain };
+// describe_kernel<BLUR_IN, DMA, TILED>: <0,0,0> | <1,0,0> | <0,1,0> | <0,1,1>
+enum class OrbDescForm { registers, blur_in, dma, dma_tiled };
+// run_pipeline: one launch chain | `n` chains on as many streams | `n` parts, front halves on one stream and back halves on a second
+enum class OrbSchedule { one_chain, chains, staggered };
+
+inline const char* orb_name(OrbBandForm f)
+{
+    static const char* const n[] = {"bh64", "bh22", "bh8"};
+    return n[(int)f];
+}
+inline const char* orb_name(OrbFastForm f)
+{
+    static const char* const n[] = {"single0", "single3", "single4", "loop0", "loop3", "loop4"};
+    return n[(int)f];
+}
+inline const char* orb_name(OrbHarrisForm f)
+{
+    static const char* const n[] = {"none", "per_cell", "dense"};
+    return n[(int)f];
+}
+inline const char* orb_name(OrbDistForm f)
+{
+    static const char* const n[] = {"one_full", "one_small", "small_drain"};
+    return n[(int)f];
+}
+inline const char* orb_name(OrbDescForm f)
+{
+    static const char* const n[] = {"registers", "blur_in", "dma", "dma_tiled"};
+    return n[(int)f];
+}
+inline const char* orb_name(OrbSchedule f)
+{
+    static const char* const n[] = {"one_chain", "chains", "staggered"};
+    return n[(int)f];
+}
+
+// XCD-aware grids (orb.hip, xcd_image_map): from 16 images on, grid.x = 8 * gx and eight images share a grid row
+inline void orb_xcd_grid(int gx, int batch, int& x, int& y)
+{
+    x = batch >= ORB_XCD_MIN_BATCH ? 8 * gx : gx;
+    y = batch >= ORB_XCD_MIN_BATCH ? (batch + 7) / 8 : batch;
+}
+
+// Rows per band of a level pass: 64 when the launch fills the chip's 8192 wavefront slots anyway, else 22, else 8 (per-frame calls: a
+// wavefront walks its band row by row behind a chain of load latencies).  bh_env: SNK_ORB_LEVEL_BH.
+inline OrbBandForm orb_band_form(int n_strips, int h, int batch, int bh_env)
+{
+    if (bh_env == 64) return OrbBandForm::bh64;
+    if (bh_env == 22) return OrbBandForm::bh22;
+    if (bh_env == 8) return OrbBandForm::bh8;
+    const long long strips = (long long)n_strips * batch;
+    return strips * orb::cdiv(h, 64) >= ORB_BAND_MIN_WAVES ? OrbBandForm::bh64 : strips * orb::cdiv(h, 22) >= ORB_BAND_MIN_WAVES ? OrbBandForm::bh22 : OrbBandForm::bh8;
+}
+constexpr int orb_band_rows(OrbBandForm f) { return f == OrbBandForm::bh64 ? 64 : f == OrbBandForm::bh22 ? 22 : 8; }
+
+// FAST cells per wavefront: 1 for small launches (keep the chip filled), more once there are plenty of workgroups -- at least four
+// rounds of the chip's wavefront slots.  cpw_env: SNK_ORB_FAST_CPW, forced whatever the launch size (tests, measurements).
+inline int orb_fast_cpw(int total_cells, int batch, int cpw_env)
+{
+    if (cpw_env >= 1 && cpw_env <= 64) return cpw_env;
+    const long long cell_waves = (long long)total_cells * batch;
+    int cpw = ORB_FAST_CPW_DEFAULT;
+    while (cpw > 1 && cell_waves / cpw < (long long)ORB_WAVE_SLOTS * ORB_FAST_MIN_ROUNDS) cpw >>= 1;
+    return cpw;
+}
+inline OrbFastForm orb_fast_form(int quads, bool loop)
+{
+    const int q = quads == 3 ? 1 : quads == 4 ? 2 : 0;
+    return (OrbFastForm)((loop ? 3 : 0) + q);
+}
+
+// harris: "orb.response" = 1; per_cell: SNK_ORB_HARRIS_PER_CELL
+inline OrbHarrisForm orb_harris_form(int total_cells, bool harris, bool per_cell)
+{
+    return !harris || total_cells <= 0 ? OrbHarrisForm::none : per_cell ? OrbHarrisForm::per_cell : OrbHarrisForm::dense;
+}
+
+// A launch of a few (image, level) workgroups (the per-frame calls) gives every workgroup the full-budget carve at once: nothing can
+// be queued, the drain launch is skipped (one launch less in the per-frame chain; the carve only limits workgroups per CU, and these
+// launches do not fill the chip).  Not under "orb.response" = 1: the Harris ranks do not fit beside the full carve.
+inline OrbDistForm orb_dist_form(int n_levels, int batch, int level_cap, bool harris)
+{
+    if (orb::dist_small_cap(level_cap) >= level_cap) return OrbDistForm::one_small;
+    return !harris && (long long)n_levels * batch <= ORB_DIST_ONE_MAX_WGS ? OrbDistForm::one_full : OrbDistForm::small_drain;
+}
+
+// round 6: the blurred patch by LDS-DMA (describe_kernel<false, true>; same-box A/B 1.457 -> 1.398 ms per 2048 images,
+// profiles/r06/r06c_ab_describe_lds_dma.txt)
+inline OrbDescForm orb_desc_form(const OrbSwitches& sw)
+{
+    if (sw.blur_in_describe) return OrbDescForm::blur_in;
+    if (sw.desc_no_dma) return OrbDescForm::registers;
+    return orb_blur_mode(sw) == 2 ? OrbDescForm::dma_tiled : OrbDescForm::dma;
+}
+
+// Launch chains of a batch: one by default.  Two half-batch chains on two streams (snk_orb_set_chains) overlap the tails of one chain's
+// launches with the other's kernels: 186.0 / 192.1 / 192.9 / 188.4 k frames/s with 1 / 2 / 3 / 4 chains in one run, 187.6 k with 2 in
+// the next (profiles/r05/r05o_chains.txt, r05p_bench_two_chains_by_default.txt) -- the chains start together and mostly run the same
+// stage at the same time, so the gain is the tails only and a kernel's duration is then measured under a concurrent copy of itself.
+// Tried as the default for big batches in round 5 and taken back.  Per-frame launches never split (and never create the extra streams).
+// parts, stagger: the handle's (snk_orb_set_chains, snk_orb_set_stagger; SNK_ORB_PARTS, SNK_ORB_STAGGER at its creation).
+// n: chains, or parts of the staggered schedule.
+inline OrbSchedule orb_schedule(int batch, int parts, int stagger, int split_min_batch, bool one_stream, int& n)
+{
+    n = 1;
+    const bool stag = stagger >= 2 && batch >= 2 * stagger;
+    if (one_stream || batch < split_min_batch || !(parts > 1 || stag)) return OrbSchedule::one_chain;
+    if (stag) return n = stagger, OrbSchedule::staggered;
+    n = parts < batch ? parts : batch;
+    return n > 1 ? OrbSchedule::chains : OrbSchedule::one_chain;
+}
+
+struct OrbLevelPlan
+{
+    bool skipped      = true;   // a level scaled down to nothing (small image, many levels): no pixels, no cells
+    bool resize_first = false;  // stand-alone resize_kernel from level l - 1 (no in-stream down-scale there)
+    bool tiny         = false;  // below 8 x 8: only down-scaled, never blurred (outside the domain of the streaming pass's reflect-101 halo)
+    OrbBandForm band  = OrbBandForm::bh8;
+    bool aligned      = true;   // level_kernel<true, .>; false: level 0 of an input whose base / pitch is not a multiple of 4
+    int n_bands = 0, gx = 0;
+    bool make_next    = false;  // the pass also writes level l + 1
+};
+struct OrbPlan
+{
+    int n_levels = 0, blur_mode = 0;
+    OrbLevelPlan lv[orb::MAX_LEVELS];
+    bool fast_run     = false;  // the layout has FAST cells
+    OrbFastForm fast  = OrbFastForm::single0;
+    int fast_cpw = 1, fast_quads = 0, fast_gx = 0;
+    size_t fast_lds   = 0;
+    OrbHarrisForm harris = OrbHarrisForm::none;
+    int harris_gx     = 0;
+    OrbDistForm dist  = OrbDistForm::one_small;
+    int dist_lds_cap  = 0;      // candidates of a level the first launch's carve holds
+    size_t dist_lds = 0, dist_large_lds = 0;
+    int large_workers = 0;
+    // the queue's counter: reset by fast_kernel when the call enqueues the whole chain on one stream (the usual case: one launch less
+    // per frame); the split schedules (front and back halves on different streams, chain slots shared by parts) keep the fill
+    bool queue_memset = true;
+    OrbDescForm desc  = OrbDescForm::dma;
+    int desc_gx = 0, desc_nb = 0, dfake = 0;
+};
+
+// A level in the plan line of run_part (SNK_DEBUG) and of tests/cpp/dispatch_driver.cpp: "-" skipped, else "r" (resize_kernel first) and
+// "t" (tiny) or the rows per band, "u" (unaligned) and "+" (the pass also writes level l + 1) -- "64+", "r22u", "rt"
+inline void orb_level_token(const OrbLevelPlan& p, char out[8])
+{
+    int n = 0;
+    if (p.skipped) out[n++] = '-';
+    else
+    {
+        if (p.resize_first) out[n++] = 'r';
+        if (p.tiny) out[n++] = 't';
+        else
+        {
+            const int bh = orb_band_rows(p.band);
+            if (bh >= 10) out[n++] = (char)('0' + bh / 10);
+            out[n++] = (char)('0' + bh % 10);
+            if (!p.aligned) out[n++] = 'u';
+            if (p.make_next) out[n++] = '+';
+        }
+    }
+    out[n] = 0;
+}
+
+// One launch chain over `batch` images.  aligned0: base, pitch and stride of the caller's images are multiples of 4; harris:
+// "orb.response" = 1; stages: 1 = the front half (pyramid / blur passes + FAST cells), 2 = the back half (distribution + descriptors),
+// 3 = both.
+inline OrbPlan orb_plan(const Layout& L, int batch, bool aligned0, bool harris, int stages, float scale_factor, const OrbSwitches& sw)
+{
+    OrbPlan P;
+    P.n_levels  = L.n_levels;
+    P.blur_mode = orb_blur_mode(sw);
+    const bool fused_ok = scale_factor <= 2.0f && !sw.unfused;  // the in-stream down-scale reaches 3 * scale + 1 columns right
+    const auto tiny     = [&](int l) { return L.lv[l].w < 8 || L.lv[l].h < 8; };
+    for (int l = 0; l < L.n_levels; ++l)
+    {
+        const LevelInfo& lv = L.lv[l];
+        OrbLevelPlan& p     = P.lv[l];
+        if (lv.w <= 0 || lv.h <= 0) continue;
+        p.skipped      = false;
+        p.resize_first = l > 0 && (!fused_ok || tiny(l - 1));
+        p.tiny         = tiny(l);
+        if (p.tiny) continue;
+        p.band      = orb_band_form(lv.n_strips, lv.h, batch, sw.level_bh);
+        p.n_bands   = orb::cdiv(lv.h, orb_band_rows(p.band));
+        p.gx        = orb::cdiv(lv.n_strips * p.n_bands, 4);
+        p.aligned   = l > 0 || aligned0;
+        p.make_next = fused_ok && l + 1 < L.n_levels && L.lv[l + 1].w > 0 && L.lv[l + 1].h > 0;
+    }
+    P.fast_run = L.total_cells > 0;
+    if (P.fast_run)
+    {
+        P.fast_cpw   = orb_fast_cpw(L.total_cells, batch, sw.fast_cpw);
+        P.fast_quads = orb::fast_quads(L);
+        P.fast       = orb_fast_form(P.fast_quads, P.fast_cpw > 1);
+        P.fast_gx    = orb::cdiv(L.total_cells, 4 * P.fast_cpw);
+        // occupancy shaping (experiment, round 4): a workgroup that asks for at least SNK_ORB_FAST_LDS_WG bytes of LDS caps how many
+        // FAST workgroups a CU holds, so that back-half workgroups of another stream (staggered schedule) find room beside them
+        const size_t own = (size_t)4 * L.f_lds_wave, asked = sw.fast_lds_wg < (size_t)orb::LDS_BYTES ? sw.fast_lds_wg : (size_t)orb::LDS_BYTES;
+        P.fast_lds       = own > asked ? own : asked;
+    }
+    P.harris = orb_harris_form(L.total_cells, harris, sw.harris_per_cell);
+    if (P.harris == OrbHarrisForm::per_cell) P.harris_gx = orb::cdiv(L.total_cells, 4);
+    if (P.harris == OrbHarrisForm::dense) P.harris_gx = orb::cdiv(orb::cdiv(L.total_cells, ORB_HARRIS_NC), 4);
+    P.queue_memset = stages != 3 || !P.fast_run;
+    P.dist         = orb_dist_form(L.n_levels, batch, L.level_cap, harris);
+    const int small_cap = orb::dist_small_cap(L.level_cap);
+    P.dist_lds_cap   = P.dist == OrbDistForm::one_full ? L.level_cap : small_cap;
+    P.dist_lds       = P.dist == OrbDistForm::one_full ? orb::dist_lds_bytes((size_t)L.level_cap)
+                                                       : orb::dist_lds_bytes((size_t)small_cap) + (harris ? orb::dist_harris_bytes((size_t)small_cap) : 0);
+    P.dist_large_lds = orb::dist_lds_bytes((size_t)L.level_cap);
+    P.large_workers  = L.n_levels * batch < ORB_DIST_LARGE_WGS ? L.n_levels * batch : ORB_DIST_LARGE_WGS;
+    int max_slot = 1;
+    for (int l = 0; l < L.n_levels; ++l) max_slot = L.lv[l].slot_cap > max_slot ? L.lv[l].slot_cap : max_slot;
+    P.desc    = orb_desc_form(sw);
+    P.desc_gx = orb::cdiv(max_slot, 4 * ORB_DESC_KPW);
+    P.desc_nb = batch >= ORB_XCD_MIN_BATCH ? 8 * orb::cdiv(batch, 8) : batch;
+    P.dfake   = sw.desc_fake;
+    return P;
+}
+
+// ---- projection matchers (track.hip: snk_match_project_coarse_batch_dev, fine_batch_impl and the host entries) -----------------------
+struct TrackSwitches
+{
+    bool no_frame_lds     = false;  // SNK_TRACK_NO_FRAME_LDS: A/B: the batched matchers with global-memory gathers
+    int frame_wgs         = 0;      // SNK_TRACK_FRAME_WGS: A/B, tests: workgroups per frame of the frame-resident matchers (0: by the batch)
+    bool no_fused_resolve = false;  // SNK_TRACK_NO_FUSED_RESOLVE: A/B, tests: always the separate resolution
+    int ppw               = 0;      // SNK_TRACK_PPW: tests: points per wavefront, 1..64 (anything else: by the number of points)
+};
+
+constexpr int TRACK_FRAME_LDS_MAX = 144 * 1024;  // LDS carve of the frame-resident matchers (one workgroup per CU above 80 KB)
+constexpr int TRACK_CHUNK_POINTS  = 1024;        // points of the local map a workgroup of the frame-resident matchers takes at a time
+constexpr int TRACK_PPW_POINTS    = 8192;        // points of a call per point of a wavefront
+
+// LDS of a frame of `cap` features over a grid of ncell1 - 1 cells: keypoints (24 B), descriptors (32 B), right points, taken flags, cell starts
+constexpr size_t track_frame_lds(int cap, int ncell1)
+{
+    return (((size_t)cap * 24 + 15) & ~(size_t)15) + (size_t)cap * 32 + (((size_t)cap * 4 + 15) & ~(size_t)15) + (((size_t)cap + 15) & ~(size_t)15) +
+           (size_t)ncell1 * 4 + 64;
+}
+
+// Points per wavefront of the projection matchers: a wavefront does the per-point geometry for `ppw` points at once and, with
+// PJ_GROUP = 1, every lane then scans its own point's window.  Many points per wavefront fill the lanes (throughput of the
+// batched forms), few spread a single frame's points over the chip: for the host calls (one frame, the reference's call
+// pattern) ONE point per wavefront is the lowest latency -- measured on MI355X with the frame bound (tools/latency_track.py,
+// profiles/r03/r03b_latency_track.log): SearchByProjectionFrameFrame2 with 1500 points 0.089 / 0.097 / 0.104 / 0.113 ms and
+// SearchByProjection2 with 10 000 points 0.785 / 0.797 / 0.800 / 0.907 ms at 1 / 4 / 16 / 64 points per wavefront -- a lane's
+// serial window scan is the critical path either way, and more wavefronts only add parallel scans.
+inline int track_points_per_wave(long long total_points, int ppw_env)
+{
+    if (ppw_env >= 1 && ppw_env <= 64) return ppw_env;
+    const long long want = total_points / TRACK_PPW_POINTS;
+    return (int)(want < 1 ? 1 : (want > 64 ? 64 : want));
+}
+
+// Workgroups per frame of the frame-resident matchers: every workgroup stages the frame in LDS once and then walks its share of the
+// local map's 1024-point chunks, so as few as keep the chip's 512 workgroup slots (two 65 KB frames per CU) filled about twice.
+// Measured on the tracking leg of bench.py (1024 frames x 10 000 points, profiles/r04/r04g_track_wgs.log): 10 workgroups per frame
+// (one per chunk, the round-3 form) 537 k frames/s, 5: 582 k, 3: 595 k, 2: 610 k, 1: 611 k.  forced: SNK_TRACK_FRAME_WGS.
+inline int track_frame_wgs(int chunks, int batch, int forced)
+{
+    int wgs = batch > 0 ? (1024 + batch - 1) / batch : chunks;
+    if (forced >= 1) wgs = forced;
+    return wgs < 1 ? 1 : (wgs > chunks ? chunks : wgs);
+}
+
+// Byte offset of the claims inside the LDS carve of a frame-resident matcher that resolves its matches itself, -1 = separate resolution
+// (several workgroups per frame, or the claims do not fit behind the frame).  off: SNK_TRACK_NO_FUSED_RESOLVE.
+inline int track_fused_claim_offset(int wgs, size_t flds, int cap, bool off)
+{
+    const size_t at = (flds + 15) & ~(size_t)15;
+    return (off || wgs != 1 || at + (size_t)cap * 4 > (size_t)TRACK_FRAME_LDS_MAX) ? -1 : (int)at;
+}
+
+// A batched projection matcher over `batch` frames of `cap` features (a grid of ncell1 - 1 cells) and pts_cap points each
+// frame: coarse_frame_kernel / fine_frame_kernel, the frame in LDS;  batch: coarse_batch_kernel / fine_batch_kernel, global-memory gathers
+enum class TrackForm { frame, batch };
+inline const char* track_name(TrackForm f) { return f == TrackForm::frame ? "frame" : "batch"; }
+
+struct TrackBatchPlan
+{
+    TrackForm form = TrackForm::batch;
+    int ppw        = 1;
+    int wgs        = 0;   // frame: workgroups per frame
+    int claim_off  = -1;  // frame: >= 0: the kernel resolves its matches itself
+    size_t lds     = 0;   // frame: the frame, and the claims behind it
+};
+inline TrackBatchPlan track_batch_plan(int pts_cap, int batch, int cap, int ncell1, const TrackSwitches& sw)
+{
+    TrackBatchPlan P;
+    P.ppw             = track_points_per_wave((long long)pts_cap * batch, sw.ppw);
+    const size_t flds = track_frame_lds(cap, ncell1);
+    if (P.ppw != 64 || flds > (size_t)TRACK_FRAME_LDS_MAX || sw.no_frame_lds) return P;
+    P.form      = TrackForm::frame;
+    P.wgs       = track_frame_wgs((pts_cap + TRACK_CHUNK_POINTS - 1) / TRACK_CHUNK_POINTS, batch, sw.frame_wgs);
+    P.claim_off = track_fused_claim_offset(P.wgs, flds, cap, sw.no_fused_resolve);
+    P.lds       = P.claim_off >= 0 ? (size_t)P.claim_off + (size_t)cap * 4 : flds;
     return P;
 }
 }  // namespace snk

@@ -22,7 +22,7 @@
 //                      (v_dot4 against a disc table), polynomial atan2, 256 steered BRIEF tests read from an
 //                      LDS copy of the blurred patch, 4 ballots assemble the 256-bit descriptor
 #include "common.hpp"
-#include "orb_keys.hpp"
+#include "dispatch.hpp"  // the launch plan (orb_plan) over the geometry of orb_layout.hpp: Layout / LevelInfo / LevelHead, the kernels' argument
 
 #include <array>
 #include <vector>
@@ -31,25 +31,20 @@ namespace snk
 {
 namespace
 {
+using namespace orb;  // MAX_LEVELS, EDGE_THRESHOLD, MIN_BORDER, CELL_W, CELL_SLOTS, SM_LANES_OUT
 using u8  = unsigned char;
 using u16 = unsigned short;
 using u32 = unsigned int;
 using u64 = unsigned long long;
 
-constexpr int MAX_LEVELS     = 16;
-constexpr int EDGE_THRESHOLD = 19;
-constexpr int MIN_BORDER     = 16;
-constexpr int CELL_W         = 30;
-constexpr int CELL_SLOTS     = 64;   // strongest candidates kept per cell
 constexpr int KEY_DIGITS     = 16;
-constexpr int DEFAULT_LEVEL_CAP = 8192;
 #ifndef SNK_DIST_MIN_WAVES
 #define SNK_DIST_MIN_WAVES 1  // build-time A/B: 8 = distribute_kernel must fit four 512-thread workgroups per CU (<= 64 VGPRs, <= 80 SGPRs)
 #endif
 #ifndef SNK_FAST_MIN_WAVES
 #define SNK_FAST_MIN_WAVES 1  // build-time A/B: wavefronts per SIMD the register allocator must leave room for in fast_kernel
 #endif
-constexpr int FAST_CPW_DEFAULT  = 8;     // FAST cells per wavefront for big launches (SNK_ORB_FAST_CPW; measured in DESIGN.md section 5)
+static_assert(LDS_BYTES == LDS_MAX_BYTES, "orb_layout.hpp and common.hpp agree on the LDS of a workgroup");
 
 constexpr signed char k_pattern[1024] = {
 #include "brief_pattern_31.inc"
@@ -105,58 +100,11 @@ constexpr MomentTab make_moment_tab()
 }
 __device__ const MomentTab c_moment = make_moment_tab();
 
-struct LevelInfo
-{
-    int w, h, pitch;
-    long long img_stride;  // bytes between consecutive images of this level
-    u8* base;              // level buffer (levels >= 1); level 0 comes from the caller
-    u8* blur;              // blurred level (all levels), same pitch / stride as the level buffers
-    int strip_stride, n_strips, n_bands, unit_off;  // streaming pass: column strips x row bands of this level
-    int store_end;         // the last strip writes the blurred row up to this column (>= w: into the row padding, whole 64-byte sectors)
-    const int* ymap;      // [h] destination row of level l+1 whose upper source row is this row, or -1
-    const int* strip_dx;  // [n_strips + 1] first destination dword (4 px) of level l+1 owned by each strip
-    int ncols, nrows, wcell, hcell;
-    int cell_off;          // first cell of this level in the per-image cell arrays
-    int nfeat;             // features wanted on this level
-    int slot_off, slot_cap;  // per-image slots for the selected keypoints of this level
-    int nroots;
-    float scale;
-    const int* xofs;  // resize tables (device): source column / weight per destination column
-    const int* xw1;
-    const int* yofs;
-    const int* yw1;
-    long long blur_stride;  // bytes between consecutive images of the BLURRED level: pitch x (h rounded up to 4) -- room for the tiled layout
-};
-
 // Tiled layout of the blurred planes (round 6, an EXPERIMENT -- see orb_blur_mode): a 128-byte line holds 32 pixels x 4 rows, so the
 // 37 x 40-pixel patch describe_kernel reads per keypoint touches ~23 lines instead of ~51 (measured upper bound with contiguous
 // patches: 1.39 -> 1.135 ms, profiles/r06/r06o_*).  Byte of pixel (x, y): (y >> 2) * 4 * pitch + (x >> 5) * 128 + (y & 3) * 32 + (x & 31).
 __device__ __forceinline__ u32 blur_tiled_x(int x) { return (u32)(((x >> 5) << 7) + (x & 31)); }
 __device__ __forceinline__ u32 blur_tiled_y(int y, int pitch) { return (u32)((y >> 2) * 4 * pitch + ((y & 3) << 5)); }
-
-// what fast_kernel reads of a level: the head of LevelInfo, taken with one 32-byte load
-struct LevelHead
-{
-    int w, h, pitch, pad_;
-    long long img_stride;
-    u8* base;
-};
-static_assert(sizeof(LevelHead) == 32 && offsetof(LevelInfo, w) == 0 && offsetof(LevelInfo, h) == 4 && offsetof(LevelInfo, pitch) == 8 &&
-                  offsetof(LevelInfo, img_stride) == 16 && offsetof(LevelInfo, base) == 24,
-              "LevelHead mirrors the first 32 bytes of LevelInfo");
-
-struct Layout
-{
-    int n_levels;
-    int total_cells;
-    int total_slots;
-    int total_units;
-    int level_cap;
-    // per-wavefront LDS slice of fast_kernel (bytes; sized from the largest cell of the layout)
-    int f_tile_pitch_dw, f_s_pitch, f_off_s, f_off_surv, f_off_list, f_off_cnt, f_lds_wave, f_surv_cap;
-    const int4* cell_tab;  // [total_cells] (x0, y0, cw | ch << 16, level) of every FAST cell: one scalar load instead of a level search and two integer divisions per cell
-    LevelInfo lv[MAX_LEVELS];
-};
 
 // ------------------------------------------------------------------------------------------------
 // pyramid
@@ -435,7 +383,12 @@ __device__ __forceinline__ bool xcd_image_map(int gx, int batch, int& b, int& bx
     (void)gx;
     return b < batch;
 }
-static inline dim3 xcd_grid(int gx, int batch) { return batch >= 16 ? dim3(8 * gx, (batch + 7) / 8) : dim3(gx, batch); }
+static inline dim3 xcd_grid(int gx, int batch)
+{
+    int x, y;
+    orb_xcd_grid(gx, batch, x, y);
+    return dim3(x, y);
+}
 
 // One WAVEFRONT per FAST cell (4 cells per workgroup, no workgroup barriers: the phases of a cell
 // only communicate through that wavefront's own LDS slice, which the LDS serves in program order).
@@ -822,18 +775,19 @@ __global__ __launch_bounds__(256, SNK_FAST_MIN_WAVES) void fast_kernel(Layout L,
     }
 }
 
-static inline int fast_quads(const Layout& L)
+using FastKernel = void (*)(Layout, const u8*, int, long long, int, int, int, u32*, u16*, int, int, int, int, int*);
+static inline FastKernel fast_kernel_of(OrbFastForm f)
 {
-    return L.f_tile_pitch_dw == 12 && L.f_s_pitch == 40 ? 3 : (L.f_tile_pitch_dw == 16 && L.f_s_pitch == 64 ? 4 : 0);
-}
-static inline const void* fast_kernel_for(const Layout& L, bool loop)
-{
-    const int fq = fast_quads(L);
-    if (loop)
-        return fq == 3 ? reinterpret_cast<const void*>(fast_kernel<3, true>)
-                       : (fq == 4 ? reinterpret_cast<const void*>(fast_kernel<4, true>) : reinterpret_cast<const void*>(fast_kernel<0, true>));
-    return fq == 3 ? reinterpret_cast<const void*>(fast_kernel<3, false>)
-                   : (fq == 4 ? reinterpret_cast<const void*>(fast_kernel<4, false>) : reinterpret_cast<const void*>(fast_kernel<0, false>));
+    switch (f)
+    {
+    case OrbFastForm::loop3: return fast_kernel<3, true>;
+    case OrbFastForm::loop4: return fast_kernel<4, true>;
+    case OrbFastForm::loop0: return fast_kernel<0, true>;
+    case OrbFastForm::single3: return fast_kernel<3, false>;
+    case OrbFastForm::single4: return fast_kernel<4, false>;
+    case OrbFastForm::single0: return fast_kernel<0, false>;
+    }
+    return nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -949,7 +903,7 @@ __global__ __launch_bounds__(256) void harris_kernel(Layout L, const u8* __restr
 // a batch under "orb.response" = 1.  Here a wavefront takes 16 cells: the counts of the cells are scanned across lanes 0..15, lane i
 // of a round finds (cell, slot) of the group's i-th candidate in the scan, the level of its cell by a select over the levels (the
 // cells of a group may lie on two levels), and reads each of the 9 rows with ONE 12-byte load.  Same integers, same float expression.
-constexpr int HARRIS_NC = 16;
+constexpr int HARRIS_NC = ORB_HARRIS_NC;
 typedef u32 u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
 __global__ __launch_bounds__(256) void harris_dense_kernel(Layout L, const u8* __restrict__ img0, int pitch0, long long stride0, int aligned0,
                                                            const u32* __restrict__ cand, const u16* __restrict__ cell_cnt,
@@ -1070,12 +1024,10 @@ __global__ __launch_bounds__(256) void harris_dense_kernel(Layout L, const u8* _
 // 248-byte store per row.  Per row: neighbour dwords by lane shuffle, horizontal pass with
 // v_alignbyte + v_dot4_u32_u8 (exact 16-bit rows), vertical pass over the register window, one rounding.
 // ------------------------------------------------------------------------------------------------
-constexpr int SM_BH        = 64;         // output rows per band (big launches); BH + 6 rows are streamed per band, a multiple of 14
-                                          // so that the 7-row window index stays static.  Small launches (the per-frame calls: one or two
-                                          // images) use bands of 22 or 8 rows: a wavefront walks its band row by row behind a chain of
-                                          // load latencies, and a 752x480 level with 64-row bands is 32 wavefronts of 70 rows each --
-                                          // 22 us per level on an otherwise empty chip (profiles/r04/r04j_*); same arithmetic per pixel.
-constexpr int SM_LANES_OUT = 61;  // strip <= 244 columns: 8 loaded columns remain to the right for the down-scale taps
+// Bands: 64 output rows (big launches); BH + 6 rows are streamed per band, a multiple of 14 so that the 7-row window index stays static.
+// Small launches (the per-frame calls: one or two images) use bands of 22 or 8 rows (dispatch.hpp, orb_band_form): a wavefront walks its
+// band row by row behind a chain of load latencies, and a 752x480 level with 64-row bands is 32 wavefronts of 70 rows each -- 22 us per
+// level on an otherwise empty chip (profiles/r04/r04j_*); same arithmetic per pixel.
 
 // The same pass also produces level l+1 (make_next): whenever the stream holds source rows sy, sy+1
 // of a destination row, the two raw rows go to a 512-byte LDS buffer of the wavefront and every lane
@@ -2073,7 +2025,7 @@ __device__ __forceinline__ int wave_sum(int v)
 // patch that the steered tests can reach (|rotated offset| <= 18).  Moments: v_dot4 against the disc
 // table (LDS copy); the patch goes to the wavefront's LDS slice and the 512 test bytes are LDS reads;
 // 4 ballots assemble the descriptor.
-constexpr int DESC_KPW    = 4;
+constexpr int DESC_KPW    = ORB_DESC_KPW;
 constexpr int PATCH_R     = 18, PATCH_DW = 12;                  // 37 rows x 12 dwords (10 needed): a row is 3 lanes x 16 bytes
 constexpr int PATCH_QUADS = (2 * PATCH_R + 1) * 3;              // 111 sixteen-byte items -> 2 loads per lane
 constexpr int PATCH_ITEMS = (2 * PATCH_R + 1) * PATCH_DW;
@@ -2543,8 +2495,6 @@ struct snk_orb : HandleBase
     DevBuf out_kps;          // host-API staging: [count | pad to 64 B][cap keypoints][cap descriptors], fetched with ONE copy
     HostBuf h_out, h_img;    // pinned mirrors of out_kps / img0
     int pitch0_host = 0;
-    size_t dist_lds = 0, dist_lds_small = 0;
-    int dist_small_cap = 0;
     // optional per-stage timing with HIP events on the handle's stream (bench.py roofline leg)
     bool profiling = false;
     std::vector<std::array<hipEvent_t, 7>> ev_sets;  // pyramid | blur | fast | distribute | describe boundaries; [6] = start of the back half (staggered schedule)
@@ -2565,130 +2515,35 @@ struct snk_orb : HandleBase
     size_t part_ev[MAX_STAGGER]      = {};  // event set of each part of the current call (profiling)
 };
 
-static int compute_layout(snk_orb* o, int w, int h)
+// The ONE reader of the extractor's switches (OrbSwitches in dispatch.hpp names each), filled at the first use in a process.
+static const OrbSwitches& orb_switches()
 {
-    const snk_orb_params& p = o->params;
-    Layout& L               = o->lay;
-    memset(&L, 0, sizeof(L));
-    L.n_levels  = p.n_levels;
-    L.level_cap = p.level_cap > 0 ? p.level_cap : DEFAULT_LEVEL_CAP;
-    float scale[MAX_LEVELS];
-    scale[0] = 1.0f;
-    for (int l = 1; l < p.n_levels; ++l) scale[l] = scale[l - 1] * p.scale_factor;
-    // ORB-SLAM2 constructor arithmetic (float)
-    const float factor = 1.0f / p.scale_factor;
-    float n_desired    = (float)p.nfeatures * (1.0f - factor) / (1.0f - (float)pow((double)factor, (double)p.n_levels));
-    int sum            = 0;
-    int cell_off = 0, slot_off = 0, tile_off = 0;
-    for (int l = 0; l < p.n_levels; ++l)
+    static const OrbSwitches once = []
     {
-        LevelInfo& lv = L.lv[l];
-        const float inv = 1.0f / scale[l];
-        lv.w     = (int)lrintf((float)w * inv);
-        lv.h     = (int)lrintf((float)h * inv);
-        lv.scale = scale[l];
-        if (l < p.n_levels - 1)
-        {
-            lv.nfeat = (int)lrintf(n_desired);
-            sum += lv.nfeat;
-            n_desired *= factor;
-        }
-        else
-            lv.nfeat = p.nfeatures - sum > 0 ? p.nfeatures - sum : 0;
-        const int width = lv.w - 2 * MIN_BORDER, height = lv.h - 2 * MIN_BORDER;
-        lv.ncols = width > 0 ? width / CELL_W : 0;
-        lv.nrows = height > 0 ? height / CELL_W : 0;
-        if (lv.ncols < 1 || lv.nrows < 1 || lv.w < 2 * EDGE_THRESHOLD + 1 || lv.h < 2 * EDGE_THRESHOLD + 1)
-        {
-            lv.ncols = lv.nrows = 0;
-            lv.wcell = lv.hcell = 1;
-        }
-        else
-        {
-            lv.wcell = (width + lv.ncols - 1) / lv.ncols;
-            lv.hcell = (height + lv.nrows - 1) / lv.nrows;
-        }
-        lv.cell_off = cell_off;
-        cell_off += lv.ncols * lv.nrows;
-        const int nroots = orb_key_nroots(width, height);  // orb_keys.hpp: the root count the key tables are filled with
-        lv.nroots        = nroots;
-        lv.slot_off = slot_off;
-        lv.slot_cap = lv.nfeat + 3 > 4 * nroots ? lv.nfeat + 3 : 4 * nroots;
-        slot_off += lv.slot_cap;
-        lv.pitch      = (lv.w + 63) & ~63;
-        lv.img_stride = (long long)lv.pitch * lv.h;
-        lv.blur_stride = (long long)lv.pitch * ((lv.h + 3) & ~3);
-        // streaming blur: balanced strips of <= 62 dwords, bands of 64 rows
-        if (lv.w > 0 && lv.h > 0)
-        {
-            // Strips START on 64-byte boundaries of the row (stride 192 columns; the last strip takes what is left, up to the 244 columns a
-            // wavefront can produce): a wavefront's row store then never shares a 64-byte sector with its neighbour strip's.  Round 5,
-            // tools/probes/hbm_write_shapes.sh: rows written as 4 x 188-byte strips (the balanced layout of a 752-px level) reach 3.3 TB/s,
-            // as 4 x 192-byte strips 5.1 TB/s.  SNK_ORB_BALANCED_STRIPS=1: the round-1..4 layout (equal strips of a multiple of 4 columns).
-            static const bool balanced = getenv("SNK_ORB_BALANCED_STRIPS") != nullptr;
-            if (balanced || lv.w <= 4 * SM_LANES_OUT)
-            {
-                lv.n_strips     = ceil_div(lv.w, 4 * SM_LANES_OUT);
-                lv.strip_stride = ((ceil_div(lv.w, lv.n_strips) + 3) / 4) * 4;
-            }
-            else
-            {
-                lv.strip_stride = 192;
-                lv.n_strips     = 1 + ceil_div(lv.w - 4 * SM_LANES_OUT, 192);
-            }
-            // The last strip's blurred store runs on to the end of the row pitch when its 61 lanes reach it (EuRoC levels 0 and 2: 576 + 192 =
-            // 768, 384 + 192 = 576): whole 64-byte sectors instead of a ragged end; the padding columns hold reflected-border blur values
-            // nobody reads.  +0.4 % end to end; one more 192-column strip wherever the rest exceeds 192 columns instead: -1.5 %
-            // (profiles/r05/r05z_strip_store_end.json).
-            lv.store_end = lv.w;
-            if (!balanced && lv.w > 4 * SM_LANES_OUT && lv.pitch - (lv.n_strips - 1) * lv.strip_stride <= 4 * SM_LANES_OUT) lv.store_end = lv.pitch;
-            lv.n_bands      = ceil_div(lv.h, SM_BH);
-        }
-        else  // a level scaled down to nothing (small image, many levels, large scale factor): no strips, no work
-        {
-            lv.w = lv.w > 0 ? lv.w : 0;
-            lv.h = lv.h > 0 ? lv.h : 0;
-            lv.n_strips = lv.n_bands = 0;
-            lv.strip_stride = 4;
-        }
-        lv.unit_off     = tile_off;
-        tile_off += lv.n_strips * lv.n_bands;
-    }
-    L.total_cells = cell_off;
-    L.total_slots = slot_off;
-    L.total_units = tile_off;
-    {
-        int mw = 1, mh = 1;
-        for (int l = 0; l < p.n_levels; ++l)
-            if (L.lv[l].ncols > 0)
-            {
-                mw = L.lv[l].wcell > mw ? L.lv[l].wcell : mw;
-                mh = L.lv[l].hcell > mh ? L.lv[l].hcell : mh;
-            }
-        auto up16 = [](int v) { return (v + 15) & ~15; };
-        L.f_tile_pitch_dw = (mw + 6 + 3 + 3) / 4;
-        L.f_s_pitch       = (mw + 2 + 3) & ~3;
-        // compile-time pitches (fast_kernel<3> / <4>) when the widest cell allows, see fast_quads()
-        if (L.f_tile_pitch_dw <= 12 && L.f_s_pitch <= 40 && mh + 6 <= 128) { L.f_tile_pitch_dw = 12; L.f_s_pitch = 40; }
-        else if (L.f_tile_pitch_dw <= 16 && L.f_s_pitch <= 64 && mh + 6 <= 128) { L.f_tile_pitch_dw = 16; L.f_s_pitch = 64; }
-        const int tile_b  = up16((mh + 6) * L.f_tile_pitch_dw * 4);
-        const int s_b     = up16((mh + 2) * L.f_s_pitch) + 16;  // zero-filled in 16-byte stores
-        // survivors of the quick test kept at a time (fast_kernel scores and restarts the list when a cell has more); the
-        // override is for the tests that force the spill path on ordinary images
-        L.f_surv_cap = (mw * mh / 2 + 63) & ~63;  // measured: 0.60 / 0.55 / 0.50 / 0.485 / 0.54 ms at 320 / 384 / 512 / 640 / all pixels
-        if (L.f_surv_cap < 256) L.f_surv_cap = 256;
-        if (const char* e = getenv("SNK_ORB_FAST_SURV_CAP")) L.f_surv_cap = atoi(e) < 128 ? 128 : atoi(e);
-        const int surv_b  = up16(L.f_surv_cap * 2);
-        const int list_b  = up16(((mw + 1) / 2) * ((mh + 1) / 2) * 4);
-        // the list of non-maximum-suppression survivors is written after the last read of the image tile: same bytes
-        SNK_REQUIRE(list_b <= tile_b, "FAST: corner list larger than the tile it aliases");
-        L.f_off_s    = tile_b;
-        L.f_off_surv = L.f_off_s + s_b;
-        L.f_off_list = 0;
-        L.f_off_cnt  = L.f_off_surv + surv_b;
-        L.f_lds_wave = L.f_off_cnt + 16;
-    }
-    return SNK_OK;
+        const auto on  = [](const char* name) { return getenv(name) != nullptr; };
+        const auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
+        OrbSwitches s;
+        s.balanced_strips = on("SNK_ORB_BALANCED_STRIPS");
+        if (on("SNK_ORB_FAST_SURV_CAP")) s.fast_surv_cap = std::max(128, num("SNK_ORB_FAST_SURV_CAP"));
+        if (on("SNK_ORB_PARTS")) s.parts = std::min(std::max(num("SNK_ORB_PARTS"), 1), (int)snk_orb::MAX_PARTS);
+        s.stagger          = num("SNK_ORB_STAGGER") >= 2 ? std::min(num("SNK_ORB_STAGGER"), (int)snk_orb::MAX_STAGGER) : 0;
+        s.blur_in_describe = on("SNK_ORB_BLUR_IN_DESCRIBE");
+        s.blur_tiled       = on("SNK_ORB_BLUR_TILED");
+        s.desc_no_dma      = on("SNK_ORB_DESC_NO_DMA");
+        s.desc_fake_on     = on("SNK_ORB_DESC_FAKE");
+        s.desc_fake        = num("SNK_ORB_DESC_FAKE");
+        s.unfused          = on("SNK_ORB_UNFUSED");
+        s.level_bh         = num("SNK_ORB_LEVEL_BH");
+        s.fast_cpw         = num("SNK_ORB_FAST_CPW");
+        s.fast_stop        = num("SNK_ORB_FAST_STOP");
+        if (const char* e = getenv("SNK_ORB_FAST_LDS_WG")) s.fast_lds_wg = (size_t)atoll(e);
+        s.dist_timing      = on("SNK_ORB_DIST_TIMING");
+        s.dist_key_loop    = on("SNK_ORB_DIST_KEY_LOOP");
+        s.harris_per_cell  = on("SNK_ORB_HARRIS_PER_CELL");
+        s.one_stream       = on("SNK_ORB_ONE_STREAM");
+        return s;
+    }();
+    return once;
 }
 
 static void resize_tables(int src, int dst, int* ofs, int* w1)
@@ -2757,16 +2612,8 @@ int snk_orb_create(const snk_orb_params* params, int device, void* stream, snk_o
     // HIP spreads streams over a handful of hardware queues in creation order, and an extractor that never splits its batches
     // (the default, and every per-frame caller) should not take four of them -- the slots of a pipelined front-end would otherwise
     // land on the same hardware queue and run one behind the other.
-    if (const char* e = getenv("SNK_ORB_PARTS"))
-    {
-        const int v = atoi(e);
-        o->parts    = v < 1 ? 1 : (v > snk_orb::MAX_PARTS ? snk_orb::MAX_PARTS : v);
-    }
-    if (const char* e = getenv("SNK_ORB_STAGGER"))
-    {
-        const int v = atoi(e);
-        o->stagger  = v >= 2 ? (v > snk_orb::MAX_STAGGER ? snk_orb::MAX_STAGGER : v) : 0;
-    }
+    o->parts   = orb_switches().parts;
+    o->stagger = orb_switches().stagger;
     if ((o->parts > 1 || o->stagger >= 2) && !ensure_extra_streams(o)) o->parts = 1, o->stagger = 0;
     *out = o;
     return SNK_OK;
@@ -2824,9 +2671,11 @@ int snk_orb_configure(snk_orb* o, int width, int height, int max_batch)
     SNK_HIP_CHECK(hipSetDevice(o->device));
     if (o->configured && o->width == width && o->height == height && o->max_batch >= max_batch) return SNK_OK;
     SNK_HIP_CHECK(hipStreamSynchronize(o->stream));
-    int rc = compute_layout(o, width, height);
-    if (rc != SNK_OK) return rc;
     Layout& L = o->lay;
+    const snk_orb_params& p = o->params;
+    const char* bad = layout(L, width, height, p.nfeatures, p.scale_factor, p.n_levels, p.level_cap, orb_switches().balanced_strips, orb_switches().fast_surv_cap);
+    SNK_REQUIRE(bad == nullptr, bad);
+    int rc;
     // resize tables
     size_t tab_ints = 0;
     for (int l = 1; l < L.n_levels; ++l)
@@ -2929,20 +2778,14 @@ int snk_orb_configure(snk_orb* o, int width, int height, int max_batch)
     if ((rc = o->sel_score.reserve(slots)) != SNK_OK) return rc;
     if ((rc = o->sel_cnt.reserve((size_t)max_batch * MAX_LEVELS * sizeof(int))) != SNK_OK) return rc;
     if ((rc = o->cand_total.reserve((size_t)max_batch * MAX_LEVELS * sizeof(int))) != SNK_OK) return rc;
-    // distribute kernel dynamic LDS
-    auto dist_lds_bytes = [](size_t cap) { return cap * 8 + cap / 2 * 8 + cap * 2 * 2 + cap + (cap + 16) + cap; };
-    o->dist_small_cap = L.level_cap < 2048 ? L.level_cap : 2048;
-    o->dist_lds       = dist_lds_bytes((size_t)L.level_cap);
-    o->dist_lds_small = dist_lds_bytes((size_t)o->dist_small_cap);
     if ((rc = o->dist_queue.reserve(snk_orb::MAX_PARTS * ((size_t)max_batch * MAX_LEVELS + 1) * sizeof(int))) != SNK_OK) return rc;  // one per chain
+    SNK_REQUIRE(fast_fits(L), "FAST cells too large for the LDS (image too small for its cell grid?)");
     // process-wide, once per kernel, to the largest carve any handle can ask for (never per-handle sizes: two extractors
     // with different image sizes / level_cap would overwrite each other's limit)
-    SNK_REQUIRE(4 * L.f_lds_wave <= LDS_MAX_BYTES, "FAST cells too large for the LDS (image too small for its cell grid?)");
-    // the largest of: the 2048-candidate carve + the Harris ranks ("orb.response" = 1), the full-budget carve (small launches take it directly)
-    if ((rc = set_max_lds_once(reinterpret_cast<const void*>(distribute_kernel), (int)std::max(dist_lds_bytes(2048) + 4 * 2048 + 16, dist_lds_bytes(8192)))) != SNK_OK) return rc;
-    if ((rc = set_max_lds_once(reinterpret_cast<const void*>(distribute_large_kernel), (int)dist_lds_bytes(8192))) != SNK_OK) return rc;
-    if ((rc = set_max_lds_once(fast_kernel_for(L, false), LDS_MAX_BYTES)) != SNK_OK) return rc;
-    if ((rc = set_max_lds_once(fast_kernel_for(L, true), LDS_MAX_BYTES)) != SNK_OK) return rc;
+    if ((rc = set_max_lds_once(reinterpret_cast<const void*>(distribute_kernel), (int)DIST_LDS_MAX)) != SNK_OK) return rc;
+    if ((rc = set_max_lds_once(reinterpret_cast<const void*>(distribute_large_kernel), (int)DIST_LARGE_LDS_MAX)) != SNK_OK) return rc;
+    for (const bool loop : {false, true})
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(fast_kernel_of(orb_fast_form(fast_quads(L), loop))), LDS_MAX_BYTES)) != SNK_OK) return rc;
     // host-API staging (snk_orb_detect): sized here so that the per-image call allocates nothing
     {
         const int dpitch = (width + 63) & ~63;
@@ -2971,20 +2814,61 @@ int snk_orb_max_keypoints(const snk_orb* o, int* out)
     return SNK_OK;
 }
 
-// One launch chain over images [b0, b0 + batch) of a call on stream `st`: every per-image buffer is indexed
-// relative to the chain's first image, so the bases are simply advanced by b0 images.
-// stages: 1 = the front half (pyramid / blur passes + FAST cells), 2 = the back half (distribution + descriptors), 3 = both
-// Layout of the blurred planes for this process (level_kernel writes it, describe_kernel reads it -- both ask here): 0 = row-major (the
-// default), 2 = tiled 32 x 4 (SNK_ORB_BLUR_TILED=1, an experiment of round 6: built, bit-exact, MEASURED SLOWER -- describe_kernel
-// 1.39 -> 1.32 ms, but level_kernel's stores, 16-byte pieces of 47 lines per row instead of two whole lines, cost 1.50 -> 1.74 ms:
-// 191.6 -> 187.9 k frames/s, profiles/r06/r06p_ab_blur_tiled_negative.txt), 1 = no blurred plane (SNK_ORB_BLUR_IN_DESCRIBE=1).
-static int orb_blur_mode()
+// The event set of a part of the current call (profiling): a new one for its front half, the same for its back half
+static int part_events(snk_orb* o, int part, int stages, std::array<hipEvent_t, 7>** ev)
 {
-    static const int mode = getenv("SNK_ORB_BLUR_IN_DESCRIBE") ? 1
-                            : (getenv("SNK_ORB_BLUR_TILED") && !getenv("SNK_ORB_DESC_NO_DMA") && !getenv("SNK_ORB_DESC_FAKE")) ? 2 : 0;
-    return mode;
+    if (stages & 1)
+    {
+        if (o->ev_used == o->ev_sets.size())
+        {
+            std::array<hipEvent_t, 7> e{};
+            for (auto& x : e) SNK_HIP_CHECK(hipEventCreate(&x));
+            o->ev_sets.push_back(e);
+        }
+        o->part_ev[part] = o->ev_used++;
+    }
+    *ev = &o->ev_sets[o->part_ev[part]];
+    return SNK_OK;
 }
 
+// SNK_ORB_DIST_TIMING=1 (diagnostic): distribute_kernel's cycle sums per phase and level, printed after a synchronisation
+static int print_dist_timing(unsigned long long* d_dbg, int n_levels, int batch, hipStream_t st)
+{
+    unsigned long long h[MAX_LEVELS * 16];
+    SNK_HIP_CHECK(hipStreamSynchronize(st));
+    SNK_HIP_CHECK(hipMemcpy(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost));
+    SNK_HIP_CHECK(hipFree(d_dbg));
+    for (int l = 0; l < n_levels; ++l)
+    {
+        fprintf(stderr, "[dist timing] level %d (avg candidates %.0f, %.2f careful rounds), cycles per workgroup:", l,
+                (double)h[l * 16 + 15] / batch, (double)h[l * 16 + 14] / batch);
+        for (int ph = 0; ph < 13; ++ph) fprintf(stderr, " %.0f", (double)h[l * 16 + ph] / batch);
+        fprintf(stderr, "\n");
+    }
+    return SNK_OK;
+}
+
+// SNK_DEBUG: the plan of a launch chain on stderr, one line per run_part (tests/forms.py reads it: orb_plan_lines)
+static void print_plan(const snk_orb* o, const OrbPlan& P, int batch, int aligned0, bool harris, int stages)
+{
+    std::string levels;
+    for (int l = 0; l < P.n_levels; ++l)
+    {
+        char tok[8];
+        orb_level_token(P.lv[l], tok);
+        levels += (l ? "," : "") + std::string(tok);
+    }
+    const snk_orb_params& p = o->params;
+    fprintf(stderr, "snake_hip: orb plan w=%d h=%d nfeat=%d levels=%d scale=%.9g cap=%d batch=%d aligned=%d harris=%d stages=%d level=%s fast=%d/%d harris_form=%s dist=%s desc=%s\n",
+            o->width, o->height, p.nfeatures, p.n_levels, (double)p.scale_factor, p.level_cap, batch, aligned0, (int)harris, stages, levels.c_str(),
+            P.fast_run ? P.fast_cpw : 0, P.fast_quads, orb_name(P.harris), orb_name(P.dist), orb_name(P.desc));
+}
+
+// One launch chain over images [b0, b0 + batch) of a call on stream `st`: every per-image buffer is indexed
+// relative to the chain's first image, so the bases are simply advanced by b0 images.
+// stages: 1 = the front half (pyramid / blur passes + FAST cells), 2 = the back half (distribution + descriptors), 3 = both.
+// Offsets the pointers, records the profiling events and walks the plan: which kernel form, grid and carve a stage takes is orb_plan's
+// answer (dispatch.hpp).
 static int run_part(snk_orb* o, hipStream_t st, int part, int b0, const u8* images_dev, int pitch, long long image_stride,
                     int batch, snk_keypoint* kps_dev, uint64_t* desc_dev, int32_t* n_dev, int out_cap, int stages = 3)
 {
@@ -3007,9 +2891,12 @@ static int run_part(snk_orb* o, hipStream_t st, int part, int b0, const u8* imag
     int* d_queue    = o->dist_queue.as<int>() + (size_t)part * ((size_t)o->max_batch * MAX_LEVELS + 1);
     // "orb.response" = 1 (snk_set_definition): Harris response of the FAST candidates ranks the points of a quadtree node and is the
     // keypoints' response.  Its scratch is reserved by the first call that runs under it (a growing reserve synchronises the device).
-    const bool harris = definition(DEF_ORB_RESPONSE) == 1;
+    const bool harris  = definition(DEF_ORB_RESPONSE) == 1;
+    const int aligned0 = (reinterpret_cast<uintptr_t>(images_dev) % 4 == 0 && pitch % 4 == 0 && image_stride % 4 == 0) ? 1 : 0;
+    const OrbSwitches& sw = orb_switches();
+    const OrbPlan P       = orb_plan(L, batch, aligned0 != 0, harris, stages, o->params.scale_factor, sw);  // every form decision of the chain
+    if (getenv("SNK_DEBUG") != nullptr) print_plan(o, P, batch, aligned0, harris, stages);  // read at every call: a test switches it on inside its process
     u32 *d_candh = nullptr, *d_selresp = nullptr, *d_disth = nullptr;
-    const int large_workers = L.n_levels * batch < 256 ? L.n_levels * batch : 256;
     if (harris)
     {
         const size_t cells = (size_t)(L.total_cells > 0 ? L.total_cells : 1) * o->max_batch;
@@ -3017,203 +2904,119 @@ static int run_part(snk_orb* o, hipStream_t st, int part, int b0, const u8* imag
         int rc;
         if ((rc = o->cand_h.reserve(cells * CELL_SLOTS * sizeof(u32))) != SNK_OK) return rc;
         if ((rc = o->sel_resp.reserve(slots * sizeof(u32))) != SNK_OK) return rc;
-        if (o->dist_small_cap < L.level_cap &&
-            (rc = o->dist_h.reserve((size_t)snk_orb::MAX_PARTS * 256 * L.level_cap * sizeof(u32))) != SNK_OK)
+        if (P.dist == OrbDistForm::small_drain &&
+            (rc = o->dist_h.reserve((size_t)snk_orb::MAX_PARTS * ORB_DIST_LARGE_WGS * L.level_cap * sizeof(u32))) != SNK_OK)
             return rc;
         d_candh   = o->cand_h.as<u32>() + (size_t)b0 * L.total_cells * CELL_SLOTS;
         d_selresp = o->sel_resp.as<u32>() + (size_t)b0 * L.total_slots;
-        d_disth   = o->dist_h.as<u32>() ? o->dist_h.as<u32>() + (size_t)part * 256 * L.level_cap : nullptr;
+        d_disth   = o->dist_h.as<u32>() ? o->dist_h.as<u32>() + (size_t)part * ORB_DIST_LARGE_WGS * L.level_cap : nullptr;
     }
     std::array<hipEvent_t, 7>* ev = nullptr;
     if (o->profiling)
-    {
-        if (stages & 1)
-        {
-            if (o->ev_used == o->ev_sets.size())
-            {
-                std::array<hipEvent_t, 7> e{};
-                for (auto& x : e) SNK_HIP_CHECK(hipEventCreate(&x));
-                o->ev_sets.push_back(e);
-            }
-            o->part_ev[part] = o->ev_used++;
-        }
-        ev = &o->ev_sets[o->part_ev[part]];
-        if (stages & 1) SNK_HIP_CHECK(hipEventRecord((*ev)[0], st));
-    }
+        if (int rc = part_events(o, part, stages, &ev)) return rc;
     if (stages & 1)
     {
-    // one streaming pass per level: blur of level l + down-scale to level l+1 (the chain makes the
-    // passes sequential; every level is read once)
-    const int aligned0 = (reinterpret_cast<uintptr_t>(images_dev) % 4 == 0 && pitch % 4 == 0 && image_stride % 4 == 0) ? 1 : 0;
-    static const bool unfused_env = getenv("SNK_ORB_UNFUSED") != nullptr;  // A/B: stand-alone resize_kernel + blur-only passes
-    const bool fused_ok = o->params.scale_factor <= 2.0f && !unfused_env;  // the in-stream down-scale reaches 3 * scale + 1 columns right
-    // levels below 8 x 8 (deep levels of small images) cannot hold a feature and are outside the domain of
-    // the streaming pass's reflect-101 halo: they are only down-scaled (stand-alone kernel), never blurred
-    auto tiny = [&](int l) { return L.lv[l].w < 8 || L.lv[l].h < 8; };
-    for (int l = 0; l < L.n_levels; ++l)
-    {
-        const LevelInfo& lv = L.lv[l];
-        const bool fused    = fused_ok && !tiny(l);
-        if (lv.w <= 0 || lv.h <= 0) continue;  // a level scaled down to nothing (small image, many levels): no pixels, no cells
-        if (l > 0 && (!fused_ok || tiny(l - 1)))
+        if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[0], st));
+        // one streaming pass per level: blur of level l + down-scale to level l+1 (the chain makes the passes sequential; every level
+        // is read once)
+        for (int l = 0; l < L.n_levels; ++l)
         {
-            const LevelInfo& sv = L.lv[l - 1];
-            dim3 grid(ceil_div(ceil_div(lv.w, 4), 256), lv.h, batch);
-            hipLaunchKernelGGL(resize_kernel, grid, dim3(256), 0, st, l == 1 ? images_dev : sv.base, l == 1 ? pitch : sv.pitch,
-                               l == 1 ? image_stride : sv.img_stride, sv.w, sv.h, lv.base, lv.pitch, lv.img_stride, lv.w, lv.h,
-                               lv.xofs, lv.xw1, lv.yofs, lv.yw1);
+            const LevelInfo& lv    = L.lv[l];
+            const OrbLevelPlan& pl = P.lv[l];
+            if (pl.skipped) continue;
+            if (pl.resize_first)
+            {
+                const LevelInfo& sv = L.lv[l - 1];
+                dim3 grid(ceil_div(ceil_div(lv.w, 4), 256), lv.h, batch);
+                hipLaunchKernelGGL(resize_kernel, grid, dim3(256), 0, st, l == 1 ? images_dev : sv.base, l == 1 ? pitch : sv.pitch,
+                                   l == 1 ? image_stride : sv.img_stride, sv.w, sv.h, lv.base, lv.pitch, lv.img_stride, lv.w, lv.h,
+                                   lv.xofs, lv.xw1, lv.yofs, lv.yw1);
+                SNK_LAUNCH_CHECK();
+            }
+            if (pl.tiny) continue;
+            auto lk = level_kernel<true, 64>;
+            switch (pl.band)
+            {
+            case OrbBandForm::bh64: lk = pl.aligned ? level_kernel<true, 64> : level_kernel<false, 64>; break;
+            case OrbBandForm::bh22: lk = pl.aligned ? level_kernel<true, 22> : level_kernel<false, 22>; break;
+            case OrbBandForm::bh8: lk = pl.aligned ? level_kernel<true, 8> : level_kernel<false, 8>; break;
+            }
+            hipLaunchKernelGGL(lk, xcd_grid(pl.gx, batch), dim3(256), 0, st, L, l, images_dev, pitch, image_stride, pl.make_next ? 1 : 0, pl.gx, batch,
+                               pl.n_bands, P.blur_mode);
             SNK_LAUNCH_CHECK();
         }
-        if (tiny(l)) continue;
+        if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[1], st));
+        SNK_LAUNCH_CHECK();
+        if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[2], st));
+        if (P.fast_run)
         {
-            // rows per band: 64 when the launch fills the chip's 8192 wavefront slots anyway, else 22, else 8 (per-frame calls)
-            static const int bh_env = getenv("SNK_ORB_LEVEL_BH") ? atoi(getenv("SNK_ORB_LEVEL_BH")) : 0;  // A/B, tests: 64 / 22 / 8
-            const long long strips = (long long)lv.n_strips * batch;
-            int bh = strips * ceil_div(lv.h, 64) >= 2048 ? 64 : (strips * ceil_div(lv.h, 22) >= 2048 ? 22 : 8);
-            if (bh_env == 64 || bh_env == 22 || bh_env == 8) bh = bh_env;
-            const int n_bands = ceil_div(lv.h, bh);
-            const int gx = ceil_div(lv.n_strips * n_bands, 4);
-            const bool al = !(l == 0 && !aligned0);
-            auto lk = bh == 64 ? (al ? level_kernel<true, 64> : level_kernel<false, 64>)
-                               : (bh == 22 ? (al ? level_kernel<true, 22> : level_kernel<false, 22>) : (al ? level_kernel<true, 8> : level_kernel<false, 8>));
-            hipLaunchKernelGGL(lk, xcd_grid(gx, batch), dim3(256), 0, st, L, l, images_dev, pitch, image_stride,
-                               fused && l + 1 < L.n_levels && L.lv[l + 1].w > 0 && L.lv[l + 1].h > 0 ? 1 : 0, gx, batch, n_bands,
-                               orb_blur_mode());
+            hipLaunchKernelGGL(fast_kernel_of(P.fast), xcd_grid(P.fast_gx, batch), dim3(256), P.fast_lds, st, L, images_dev, pitch, image_stride, aligned0,
+                               o->params.ini_th_fast, o->params.min_th_fast, d_cand, d_cellcnt, P.fast_gx, batch, sw.fast_stop, P.fast_cpw,
+                               P.queue_memset ? (int*)nullptr : d_queue);
+            SNK_LAUNCH_CHECK();
         }
-        SNK_LAUNCH_CHECK();
-    }
-    if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[1], st));
-    SNK_LAUNCH_CHECK();
-    if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[2], st));
-    if (L.total_cells > 0)
-    {
-        // cells per wavefront: 1 for small launches (keep the chip filled), more once there are plenty of workgroups
-        static const int cpw_env = getenv("SNK_ORB_FAST_CPW") ? atoi(getenv("SNK_ORB_FAST_CPW")) : 0;
-        const long long cell_waves = (long long)L.total_cells * batch;
-        int cpw = FAST_CPW_DEFAULT;
-        while (cpw > 1 && cell_waves / cpw < 256 * 32 * 4) cpw >>= 1;  // at least four rounds of the chip's 8192 wavefront slots
-        if (cpw_env >= 1 && cpw_env <= 64) cpw = cpw_env;               // forced (tests, measurements): whatever the launch size
-        const int gx = ceil_div(L.total_cells, 4 * cpw);
-        const int fq = fast_quads(L);
-        static const int fast_stop = getenv("SNK_ORB_FAST_STOP") ? atoi(getenv("SNK_ORB_FAST_STOP")) : 0;  // timing experiments
-        auto fk      = cpw > 1 ? (fq == 3 ? fast_kernel<3, true> : (fq == 4 ? fast_kernel<4, true> : fast_kernel<0, true>))
-                               : (fq == 3 ? fast_kernel<3, false> : (fq == 4 ? fast_kernel<4, false> : fast_kernel<0, false>));
-        // occupancy shaping (experiment, round 4): a workgroup that asks for at least SNK_ORB_FAST_LDS_WG bytes of LDS caps how many
-        // FAST workgroups a CU holds, so that back-half workgroups of another stream (staggered schedule) find room beside them
-        static const size_t lds_wg_env = getenv("SNK_ORB_FAST_LDS_WG") ? (size_t)atoll(getenv("SNK_ORB_FAST_LDS_WG")) : 0;
-        const size_t fast_lds = std::max((size_t)4 * L.f_lds_wave, std::min(lds_wg_env, (size_t)LDS_MAX_BYTES));
-        hipLaunchKernelGGL(fk, xcd_grid(gx, batch), dim3(256), fast_lds, st, L, images_dev, pitch,
-                           image_stride, aligned0, o->params.ini_th_fast, o->params.min_th_fast, d_cand, d_cellcnt, gx, batch, fast_stop,
-                           cpw, stages == 3 ? d_queue : (int*)nullptr);
-        SNK_LAUNCH_CHECK();
-    }
-    if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[3], st));
+        if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[3], st));
     }
     if (!(stages & 2)) return SNK_OK;
     if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[6], st));
-    {
-    const int aligned0 = (reinterpret_cast<uintptr_t>(images_dev) % 4 == 0 && pitch % 4 == 0 && image_stride % 4 == 0) ? 1 : 0;
-    // the queue's counter: reset by fast_kernel when this call enqueues the whole chain on one stream (the usual case: one launch less
-    // per frame); the split schedules (front and back halves on different streams, chain slots shared by parts) keep the fill
-    if (stages != 3 || L.total_cells <= 0) SNK_HIP_CHECK(hipMemsetAsync(d_queue, 0, sizeof(int), st));
-    // SNK_ORB_DIST_TIMING=1 (diagnostic): cycle sums per phase and level, printed after a synchronisation
-    static const bool dist_timing = getenv("SNK_ORB_DIST_TIMING") != nullptr;
-    static const bool key_loop    = getenv("SNK_ORB_DIST_KEY_LOOP") != nullptr;  // A/B: subdivision keys by the loop form, not from the tables
-    const u32* d_keytab           = key_loop ? nullptr : o->key_tab.as<u32>();
+    if (P.queue_memset) SNK_HIP_CHECK(hipMemsetAsync(d_queue, 0, sizeof(int), st));
+    const u32* d_keytab       = sw.dist_key_loop ? nullptr : o->key_tab.as<u32>();
     unsigned long long* d_dbg = nullptr;
-    if (dist_timing)
+    if (sw.dist_timing)
     {
         SNK_HIP_CHECK(hipMalloc(&d_dbg, MAX_LEVELS * 16 * sizeof(unsigned long long)));
         SNK_HIP_CHECK(hipMemsetAsync(d_dbg, 0, MAX_LEVELS * 16 * sizeof(unsigned long long), st));
     }
-    if (harris && L.total_cells > 0)
+    switch (P.harris)
     {
-        static const bool per_cell = getenv("SNK_ORB_HARRIS_PER_CELL") != nullptr;  // A/B: one wavefront per cell, one lane per slot (round 5)
-        if (per_cell)
-        {
-            const int gxh = ceil_div(L.total_cells, 4);
-            hipLaunchKernelGGL(harris_kernel, xcd_grid(gxh, batch), dim3(256), 0, st, L, images_dev, pitch, image_stride, aligned0, d_cand, d_cellcnt,
-                               d_candh, gxh, batch);
-        }
-        else
-        {
-            const int gxh = ceil_div(ceil_div(L.total_cells, HARRIS_NC), 4);
-            hipLaunchKernelGGL(harris_dense_kernel, xcd_grid(gxh, batch), dim3(256), 0, st, L, images_dev, pitch, image_stride, aligned0, d_cand,
-                               d_cellcnt, d_candh, gxh, batch);
-        }
-        SNK_LAUNCH_CHECK();
+    case OrbHarrisForm::none: break;
+    case OrbHarrisForm::per_cell:
+        hipLaunchKernelGGL(harris_kernel, xcd_grid(P.harris_gx, batch), dim3(256), 0, st, L, images_dev, pitch, image_stride, aligned0, d_cand, d_cellcnt,
+                           d_candh, P.harris_gx, batch);
+        break;
+    case OrbHarrisForm::dense:
+        hipLaunchKernelGGL(harris_dense_kernel, xcd_grid(P.harris_gx, batch), dim3(256), 0, st, L, images_dev, pitch, image_stride, aligned0, d_cand,
+                           d_cellcnt, d_candh, P.harris_gx, batch);
+        break;
     }
-    // A launch of a few (image, level) workgroups (the per-frame calls) gives every workgroup the full-budget carve at once: nothing can
-    // be queued, the drain launch is skipped (one launch less in the per-frame chain; the carve only limits workgroups per CU, and these
-    // launches do not fill the chip).  Not under "orb.response" = 1: the Harris ranks do not fit beside the full carve.
-    const bool one_dist_launch = !harris && o->dist_small_cap < L.level_cap && (long long)L.n_levels * batch <= 128;
-    hipLaunchKernelGGL(distribute_kernel, dim3(L.n_levels, batch), dim3(DIST_THREADS),
-                       one_dist_launch ? o->dist_lds : o->dist_lds_small + (harris ? 4 * (size_t)o->dist_small_cap + 16 : 0), st, L,
-                       one_dist_launch ? L.level_cap : o->dist_small_cap, d_cand, d_cellcnt, d_sel, d_selscore,
-                       d_selcnt, d_candtot, d_queue, d_dbg, d_candh, d_selresp, d_keytab);
     SNK_LAUNCH_CHECK();
-    if (dist_timing)
+    hipLaunchKernelGGL(distribute_kernel, dim3(L.n_levels, batch), dim3(DIST_THREADS), P.dist_lds, st, L, P.dist_lds_cap, d_cand, d_cellcnt, d_sel,
+                       d_selscore, d_selcnt, d_candtot, d_queue, d_dbg, d_candh, d_selresp, d_keytab);
+    SNK_LAUNCH_CHECK();
+    if (d_dbg)
+        if (int rc = print_dist_timing(d_dbg, L.n_levels, batch, st)) return rc;
+    if (P.dist == OrbDistForm::small_drain)
     {
-        unsigned long long h[MAX_LEVELS * 16];
-        SNK_HIP_CHECK(hipStreamSynchronize(st));
-        SNK_HIP_CHECK(hipMemcpy(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost));
-        SNK_HIP_CHECK(hipFree(d_dbg));
-        for (int l = 0; l < L.n_levels; ++l)
-        {
-            fprintf(stderr, "[dist timing] level %d (avg candidates %.0f, %.2f careful rounds), cycles per workgroup:", l,
-                    (double)h[l * 16 + 15] / batch, (double)h[l * 16 + 14] / batch);
-            for (int ph = 0; ph < 13; ++ph) fprintf(stderr, " %.0f", (double)h[l * 16 + ph] / batch);
-            fprintf(stderr, "\n");
-        }
-    }
-    if (o->dist_small_cap < L.level_cap && !one_dist_launch)
-    {
-        hipLaunchKernelGGL(distribute_large_kernel, dim3(large_workers), dim3(DIST_THREADS), o->dist_lds, st, L,
-                           d_cand, d_cellcnt, d_sel, d_selscore,
-                           d_selcnt, d_candtot, d_queue, d_candh, d_selresp, d_disth, d_keytab);
+        hipLaunchKernelGGL(distribute_large_kernel, dim3(P.large_workers), dim3(DIST_THREADS), P.dist_large_lds, st, L, d_cand, d_cellcnt, d_sel,
+                           d_selscore, d_selcnt, d_candtot, d_queue, d_candh, d_selresp, d_disth, d_keytab);
         SNK_LAUNCH_CHECK();
     }
     if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[4], st));
-    int max_slot = 1;
-    for (int l = 0; l < L.n_levels; ++l) max_slot = L.lv[l].slot_cap > max_slot ? L.lv[l].slot_cap : max_slot;
+    auto dk = describe_kernel<false, false, false>;
+    switch (P.desc)
     {
-        const int nb = batch >= 16 ? 8 * ceil_div(batch, 8) : batch;
-        static const bool blur_in = getenv("SNK_ORB_BLUR_IN_DESCRIBE") != nullptr;  // experiment (round 5), see describe_kernel<true>
-        // round 6: the blurred patch by LDS-DMA (describe_kernel<false, true>; same-box A/B 1.457 -> 1.398 ms per 2048 images,
-        // profiles/r06/r06c_ab_describe_lds_dma.txt).  SNK_ORB_DESC_NO_DMA=1: the register path
-        static const bool dma = getenv("SNK_ORB_DESC_NO_DMA") == nullptr;
-        const int dfake       = getenv("SNK_ORB_DESC_FAKE") ? atoi(getenv("SNK_ORB_DESC_FAKE")) : 0;
-        const int gx          = ceil_div(max_slot, 4 * DESC_KPW);
-        auto dk = describe_kernel<false, false, false>;
-        if (blur_in) dk = describe_kernel<true, false, false>;
-        else if (dma && orb_blur_mode() == 2) dk = describe_kernel<false, true, true>;
-        else if (dma) dk = describe_kernel<false, true, false>;
-        hipLaunchKernelGGL(dk, dim3(gx * L.n_levels * nb), dim3(256), 0, st, L, images_dev, pitch, image_stride, aligned0, d_sel, d_selscore, d_selcnt,
-                           kps_dev, (u64*)desc_dev, n_dev, out_cap, gx, batch, dfake, d_selresp);
+    case OrbDescForm::registers: break;
+    case OrbDescForm::blur_in: dk = describe_kernel<true, false, false>; break;
+    case OrbDescForm::dma_tiled: dk = describe_kernel<false, true, true>; break;
+    case OrbDescForm::dma: dk = describe_kernel<false, true, false>; break;
     }
+    hipLaunchKernelGGL(dk, dim3(P.desc_gx * L.n_levels * P.desc_nb), dim3(256), 0, st, L, images_dev, pitch, image_stride, aligned0, d_sel, d_selscore,
+                       d_selcnt, kps_dev, (u64*)desc_dev, n_dev, out_cap, P.desc_gx, batch, P.dfake, d_selresp);
     SNK_LAUNCH_CHECK();
     if (ev) SNK_HIP_CHECK(hipEventRecord((*ev)[5], st));
-    }
     return SNK_OK;
 }
 
-
-// A batch of at least split_min_batch images runs as two half-batch chains on two streams (fork / join
-// with events on the caller-visible stream); smaller batches as one chain.
+// The launch chains of a call, by the handle's schedule (orb_schedule in dispatch.hpp): fork / join with events on the caller-visible
+// stream.
 static int run_pipeline(snk_orb* o, const u8* images_dev, int pitch, long long image_stride, int batch,
                         snk_keypoint* kps_dev, uint64_t* desc_dev, int32_t* n_dev, int out_cap)
 {
-    static const bool one_stream = getenv("SNK_ORB_ONE_STREAM") != nullptr;
-    // Launch chains: one by default.  Two half-batch chains on two streams (snk_orb_set_chains) overlap the tails of one chain's launches
-    // with the other's kernels: 186.0 / 192.1 / 192.9 / 188.4 k frames/s with 1 / 2 / 3 / 4 chains in one run, 187.6 k with 2 in the next
-    // (profiles/r05/r05o_chains.txt, r05p_bench_two_chains_by_default.txt) -- the chains start together and mostly run the same stage at
-    // the same time, so the gain is the tails only and a kernel's duration is then measured under a concurrent copy of itself.  Tried as
-    // the default for big batches in round 5 and taken back.  Per-frame launches never split (and never create the extra streams).
-    const int want_parts = o->parts;
-    const bool want_split = !one_stream && batch >= o->split_min_batch && (want_parts > 1 || (o->stagger >= 2 && batch >= 2 * o->stagger));
-    if (!want_split || !ensure_extra_streams(o))
+    int parts;
+    const OrbSchedule sched = orb_schedule(batch, o->parts, o->stagger, o->split_min_batch, orb_switches().one_stream, parts);
+    if (sched == OrbSchedule::one_chain || !ensure_extra_streams(o))
         return run_part(o, o->stream, 0, 0, images_dev, pitch, image_stride, batch, kps_dev, desc_dev, n_dev, out_cap);
-    if (o->stagger >= 2 && batch >= 2 * o->stagger)
+    if (sched == OrbSchedule::staggered)
     {
         // Front halves (VALU-bound: level passes, FAST) back to back on the handle's stream; the back half of part p (latency-bound:
         // distribution, descriptors) on the second stream beside the front half of part p + 1.  Parts are disjoint image ranges
@@ -3222,7 +3025,7 @@ static int run_pipeline(snk_orb* o, const u8* images_dev, int pitch, long long i
         // profiling event set.  Both are touched by the BACK half only (stages & 2 in run_part), and every back half is enqueued on
         // the single stream `sb`, so two users of a slot never overlap.  Moving back halves onto more than one stream requires
         // sizing dist_queue / part_ev by MAX_STAGGER and passing `p` as the part index.
-        const int P = o->stagger;
+        const int P = parts;
         hipStream_t sf = o->stream, sb = o->extra[0];
         SNK_HIP_CHECK(hipEventRecord(o->ev_fork, sf));
         SNK_HIP_CHECK(hipStreamWaitEvent(sb, o->ev_fork, 0));
@@ -3243,8 +3046,6 @@ static int run_pipeline(snk_orb* o, const u8* images_dev, int pitch, long long i
         SNK_HIP_CHECK(hipStreamWaitEvent(o->stream, o->ev_join_n[0], 0));
         return SNK_OK;
     }
-    const int parts = want_parts < batch ? want_parts : batch;
-    if (parts <= 1) return run_part(o, o->stream, 0, 0, images_dev, pitch, image_stride, batch, kps_dev, desc_dev, n_dev, out_cap);
     SNK_HIP_CHECK(hipEventRecord(o->ev_fork, o->stream));
     int b0 = 0;
     for (int p = 0; p < parts; ++p)

@@ -15,6 +15,7 @@
 // integer atomicMin of the local-map index per claimed feature (order independent, deterministic).
 // The keyframe matcher is greedy-sequential by definition (a feature taken by point i is gone for
 // point i+1), so one wavefront walks the points in order with the taken mask in LDS.
+#include "dispatch.hpp"
 #include "matcher_handle.hpp"
 
 namespace snk
@@ -1304,52 +1305,20 @@ __global__ __launch_bounds__(256) void relink_kernel(FrameDev F, CamDev C, const
     }
 }
 
-// Points per wavefront of the projection matchers: a wavefront does the per-point geometry for `ppw` points at once and, with
-// PJ_GROUP = 1, every lane then scans its own point's window.  Many points per wavefront fill the lanes (throughput of the
-// batched forms), few spread a single frame's points over the chip: for the host calls (one frame, the reference's call
-// pattern) ONE point per wavefront is the lowest latency -- measured on MI355X with the frame bound (tools/latency_track.py,
-// profiles/r03/r03b_latency_track.log): SearchByProjectionFrameFrame2 with 1500 points 0.089 / 0.097 / 0.104 / 0.113 ms and
-// SearchByProjection2 with 10 000 points 0.785 / 0.797 / 0.800 / 0.907 ms at 1 / 4 / 16 / 64 points per wavefront -- a lane's
-// serial window scan is the critical path either way, and more wavefronts only add parallel scans.
-constexpr int FRAME_LDS_MAX = 144 * 1024;  // LDS carve of the frame-resident matchers (one workgroup per CU above 80 KB)
-size_t frame_lds_host(int cap, int ncell1)
+// The four switches of the projection matchers (dispatch.hpp names each and holds the rules they enter), read once per process
+const TrackSwitches& track_switches()
 {
-    return (((size_t)cap * 24 + 15) & ~(size_t)15) + (size_t)cap * 32 + (((size_t)cap * 4 + 15) & ~(size_t)15) + (((size_t)cap + 15) & ~(size_t)15) +
-           (size_t)ncell1 * 4 + 64;
-}
-bool no_frame_lds()
-{
-    static const bool v = getenv("SNK_TRACK_NO_FRAME_LDS") != nullptr;  // A/B: the batched matchers with global-memory gathers
-    return v;
-}
-
-// Workgroups per frame of the frame-resident matchers: every workgroup stages the frame in LDS once and then walks its share of the
-// local map's 1024-point chunks, so as few as keep the chip's 512 workgroup slots (two 65 KB frames per CU) filled about twice.
-// Measured on the tracking leg of bench.py (1024 frames x 10 000 points, profiles/r04/r04g_track_wgs.log): 10 workgroups per frame
-// (one per chunk, the round-3 form) 537 k frames/s, 5: 582 k, 3: 595 k, 2: 610 k, 1: 611 k.  SNK_TRACK_FRAME_WGS forces a value.
-int frame_wgs(int chunks, int batch)
-{
-    static const int forced = getenv("SNK_TRACK_FRAME_WGS") ? atoi(getenv("SNK_TRACK_FRAME_WGS")) : 0;  // A/B, tests
-    int wgs = batch > 0 ? (1024 + batch - 1) / batch : chunks;
-    if (forced >= 1) wgs = forced;
-    return wgs < 1 ? 1 : (wgs > chunks ? chunks : wgs);
-}
-
-// Byte offset of the claims inside the LDS carve of a frame-resident matcher that resolves its matches itself, -1 = separate resolution
-// (several workgroups per frame, or the claims do not fit behind the frame).  SNK_TRACK_NO_FUSED_RESOLVE=1: always separate (A/B, tests).
-int fused_claim_offset(int wgs, size_t flds, int cap)
-{
-    static const bool off = getenv("SNK_TRACK_NO_FUSED_RESOLVE") != nullptr;
-    const size_t at = (flds + 15) & ~(size_t)15;
-    return (off || wgs != 1 || at + (size_t)cap * 4 > (size_t)FRAME_LDS_MAX) ? -1 : (int)at;
-}
-
-int points_per_wave(long long total_points)
-{
-    static const int forced = getenv("SNK_TRACK_PPW") ? atoi(getenv("SNK_TRACK_PPW")) : 0;  // tests: force a value
-    if (forced >= 1 && forced <= 64) return forced;
-    const long long want = total_points / 8192;
-    return (int)(want < 1 ? 1 : (want > 64 ? 64 : want));
+    static const TrackSwitches once = []
+    {
+        const auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
+        TrackSwitches s;
+        s.no_frame_lds     = getenv("SNK_TRACK_NO_FRAME_LDS") != nullptr;
+        s.frame_wgs        = num("SNK_TRACK_FRAME_WGS");
+        s.no_fused_resolve = getenv("SNK_TRACK_NO_FUSED_RESOLVE") != nullptr;
+        s.ppw              = num("SNK_TRACK_PPW");
+        return s;
+    }();
+    return once;
 }
 
 int make_cam(const snk_camera* cam, const double* pose, CamDev* c)
@@ -1612,7 +1581,7 @@ int snk_match_project_coarse(snk_matcher* m, const snk_frame_view* frame, const 
     int* d_match = d_bins + np;  // match[np] | count: one block, one copy back
     memcpy(m->h_in.p, pts, np * sizeof(snk_lm_coarse));
     SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, np * sizeof(snk_lm_coarse), hipMemcpyHostToDevice, m->stream));
-    const int ppw = points_per_wave(n_pts);
+    const int ppw = track_points_per_wave(n_pts, track_switches().ppw);
     hipLaunchKernelGGL(coarse_kernel, dim3(ceil_div(n_pts, 4 * ppw)), dim3(256), 0, m->stream, F, C, S, m->q.as<snk_lm_coarse>(), n_pts, ppw,
                        th, feature_error, direction, d_best, d_bins);
     hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(256), 0, m->stream, d_best, d_bins, n_pts, F.taken, m->t.as<int>(), F.n, 1,
@@ -1655,7 +1624,7 @@ int snk_match_project_fine(snk_matcher* m, const snk_frame_view* frame, const sn
     u8* d_vis    = reinterpret_cast<u8*>(d_cnt + 1);
     memcpy(m->h_in.p, pts, np * sizeof(snk_lm_fine));
     SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, np * sizeof(snk_lm_fine), hipMemcpyHostToDevice, m->stream));
-    const int ppw = points_per_wave(n_pts);
+    const int ppw = track_points_per_wave(n_pts, track_switches().ppw);
     hipLaunchKernelGGL(fine_kernel, dim3(ceil_div(n_pts, 4 * ppw)), dim3(256), 0, m->stream, F, C, S, m->q.as<snk_lm_fine>(), n_pts, ppw, th,
                        ratio, d_best, d_vis);
     hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(256), 0, m->stream, d_best, (const int*)nullptr, n_pts, F.taken,
@@ -1747,22 +1716,18 @@ int snk_match_project_coarse_batch_dev(snk_matcher* m, const snk_frames_dev* fra
     CamDev* cams;
     int *best, *bins, *claim;
     if ((rc = batch_scratch(m, batch, pts_cap, F.cap, cam, poses_dev, &cams, &best, &bins, &claim)) != SNK_OK) return rc;
-    const int ppw = points_per_wave((long long)pts_cap * batch);
-    const size_t flds = frame_lds_host(F.cap, F.cols * F.rows + 1);
-    if (ppw == 64 && flds <= FRAME_LDS_MAX && !no_frame_lds())
+    const TrackBatchPlan P = track_batch_plan(pts_cap, batch, F.cap, F.cols * F.rows + 1, track_switches());
+    if (P.form == TrackForm::frame)
     {
-        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(coarse_frame_kernel), FRAME_LDS_MAX)) != SNK_OK) return rc;
-        const int wgs       = frame_wgs(ceil_div(pts_cap, 1024), batch);
-        const int claim_off = fused_claim_offset(wgs, flds, F.cap);
-        hipLaunchKernelGGL(coarse_frame_kernel, dim3(wgs, batch), dim3(1024), claim_off >= 0 ? (size_t)claim_off + (size_t)F.cap * 4 : flds, m->stream, F,
-                           (const CamDev*)cams, S, pts_dev, n_pts_dev, pts_cap, th, feature_error, direction, best, bins, claim_off, match_idx_dev,
-                           n_matches_dev);
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(coarse_frame_kernel), TRACK_FRAME_LDS_MAX)) != SNK_OK) return rc;
+        hipLaunchKernelGGL(coarse_frame_kernel, dim3(P.wgs, batch), dim3(1024), P.lds, m->stream, F, (const CamDev*)cams, S, pts_dev, n_pts_dev,
+                           pts_cap, th, feature_error, direction, best, bins, P.claim_off, match_idx_dev, n_matches_dev);
         SNK_LAUNCH_CHECK();
-        if (claim_off >= 0) return SNK_OK;  // resolved in the kernel
+        if (P.claim_off >= 0) return SNK_OK;  // resolved in the kernel
     }
     else
-        hipLaunchKernelGGL(coarse_batch_kernel, dim3(ceil_div(pts_cap, 4 * ppw), batch), dim3(256), 0, m->stream, F, (const CamDev*)cams, S,
-                           pts_dev, n_pts_dev, pts_cap, ppw, th, feature_error, direction, best, bins);
+        hipLaunchKernelGGL(coarse_batch_kernel, dim3(ceil_div(pts_cap, 4 * P.ppw), batch), dim3(256), 0, m->stream, F, (const CamDev*)cams, S,
+                           pts_dev, n_pts_dev, pts_cap, P.ppw, th, feature_error, direction, best, bins);
     if ((rc = launch_resolve_batch(m, batch, frames->cap, (const int*)best, (const int*)bins, n_pts_dev, pts_cap, F, claim, 1, match_idx_dev,
                                    n_matches_dev)) != SNK_OK)
         return rc;
@@ -1790,22 +1755,19 @@ static int fine_batch_impl(snk_matcher* m, const snk_frames_dev* frames, const s
     int *best, *bins, *claim;
     if ((rc = batch_scratch(m, batch, pts_cap, F.cap, cam, poses_dev, &cams, &best, &bins, &claim)) != SNK_OK) return rc;
     SNK_HIP_CHECK(hipMemsetAsync(visible_dev, 0, (size_t)batch * pts_cap, m->stream));
-    const int ppw = points_per_wave((long long)pts_cap * batch);
-    const size_t flds = frame_lds_host(F.cap, F.cols * F.rows + 1);
-    if (ppw == 64 && flds <= FRAME_LDS_MAX && !no_frame_lds())
+    const TrackBatchPlan P = track_batch_plan(pts_cap, batch, F.cap, F.cols * F.rows + 1, track_switches());
+    const int ppw          = P.ppw;
+    if (P.form == TrackForm::frame)
     {
         const void* fk = write_valid ? reinterpret_cast<const void*>(fine_frame_kernel<true>) : reinterpret_cast<const void*>(fine_frame_kernel<false>);
-        if ((rc = set_max_lds_once(fk, FRAME_LDS_MAX)) != SNK_OK) return rc;
-        const int wgs = frame_wgs(ceil_div(pts_cap, 1024), batch);
-        const int claim_off = fused_claim_offset(wgs, flds, F.cap);
-        const size_t lds    = claim_off >= 0 ? (size_t)claim_off + (size_t)F.cap * 4 : flds;
+        if ((rc = set_max_lds_once(fk, TRACK_FRAME_LDS_MAX)) != SNK_OK) return rc;
         if (write_valid)
-            hipLaunchKernelGGL(fine_frame_kernel<true>, dim3(wgs, batch), dim3(1024), lds, m->stream, F, (const CamDev*)cams, S, pts_dev,
-                               n_pts_dev, pts_cap, th, ratio, best, visible_dev, claim_off, match_idx_dev, n_matches_dev);
+            hipLaunchKernelGGL(fine_frame_kernel<true>, dim3(P.wgs, batch), dim3(1024), P.lds, m->stream, F, (const CamDev*)cams, S, pts_dev,
+                               n_pts_dev, pts_cap, th, ratio, best, visible_dev, P.claim_off, match_idx_dev, n_matches_dev);
         else
-            hipLaunchKernelGGL(fine_frame_kernel<false>, dim3(wgs, batch), dim3(1024), lds, m->stream, F, (const CamDev*)cams, S, pts_dev,
-                               n_pts_dev, pts_cap, th, ratio, best, visible_dev, claim_off, match_idx_dev, n_matches_dev);
-        if (claim_off >= 0)
+            hipLaunchKernelGGL(fine_frame_kernel<false>, dim3(P.wgs, batch), dim3(1024), P.lds, m->stream, F, (const CamDev*)cams, S, pts_dev,
+                               n_pts_dev, pts_cap, th, ratio, best, visible_dev, P.claim_off, match_idx_dev, n_matches_dev);
+        if (P.claim_off >= 0)
         {
             SNK_LAUNCH_CHECK();
             return SNK_OK;  // resolved in the kernel

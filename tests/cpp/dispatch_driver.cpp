@@ -14,6 +14,19 @@
 //   ba_reg_rows:n6:switches                       ba_sets:<shape>:switches
 //   ba_persist:count:n6:nfc:coop:n_cu:res_persist:res_persist1:res_reg:switches    "wgs,one,rows"
 //   ba_persist_imp:np:nfc:coop:n_cu:res:switches                                    "wgs,one,rows"
+//   orb_band:n_strips:h:batch:bh_env              orb_cpw:total_cells:batch:cpw_env (the number)
+//   orb_fast:quads:cpw                            orb_harris:total_cells:harris:per_cell
+//   orb_dist:n_levels:batch:level_cap:harris      orb_desc:switches
+//   orb_xcd:gx:batch                              "x,y"
+//   orb_sched:batch:parts:stagger:split_min_batch:one_stream     orb_sched_n:... (chains, or parts of the staggered schedule)
+//   orb_geom:<config>:switches                    per level "w,h,scale,nfeat,pitch,strip_stride,n_strips,store_end,n_bands,ncols,nrows,wcell,hcell,slot_cap,nroots", joined by ';'
+//   orb_slice:<config>:switches                   "tile_pitch_dw,s_pitch,off_s,off_surv,off_list,off_cnt,lds_wave,surv_cap,quads,cells,slots,units,list_fits,fast_fits"
+//   orb_plan:<config>:batch:aligned0:harris:stages:switches      "levels;cpw/quads;harris;dist;desc" as run_part's plan line names them
+//   orb_plan_nums:...                             "fast_gx,fast_lds,harris_gx,lds_cap,dist_lds,large_workers,queue_memset,desc_gx,desc_nb,dfake,blur_mode;n_bands.gx per level"
+//     <config> = w:h:nfeatures:n_levels:scale_factor:level_cap;  switches: as above with the names of OrbSwitches' comments (SNK_ORB_ left off)
+//   track_form:pts_cap:batch:cap:ncell1:no_frame_lds:ppw_env     track_plan:pts_cap:batch:cap:ncell1:no_frame_lds:frame_wgs:no_fused_resolve:ppw_env  "ppw,wgs,claim_off,lds"
+//   track_wgs:chunks:batch:forced                 track_claim:wgs:frame_lds:cap:off
+//   track_ppw:total_points:ppw_env                track_lds:cap:ncell1
 //   const:NAME
 // Exit status 2 on an argument it cannot read.
 #include <cstdio>
@@ -101,6 +114,93 @@ static bool read_switches(const std::string& list, snk::BaSwitches& s)
     return true;
 }
 
+// "LEVEL_BH=22,UNFUSED" -> OrbSwitches, by the rules of orb_switches() in orb.hip
+static bool read_orb_switches(const std::string& list, snk::OrbSwitches& s)
+{
+    size_t p = 0;
+    while (p < list.size())
+    {
+        size_t q = list.find(',', p);
+        if (q == std::string::npos) q = list.size();
+        const std::string item = list.substr(p, q - p);
+        p                      = q + 1;
+        const size_t eq        = item.find('=');
+        const std::string name = item.substr(0, eq);
+        const long long v      = eq == std::string::npos ? 0 : std::atoll(item.c_str() + eq + 1);
+        const auto is          = [&](const char* n) { return name == n; };
+        if (is("BALANCED_STRIPS")) s.balanced_strips = true;
+        else if (is("FAST_SURV_CAP")) s.fast_surv_cap = v < 128 ? 128 : (int)v;
+        else if (is("PARTS")) s.parts = v < 1 ? 1 : v > 4 ? 4 : (int)v;
+        else if (is("STAGGER")) s.stagger = v >= 2 ? (v > 16 ? 16 : (int)v) : 0;
+        else if (is("BLUR_IN_DESCRIBE")) s.blur_in_describe = true;
+        else if (is("BLUR_TILED")) s.blur_tiled = true;
+        else if (is("DESC_NO_DMA")) s.desc_no_dma = true;
+        else if (is("DESC_FAKE")) s.desc_fake_on = true, s.desc_fake = (int)v;
+        else if (is("UNFUSED")) s.unfused = true;
+        else if (is("LEVEL_BH")) s.level_bh = (int)v;
+        else if (is("FAST_CPW")) s.fast_cpw = (int)v;
+        else if (is("FAST_STOP")) s.fast_stop = (int)v;
+        else if (is("FAST_LDS_WG")) s.fast_lds_wg = (size_t)v;
+        else if (is("DIST_TIMING")) s.dist_timing = true;
+        else if (is("DIST_KEY_LOOP")) s.dist_key_loop = true;
+        else if (is("HARRIS_PER_CELL")) s.harris_per_cell = true;
+        else if (is("ONE_STREAM")) s.one_stream = true;
+        else return false;
+    }
+    return true;
+}
+
+// orb_geom / orb_slice / orb_plan / orb_plan_nums: the fields "w:h:nfeatures:n_levels:scale_factor:level_cap" in front
+constexpr size_t ORB_CONFIG_ARGS = 6;
+static const char* orb_layout_of(const std::vector<std::string>& f, const snk::OrbSwitches& sw, snk::Layout& L)
+{
+    return snk::orb::layout(L, std::atoi(f[1].c_str()), std::atoi(f[2].c_str()), std::atoi(f[3].c_str()), (float)std::atof(f[5].c_str()), std::atoi(f[4].c_str()),
+                            std::atoi(f[6].c_str()), sw.balanced_strips, sw.fast_surv_cap);
+}
+
+static int orb_entry(const std::string& e, const std::vector<std::string>& f, const snk::OrbSwitches& sw)
+{
+    snk::Layout L;
+    const char* bad = orb_layout_of(f, sw, L);
+    if (e == "orb_geom")
+    {
+        for (int l = 0; l < L.n_levels; ++l)
+        {
+            const snk::LevelInfo& v = L.lv[l];
+            std::printf("%s%d,%d,%.9g,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", l ? ";" : "", v.w, v.h, (double)v.scale, v.nfeat, v.pitch, v.strip_stride, v.n_strips, v.store_end,
+                        v.n_bands, v.ncols, v.nrows, v.wcell, v.hcell, v.slot_cap, v.nroots);
+        }
+        std::printf("\n");
+    }
+    else if (e == "orb_slice")
+        std::printf("%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d\n", L.f_tile_pitch_dw, L.f_s_pitch, L.f_off_s, L.f_off_surv, L.f_off_list, L.f_off_cnt, L.f_lds_wave,
+                    L.f_surv_cap, snk::orb::fast_quads(L), L.total_cells, L.total_slots, L.total_units, (int)(bad == nullptr), (int)snk::orb::fast_fits(L));
+    else
+    {
+        const size_t a        = ORB_CONFIG_ARGS + 1;
+        const snk::OrbPlan P  = snk::orb_plan(L, std::atoi(f[a].c_str()), std::atoi(f[a + 1].c_str()) != 0, std::atoi(f[a + 2].c_str()) != 0, std::atoi(f[a + 3].c_str()),
+                                              (float)std::atof(f[5].c_str()), sw);
+        if (e == "orb_plan")
+        {
+            for (int l = 0; l < P.n_levels; ++l)
+            {
+                char tok[8];
+                snk::orb_level_token(P.lv[l], tok);
+                std::printf("%s%s", l ? "," : "", tok);
+            }
+            std::printf(";%d/%d;%s;%s;%s\n", P.fast_run ? P.fast_cpw : 0, P.fast_quads, snk::orb_name(P.harris), snk::orb_name(P.dist), snk::orb_name(P.desc));
+        }
+        else
+        {
+            std::printf("%d,%zu,%d,%d,%zu,%d,%d,%d,%d,%d,%d", P.fast_gx, P.fast_lds, P.harris_gx, P.dist_lds_cap, P.dist_lds, P.large_workers, (int)P.queue_memset, P.desc_gx,
+                        P.desc_nb, P.dfake, P.blur_mode);
+            for (int l = 0; l < P.n_levels; ++l) std::printf("%s%d.%d", l ? "," : ";", P.lv[l].n_bands, P.lv[l].gx);
+            std::printf("\n");
+        }
+    }
+    return 0;
+}
+
 constexpr size_t BA_SHAPE_ARGS = 19;
 static snk::BaShape read_shape(const std::vector<long long>& v)
 {
@@ -131,6 +231,20 @@ int main(int argc, char** argv)
         {
             std::fprintf(stderr, "dispatch_driver: cannot read the switches of %s\n", argv[a]);
             return 2;
+        }
+        const bool orb_sw = e == "orb_desc" || e == "orb_geom" || e == "orb_slice" || e == "orb_plan" || e == "orb_plan_nums";  // the last field: the switches
+        snk::OrbSwitches osw;
+        if (orb_sw)
+        {
+            const size_t want = e == "orb_desc" ? 2 : ORB_CONFIG_ARGS + 2 + (e == "orb_plan" || e == "orb_plan_nums" ? 4 : 0);
+            if (f.size() != want || !read_orb_switches(f.back(), osw))
+            {
+                std::fprintf(stderr, "dispatch_driver: cannot read %s\n", argv[a]);
+                return 2;
+            }
+            if (e == "orb_desc") std::printf("%s\n", snk::orb_name(snk::orb_desc_form(osw)));
+            else orb_entry(e, f, osw);
+            continue;
         }
         if (e != "const")
             for (size_t i = 1; i + (ba ? 1 : 0) < f.size(); ++i) v.push_back(std::atoll(f[i].c_str()));
@@ -168,6 +282,38 @@ int main(int argc, char** argv)
         else if (e == "pose_host_carve" && n == 2) std::printf("%d\n", snk::pose_host_carve((int)v[0], (int)v[1]));
         else if (e == "pose_batch" && n == 5) std::printf("%s\n", name(snk::pose_batch_form((int)v[0], (int)v[1], (int)v[2], (int)v[3], v[4] != 0)));
         else if (e == "pose_batch_carve" && n == 4) std::printf("%d\n", snk::pose_batch_carve((int)v[0], (int)v[1], (int)v[2], v[3] != 0));
+        else if (e == "orb_band" && n == 4) std::printf("%s\n", snk::orb_name(snk::orb_band_form((int)v[0], (int)v[1], (int)v[2], (int)v[3])));
+        else if (e == "orb_cpw" && n == 3) std::printf("%d\n", snk::orb_fast_cpw((int)v[0], (int)v[1], (int)v[2]));
+        else if (e == "orb_fast" && n == 2) std::printf("%s\n", snk::orb_name(snk::orb_fast_form((int)v[0], v[1] > 1)));
+        else if (e == "orb_harris" && n == 3) std::printf("%s\n", snk::orb_name(snk::orb_harris_form((int)v[0], v[1] != 0, v[2] != 0)));
+        else if (e == "orb_dist" && n == 4) std::printf("%s\n", snk::orb_name(snk::orb_dist_form((int)v[0], (int)v[1], (int)v[2], v[3] != 0)));
+        else if (e == "orb_xcd" && n == 2)
+        {
+            int x, y;
+            snk::orb_xcd_grid((int)v[0], (int)v[1], x, y);
+            std::printf("%d,%d\n", x, y);
+        }
+        else if ((e == "orb_sched" || e == "orb_sched_n") && n == 5)
+        {
+            int parts;
+            const snk::OrbSchedule sc = snk::orb_schedule((int)v[0], (int)v[1], (int)v[2], (int)v[3], v[4] != 0, parts);
+            if (e == "orb_sched") std::printf("%s\n", snk::orb_name(sc));
+            else std::printf("%d\n", parts);
+        }
+        else if ((e == "track_form" && n == 6) || (e == "track_plan" && n == 8))
+        {
+            snk::TrackSwitches ts;
+            ts.no_frame_lds = v[4] != 0;
+            if (e == "track_form") ts.ppw = (int)v[5];
+            else ts.frame_wgs = (int)v[5], ts.no_fused_resolve = v[6] != 0, ts.ppw = (int)v[7];
+            const snk::TrackBatchPlan P = snk::track_batch_plan((int)v[0], (int)v[1], (int)v[2], (int)v[3], ts);
+            if (e == "track_form") std::printf("%s\n", snk::track_name(P.form));
+            else std::printf("%d,%d,%d,%zu\n", P.ppw, P.wgs, P.claim_off, P.lds);
+        }
+        else if (e == "track_wgs" && n == 3) std::printf("%d\n", snk::track_frame_wgs((int)v[0], (int)v[1], (int)v[2]));
+        else if (e == "track_claim" && n == 4) std::printf("%d\n", snk::track_fused_claim_offset((int)v[0], (size_t)v[1], (int)v[2], v[3] != 0));
+        else if (e == "track_ppw" && n == 2) std::printf("%d\n", snk::track_points_per_wave(v[0], (int)v[1]));
+        else if (e == "track_lds" && n == 2) std::printf("%zu\n", snk::track_frame_lds((int)v[0], (int)v[1]));
         else if (e == "const" && f.size() == 2)
         {
             const std::string& c = f[1];
@@ -198,6 +344,18 @@ int main(int argc, char** argv)
             else if (c == "BA_GRAPH_CHAIN_MIN") val = snk::BA_GRAPH_CHAIN_MIN;
             else if (c == "SUM_NB") val = snk::SUM_NB;
             else if (c == "PERSIST_WGS_MAX") val = snk::PERSIST_WGS_MAX;
+            else if (c == "ORB_BAND_MIN_WAVES") val = snk::ORB_BAND_MIN_WAVES;
+            else if (c == "ORB_WAVE_SLOTS") val = snk::ORB_WAVE_SLOTS;
+            else if (c == "ORB_FAST_CPW_DEFAULT") val = snk::ORB_FAST_CPW_DEFAULT;
+            else if (c == "ORB_FAST_MIN_ROUNDS") val = snk::ORB_FAST_MIN_ROUNDS;
+            else if (c == "ORB_XCD_MIN_BATCH") val = snk::ORB_XCD_MIN_BATCH;
+            else if (c == "ORB_DIST_ONE_MAX_WGS") val = snk::ORB_DIST_ONE_MAX_WGS;
+            else if (c == "ORB_DIST_LARGE_WGS") val = snk::ORB_DIST_LARGE_WGS;
+            else if (c == "ORB_DIST_SMALL_CAP") val = snk::orb::DIST_SMALL_CAP;
+            else if (c == "ORB_DIST_LDS_MAX") val = (int)snk::orb::DIST_LDS_MAX;
+            else if (c == "ORB_DIST_LARGE_LDS_MAX") val = (int)snk::orb::DIST_LARGE_LDS_MAX;
+            else if (c == "TRACK_FRAME_LDS_MAX") val = snk::TRACK_FRAME_LDS_MAX;
+            else if (c == "TRACK_PPW_POINTS") val = snk::TRACK_PPW_POINTS;
             else
             {
                 std::fprintf(stderr, "dispatch_driver: no constant %s\n", c.c_str());

@@ -11,6 +11,16 @@ A row is (entry, shape, form).  entry names a function of dispatch.hpp, shape is
   pose_batch    (stride, batch, n_cu, waves_env, no_lds)     stride = cap (frame form) or pts_cap (matches form)
   ba_lm         ba(...): the fields of BaShape, `recording`, and the switches as one string -- the five forms of an LM iteration of
                 the BA solver, "linearisation/camera pass/Schur complement/PCG/update and cost"
+  orb_band      (n_strips, h, batch, bh_env)                 a level pass of the extractor: rows per band of level_kernel
+  orb_fast      (quads, cpw)                                 fast_kernel<NQ, LOOP>
+  orb_harris    (total_cells, harris, per_cell)              harris: "orb.response" = 1
+  orb_dist      (n_levels, batch, level_cap, harris)
+  orb_desc      (switches,)                                  the extractor's switches as one string ("NAME=VALUE,..." without SNK_ORB_)
+  orb_sched     (batch, parts, stagger, split_min_batch, one_stream)   parts / stagger: the handle's (snk_orb_set_chains / _set_stagger)
+  orb_plan      orb(...): an extractor's configuration, a launch chain and the switches -- "levels;cpw/quads;harris;dist;desc", the
+                fields of run_part's plan line (a level: rows per band, "r" resize_kernel first, "t" tiny, "u" unaligned, "+" also
+                writes level l + 1, "-" no pixels)
+  track_form    (pts_cap, batch, cap, ncell1, no_frame_lds, ppw_env)   a batched projection matcher
 """
 import re
 import subprocess
@@ -42,6 +52,24 @@ def ba(sw="", **kw):
 SETS = dict(set_ok=1, items=2)   # what a hand-over of >= 8 windows adds: the point-major work items
 SETS_ON = "SCHUR_SET_MIN_ITEMS=1"
 GLOBAL = dict(nfc=299, np=9000, ni=300, wv=9000)  # a 300-keyframe global scene: the multi-workgroup PCG
+
+# ---- ORB extractor: a configuration (OrbParams' fields the geometry depends on), a launch chain, the switches
+ORB_FIELDS = ("w", "h", "nfeat", "levels", "scale", "cap", "batch", "aligned", "harris", "stages")
+# every switch of OrbSwitches (dispatch.hpp), as the environment names it
+ORB_SWITCHES = ["BALANCED_STRIPS", "FAST_SURV_CAP", "PARTS", "STAGGER", "BLUR_IN_DESCRIBE", "BLUR_TILED", "DESC_NO_DMA", "DESC_FAKE", "UNFUSED",
+                "LEVEL_BH", "FAST_CPW", "FAST_STOP", "FAST_LDS_WG", "DIST_TIMING", "DIST_KEY_LOOP", "HARRIS_PER_CELL", "ONE_STREAM"]
+TRACK_SWITCHES = ["NO_FRAME_LDS", "FRAME_WGS", "NO_FUSED_RESOLVE", "PPW"]
+
+
+def orb(sw="", **kw):
+    """An extractor launch chain.  Defaults: one aligned 752 x 480 image, 1000 features on 4 levels of 1.2 (the EuRoC configuration), FAST
+    score as the response, both halves of the chain."""
+    d = dict(w=752, h=480, nfeat=1000, levels=4, scale=1.2, cap=0, batch=1, aligned=1, harris=0, stages=3)
+    d.update(kw)
+    return tuple(d[f] for f in ORB_FIELDS) + (sw,)
+
+
+KITTI = dict(w=1241, h=376, nfeat=2000, levels=8)
 
 FORMS = [
     # ---- kNN-2: vector4 needs batch * nq_cap >= 16384 AND (nq_cap < 24 OR nt_cap < 24)
@@ -124,6 +152,53 @@ FORMS = [
     ("ba_lm", ba("NO_SCHUR_WIDE,NO_SCHUR_SET"), "point_wave/cam256/pass1/small/update_wave"),
     ("ba_lm", ba("NO_UPDATE_COST", B=256, **SETS), "fused3/cam64_xcd/in_fused/small/update_wave"),
     ("ba_lm", ba("GRAPH_CHAINS=2,GRAPH_FIRST", B=256, rec=1, **SETS), "fused3/cam64_xcd/in_fused/small/update_cost"),
+    # ---- ORB, level passes: 64 rows per band from 2048 strips x bands on, else 22 from 2048 on, else 8
+    ("orb_band", (4, 480, 64, 0), "bh64"),        # 4 * 64 * ceil(480 / 64) = 2048 exactly
+    ("orb_band", (4, 480, 24, 0), "bh22"),        # 96 * 8 = 768 < 2048 <= 96 * 22 = 2112
+    ("orb_band", (4, 480, 1, 0), "bh8"),          # a per-frame call
+    ("orb_band", (4, 480, 1, 22), "bh22"),        # SNK_ORB_LEVEL_BH
+    # ---- ORB, FAST: the compile-time tile pitches of the layout and one cell per wavefront or a loop over cpw cells
+    ("orb_fast", (3, 1), "single3"), ("orb_fast", (4, 1), "single4"), ("orb_fast", (0, 1), "single0"),
+    ("orb_fast", (3, 8), "loop3"), ("orb_fast", (4, 2), "loop4"), ("orb_fast", (0, 8), "loop0"),
+    ("orb_harris", (828, 0, 0), "none"), ("orb_harris", (828, 1, 0), "dense"), ("orb_harris", (0, 1, 0), "none"), ("orb_harris", (828, 1, 1), "per_cell"),
+    # ---- ORB, distribution: one launch at the full carve up to 128 (image, level) workgroups
+    ("orb_dist", (4, 32, 8192, 0), "one_full"),      # 128
+    ("orb_dist", (3, 43, 8192, 0), "small_drain"),   # 129
+    ("orb_dist", (4, 1, 8192, 1), "small_drain"),    # the Harris ranks do not fit beside the full carve
+    ("orb_dist", (4, 1, 2048, 0), "one_small"),      # level_cap <= 2048: the small carve holds every level
+    ("orb_dist", (4, 2048, 1024, 1), "one_small"),
+    ("orb_dist", (4, 1, 4096, 0), "one_full"),
+    # ---- ORB, descriptors
+    ("orb_desc", ("",), "dma"),
+    ("orb_desc", ("BLUR_IN_DESCRIBE",), "blur_in"),
+    ("orb_desc", ("DESC_NO_DMA",), "registers"),
+    ("orb_desc", ("BLUR_TILED",), "dma_tiled"),
+    ("orb_desc", ("BLUR_TILED,DESC_NO_DMA",), "registers"),   # the tiled planes need the DMA path: row-major
+    ("orb_desc", ("BLUR_TILED,DESC_FAKE=1",), "dma"),
+    # ---- ORB, launch chains of a batch
+    ("orb_sched", (2048, 1, 0, 8, 0), "one_chain"),
+    ("orb_sched", (2048, 2, 0, 8, 0), "chains"),
+    ("orb_sched", (7, 2, 0, 8, 0), "one_chain"),     # below split_min_batch
+    ("orb_sched", (64, 1, 4, 8, 0), "staggered"),
+    ("orb_sched", (8, 1, 5, 8, 0), "one_chain"),     # fewer than two images per part
+    ("orb_sched", (2048, 2, 4, 8, 1), "one_chain"),  # SNK_ORB_ONE_STREAM
+    # ---- ORB, whole chains: the two calls of tests/test_orb_plan_gpu.py, the benchmark's batch, and the paths a configuration selects
+    ("orb_plan", orb(), "8+,8+,8+,8;1/3;none;one_full;dma"),                                          # snk_orb_detect on one 752 x 480 image
+    ("orb_plan", orb(w=160, h=120, nfeat=500, batch=16), "8+,8+,8+,8;1/4;none;one_full;dma"),         # 16 images of 160 x 120: 40-pixel cells on level 2, 64 workgroups
+    ("orb_plan", orb(batch=2048), "64+,64+,64+,64;8/3;none;small_drain;dma"),
+    ("orb_plan", orb(batch=2048, aligned=0), "64u+,64+,64+,64;8/3;none;small_drain;dma"),
+    ("orb_plan", orb(batch=64, harris=1, **KITTI), "64+,22+,22+,22+,8+,8+,8+,8;2/3;dense;small_drain;dma"),   # 7 * 64 strips x 6 bands = 2688 on level 0
+    ("orb_plan", orb(scale=2.5), "8,r8,r8,r8;1/4;none;one_full;dma"),                                 # scale factor > 2: stand-alone resize_kernel
+    ("orb_plan", orb("UNFUSED"), "8,r8,r8,r8;1/3;none;one_full;dma"),
+    ("orb_plan", orb(w=40, h=40, nfeat=500, levels=16), "8+,8+,8+,8+,8+,8+,8+,8+,8+,8+,t,rt,rt,rt,rt,rt;0/0;none;one_full;dma"),  # tiny levels, no cells
+    ("orb_plan", orb(w=40, h=40, nfeat=500, levels=16, scale=2.0), "8+,8+,8+,t,rt,rt,rt,-,-,-,-,-,-,-,-,-;0/0;none;one_full;dma"),  # 40, 20, 10, 5, 2, 1, 1, then levels scaled to nothing
+    # ---- projection matchers, batched: the frame in LDS from 64 points per wavefront on (8192 * 64 points in the call)
+    ("track_form", (512, 1024, 1000, 2401, 0, 0), "frame"),   # 524288 points
+    ("track_form", (512, 1023, 1000, 2401, 0, 0), "batch"),
+    ("track_form", (10000, 1024, 2258, 2401, 0, 0), "frame"),  # 147428 bytes of LDS ...
+    ("track_form", (10000, 1024, 2259, 2401, 0, 0), "batch"),  # ... 147492 > 144 KB = 147456
+    ("track_form", (512, 1024, 1000, 2401, 1, 0), "batch"),   # SNK_TRACK_NO_FRAME_LDS
+    ("track_form", (512, 8, 1000, 2401, 0, 64), "frame"),     # SNK_TRACK_PPW=64
 ]
 
 # the values of the enums of dispatch.hpp (the CPU test reads the header and compares)
@@ -134,21 +209,32 @@ ENUMS = {"Knn2Form": ["vector1", "vector4", "mfma"], "StereoForm": ["frame", "co
          "BaSchurForm": ["none", "in_fused", "mfma32", "mfma33", "mfma43", "set42", "set63", "pass4", "pass1"],
          "BaPcgForm": ["none", "small", "solve_lds", "solve_global", "persist_reg16", "persist_reg8", "persist1", "persist", "launches", "imp_persist",
                        "imp_launches"],
-         "BaUpdateForm": ["update_cost", "update_wave", "update_point"]}
+         "BaUpdateForm": ["update_cost", "update_wave", "update_point"],
+         "OrbBandForm": ["bh64", "bh22", "bh8"], "OrbFastForm": ["single0", "single3", "single4", "loop0", "loop3", "loop4"],
+         "OrbHarrisForm": ["none", "per_cell", "dense"], "OrbDistForm": ["one_full", "one_small", "small_drain"],
+         "OrbDescForm": ["registers", "blur_in", "dma", "dma_tiled"], "OrbSchedule": ["one_chain", "chains", "staggered"],
+         "TrackForm": ["frame", "batch"]}
 # the enum of an entry's form; an entry whose form is "a/b/..." names one enum per part
 ENUM_OF = {"knn2": "Knn2Form", "stereo_host": "StereoForm", "stereo_batch": "StereoForm", "pose_host": "PoseForm", "pose_batch": "PoseForm",
-           "ba_lm": ("BaLinForm", "BaCamForm", "BaSchurForm", "BaPcgForm", "BaUpdateForm")}
+           "ba_lm": ("BaLinForm", "BaCamForm", "BaSchurForm", "BaPcgForm", "BaUpdateForm"),
+           "orb_band": "OrbBandForm", "orb_fast": "OrbFastForm", "orb_harris": "OrbHarrisForm", "orb_dist": "OrbDistForm", "orb_desc": "OrbDescForm",
+           "orb_sched": "OrbSchedule", "orb_plan": (None, None, "OrbHarrisForm", "OrbDistForm", "OrbDescForm"), "track_form": "TrackForm"}
 # forms that no shape selects (test_match_forms_gpu.py / test_pose_forms_gpu.py run each once in a child process under its switch;
 # the BA forms: the rows of tests/test_zy_ba_variants_gpu.py)
 ENV_ONLY = {("PoseForm", "wave4_global"), ("StereoForm", "sort16"),
             ("BaLinForm", "fused3_sums"), ("BaLinForm", "fused4"), ("BaCamForm", "cam_sum"), ("BaCamForm", "cam64_2d"), ("BaSchurForm", "mfma32"),
-            ("BaSchurForm", "mfma33"), ("BaSchurForm", "set42"), ("BaSchurForm", "set63"), ("BaPcgForm", "solve_lds")}
+            ("BaSchurForm", "mfma33"), ("BaSchurForm", "set42"), ("BaSchurForm", "set63"), ("BaPcgForm", "solve_lds"),
+            # the extractor: tests/test_zx_frontend_variants_gpu.py and test_orb_gpu.py run each under its switch
+            ("OrbHarrisForm", "per_cell"), ("OrbDescForm", "registers"), ("OrbDescForm", "blur_in"), ("OrbDescForm", "dma_tiled")}
 
 
 def parts(entry, form):
     """(enum, value) for every part of an entry's form."""
     enums = ENUM_OF[entry]
-    return [(enums, form)] if isinstance(enums, str) else list(zip(enums, form.split("/"), strict=True))
+    if isinstance(enums, str):
+        return [(enums, form)]
+    # "a/b/..." names one enum per part; the extractor's "levels;cpw/quads;a;b;c" has two parts that are no enum (None)
+    return [(e, v) for e, v in zip(enums, form.split(";" if entry == "orb_plan" else "/"), strict=True) if e is not None]
 
 
 def ba_env_switches(environ):
@@ -166,6 +252,27 @@ def ba_plan_lines(stderr):
             continue
         kv = dict(re.findall(r"(\w+)=(\S+)", ln))
         out.append((tuple(int(kv[f]) for f in BA_FIELDS), "/".join(kv[k] for k in ("lin", "cam", "schur", "pcg", "update"))))
+    return out
+
+
+def orb_env_switches(environ):
+    """The extractor's switches of an environment as the `switches` argument of the driver's orb_* entries."""
+    return ",".join(f"{n}={environ['SNK_ORB_' + n] or 0}" for n in ORB_SWITCHES if "SNK_ORB_" + n in environ)
+
+
+def orb_plan_lines(stderr):
+    """The plan lines of run_part under SNK_DEBUG ("snake_hip: orb plan w=... desc=..."), each as (driver query for orb_plan without the
+    switches, "levels;cpw/quads;harris;dist;desc")."""
+    import numpy as np
+
+    out = []
+    for ln in stderr.splitlines():
+        if not ln.startswith("snake_hip: orb plan "):
+            continue
+        kv = dict(re.findall(r"(\w+)=(\S+)", ln))
+        # the scale factor is printed with nine digits (the float itself): back to its shortest decimal, 1.20000005 -> 1.2
+        out.append((tuple(float(str(np.float32(kv[f]))) if f == "scale" else int(kv[f]) for f in ORB_FIELDS),
+                    ";".join(kv[k] for k in ("level", "fast", "harris_form", "dist", "desc"))))
     return out
 
 

@@ -9,7 +9,8 @@ import forms
 from forms import ENUM_OF, ENUMS, ENV_ONLY, FORMS
 
 SWITCH_ARGS = {"knn2": [3], "stereo_host": [1], "stereo_batch": [2, 3], "pose_host": [2], "pose_batch": [3, 4],
-               "ba_lm": [len(forms.BA_FIELDS)]}  # environment switches in a shape
+               "ba_lm": [len(forms.BA_FIELDS)], "orb_band": [3], "orb_fast": [], "orb_harris": [2], "orb_dist": [], "orb_desc": [0], "orb_sched": [4],
+               "orb_plan": [len(forms.ORB_FIELDS)], "track_form": [4, 5]}  # environment switches in a shape
 
 
 @pytest.fixture(scope="module")
@@ -192,3 +193,130 @@ def test_ba_switch_lists_agree():
     handover = set(re.findall(r'"SNK_BA_(\w+)"', (csrc / "ba_handover.hip").read_text()))
     assert handover == {"NO_BIG_ITEMS", "SCHUR_SET_MIN_ITEMS", "PROFILE_CREATE", "HOST_THREADS", "NO_HOST_POOL", "FILL_CHUNKS", "HOST_ENTRIES",
                         "BECNT_BUDGET", "CHECK_LISTS"}
+
+
+ORB_CONSTANTS = {"ORB_BAND_MIN_WAVES": 2048, "ORB_WAVE_SLOTS": 8192, "ORB_FAST_CPW_DEFAULT": 8, "ORB_FAST_MIN_ROUNDS": 4, "ORB_XCD_MIN_BATCH": 16,
+                 "ORB_DIST_ONE_MAX_WGS": 128, "ORB_DIST_LARGE_WGS": 256, "ORB_DIST_SMALL_CAP": 2048,
+                 # 19 bytes per candidate + 16; the 2048-candidate carve with the Harris ranks (4 bytes each + 16) is the smaller one
+                 "ORB_DIST_LDS_MAX": 8192 * 19 + 16, "ORB_DIST_LARGE_LDS_MAX": 8192 * 19 + 16,
+                 "TRACK_FRAME_LDS_MAX": 144 * 1024, "TRACK_PPW_POINTS": 8192}
+
+
+def test_orb_and_track_constants(driver):
+    names = list(ORB_CONSTANTS)
+    assert dict(zip(names, map(int, forms.ask(driver, [("const", (n,)) for n in names])))) == ORB_CONSTANTS
+    assert 2048 * 19 + 16 + 4 * 2048 + 16 < 8192 * 19 + 16 <= 160 * 1024
+
+
+def test_orb_thresholds_from_both_sides(driver):
+    """Both neighbours of every threshold of orb_plan's parts."""
+    ask = lambda *q: forms.ask(driver, list(q))
+    # rows per band: strips * ceil(h / bh) = 2047 and 2048, for 64 and for 22 rows (23 * 89 = 2047, 2048 = 2 * 1024; 1 strip x 2047 / 2048 images)
+    assert ask(("orb_band", (1, 64, 2047, 0)), ("orb_band", (1, 64, 2048, 0)), ("orb_band", (89, 23 * 64, 1, 0)), ("orb_band", (2, 1024 * 64, 1, 0)),
+               ("orb_band", (89, 23 * 22, 1, 0)), ("orb_band", (127, 16 * 22, 1, 0)), ("orb_band", (128, 16 * 22, 1, 0)), ("orb_band", (1, 22, 2047, 0)),
+               ("orb_band", (1, 65, 1024, 0)),                                   # ceil: 65 rows are two bands of 64
+               ("orb_band", (1, 64, 2048, 8)), ("orb_band", (1, 22, 1, 64)), ("orb_band", (1, 64, 2048, 23))) == \
+        ["bh22", "bh64", "bh22", "bh64", "bh8", "bh8", "bh22", "bh8", "bh64", "bh8", "bh64", "bh64"]
+    # cells per wavefront: halved while cell_waves / cpw < 32768 (four rounds of 8192 wavefront slots)
+    assert [int(a) for a in ask(("orb_cpw", (32768 * 8, 1, 0)), ("orb_cpw", (32768 * 8 - 1, 1, 0)),       # / 8 = 32768 and 32767
+                                ("orb_cpw", (32768 * 4, 1, 0)), ("orb_cpw", (32768 * 4 - 1, 1, 0)),
+                                ("orb_cpw", (32768 * 2, 1, 0)), ("orb_cpw", (32768 * 2 - 1, 1, 0)),
+                                ("orb_cpw", (828, 2048, 0)), ("orb_cpw", (828, 1, 0)), ("orb_cpw", (1 << 20, 1 << 15, 0)),   # past 2^31 cells
+                                ("orb_cpw", (828, 1, 64)), ("orb_cpw", (828, 2048, 1)), ("orb_cpw", (828, 2048, 65)))] == \
+        [8, 4, 4, 2, 2, 1, 8, 1, 8, 64, 1, 8]
+    # one distribute launch: n_levels * batch = 128 and 129; never under Harris; the small carve alone when it holds level_cap
+    assert ask(("orb_dist", (8, 16, 8192, 0)), ("orb_dist", (1, 129, 8192, 0)), ("orb_dist", (8, 16, 8192, 1)), ("orb_dist", (1, 1, 4096, 1)),
+               ("orb_dist", (1, 1, 2048, 0)), ("orb_dist", (1, 1, 2048, 1)), ("orb_dist", (16, 65535, 256, 0)), ("orb_dist", (16, 65535, 8192, 0))) == \
+        ["one_full", "small_drain", "small_drain", "small_drain", "one_small", "one_small", "one_small", "small_drain"]
+    # the carve and its capacity, the drain launch's workers, the queue counter's fill: fast_gx, fast_lds, harris_gx, lds_cap, dist_lds,
+    # large_workers, queue_memset, desc_gx, desc_nb, dfake, blur_mode; then n_bands.gx per level
+    nums = lambda *shapes: [([int(x) for x in a.split(";")[0].split(",")], a.split(";")[1]) for a in forms.ask(driver, [("orb_plan_nums", sh) for sh in shapes])]
+    orb = forms.orb
+    carve = lambda cap: cap * 19 + 16
+    (a, al), (b, _), (c, _), (d, _), (e, _), (f, _) = nums(orb(), orb(batch=33), orb(harris=1), orb(cap=1024, harris=1), orb(stages=1), orb(stages=2))
+    assert a[3:7] == [8192, carve(8192), 4, 0] and b[3:7] == [2048, carve(2048), 132, 0]
+    assert c[3:5] == [2048, carve(2048) + 4 * 2048 + 16] and d[3:5] == [1024, carve(1024) + 4 * 1024 + 16]
+    assert (a[6], e[6], f[6]) == (0, 1, 1)                       # fast_kernel resets the counter only when the whole chain is one call's
+    assert nums(orb(batch=300))[0][0][5] == 256
+    # one image of 752 x 480: 828 cells, one per wavefront, four wavefronts of 4240 bytes; bands of 8 rows, strips x bands / 4 workgroups
+    assert a[0:2] == [207, 4 * 4240] and al == "60.60,50.38,42.32,35.18" and a[7:9] == [ceil_div(325, 16), 1]
+    g, h, i = nums(orb(batch=2048), orb("FAST_LDS_WG=65536"), orb("FAST_LDS_WG=999999"))
+    assert g[0][0] == ceil_div(828, 32) and g[1] == "8.8,7.6,6.5,5.3" and g[0][8] == 2048 and (h[0][1], i[0][1]) == (65536, 160 * 1024)
+    assert nums(orb(batch=17))[0][0][8] == 24 and nums(orb(batch=15))[0][0][8] == 15                   # describe_kernel's image slots: eights from 16 on
+    assert [n[0][10] for n in nums(orb("BLUR_IN_DESCRIBE"), orb("BLUR_TILED"), orb("BLUR_TILED,DESC_NO_DMA"), orb("BLUR_TILED,DESC_FAKE=0"), orb("DESC_FAKE=2"))] == \
+        [1, 2, 0, 0, 0]
+    assert nums(orb("DESC_FAKE=2"))[0][0][9] == 2
+    # Harris: 16 cells per wavefront, or one
+    assert nums(orb(harris=1))[0][0][2] == ceil_div(ceil_div(828, 16), 4) and nums(orb("HARRIS_PER_CELL", harris=1))[0][0][2] == 207
+    # XCD-aware grids: batch 15 and 16
+    assert ask(("orb_xcd", (207, 15)), ("orb_xcd", (207, 16)), ("orb_xcd", (207, 17)), ("orb_xcd", (3, 1))) == ["207,15", "1656,2", "1656,3", "3,1"]
+    # launch chains: split_min_batch, two images per staggered part, parts capped by the batch
+    assert ask(("orb_sched", (8, 2, 0, 8, 0)), ("orb_sched", (7, 2, 0, 8, 0)), ("orb_sched", (8, 1, 4, 8, 0)), ("orb_sched", (9, 1, 5, 8, 0)),
+               ("orb_sched", (10, 1, 5, 8, 0)), ("orb_sched", (10, 3, 5, 8, 0)), ("orb_sched", (9, 3, 5, 8, 0)), ("orb_sched", (2, 4, 0, 1, 0)),
+               ("orb_sched", (1, 4, 0, 1, 0)), ("orb_sched", (64, 4, 4, 8, 1))) == \
+        ["chains", "one_chain", "staggered", "one_chain", "staggered", "staggered", "chains", "chains", "one_chain", "one_chain"]
+    assert ask(("orb_sched_n", (8, 2, 0, 8, 0)), ("orb_sched_n", (10, 3, 5, 8, 0)), ("orb_sched_n", (9, 3, 5, 8, 0)), ("orb_sched_n", (2, 4, 0, 1, 0)),
+               ("orb_sched_n", (7, 2, 0, 8, 0))) == ["2", "5", "3", "2", "1"]
+
+
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def frame_lds(cap, ncell1):
+    """LDS of a frame: keypoints, descriptors, right points, taken flags (each padded to 16 bytes), cell starts, 64 bytes of slack."""
+    up = lambda v: (v + 15) & ~15
+    return up(cap * 24) + cap * 32 + up(cap * 4) + up(cap) + ncell1 * 4 + 64
+
+
+def test_track_thresholds_from_both_sides(driver):
+    ask = lambda *q: [int(a) for a in forms.ask(driver, list(q))]
+    # workgroups per frame: ceil(1024 / batch), at most one per chunk, at least one; SNK_TRACK_FRAME_WGS
+    assert ask(("track_wgs", (10, 1, 0)), ("track_wgs", (10, 1024, 0)), ("track_wgs", (10, 1025, 0)), ("track_wgs", (10, 512, 0)), ("track_wgs", (10, 511, 0)),
+               ("track_wgs", (10, 103, 0)), ("track_wgs", (1, 1, 0)), ("track_wgs", (10, 1024, 3)), ("track_wgs", (2, 1024, 3)), ("track_wgs", (10, 0, 0))) == \
+        [10, 1, 1, 2, 3, 10, 1, 3, 2, 10]
+    # the claims behind the frame: the last capacity at which frame + claims fit 144 KB, and the next
+    M = 144 * 1024
+    cap = max(c for c in range(1, 4000) if ((frame_lds(c, 2401) + 15) & ~15) + 4 * c <= M)
+    f0, f1 = frame_lds(cap, 2401), frame_lds(cap + 1, 2401)
+    assert ask(("track_lds", (cap, 2401)), ("track_lds", (cap + 1, 2401)), ("track_lds", (1000, 2401))) == [f0, f1, 24000 + 32000 + 4000 + 1008 + 9604 + 64]
+    assert ask(("track_claim", (1, f0, cap, 0)), ("track_claim", (1, f1, cap + 1, 0)), ("track_claim", (2, f0, cap, 0)), ("track_claim", (1, f0, cap, 1)),
+               ("track_claim", (1, M - 4 * 2116, 2116, 0)), ("track_claim", (1, M - 4 * 2116 + 1, 2116, 0)), ("track_claim", (1, 100, 10, 0))) == \
+        [(f0 + 15) & ~15, -1, -1, -1, M - 4 * 2116, -1, 112]   # (4 * 2116 is a multiple of 16: the claims end on the last byte)
+    # points per wavefront: a point per 8192 of the call, 1 .. 64; SNK_TRACK_PPW
+    assert ask(("track_ppw", (8191, 0)), ("track_ppw", (8192, 0)), ("track_ppw", (16383, 0)), ("track_ppw", (16384, 0)), ("track_ppw", (0, 0)),
+               ("track_ppw", (64 * 8192 - 1, 0)), ("track_ppw", (64 * 8192, 0)), ("track_ppw", (1 << 40, 0)), ("track_ppw", (100, 64)), ("track_ppw", (1 << 40, 1)),
+               ("track_ppw", (8192 * 5, 65))) == [1, 1, 1, 2, 1, 63, 64, 64, 64, 1, 5]
+    # a whole launch: ppw, wgs, claim_off, lds -- the frame form resolves in the kernel with one workgroup per frame
+    plan = lambda *a: [int(x) for x in forms.ask(driver, [("track_plan", a)])[0].split(",")]
+    fl = frame_lds(1000, 2401)
+    assert plan(10000, 1024, 1000, 2401, 0, 0, 0, 0) == [64, 1, (fl + 15) & ~15, ((fl + 15) & ~15) + 4000]
+    assert plan(10000, 512, 1000, 2401, 0, 0, 0, 0) == [64, 2, -1, fl]
+    assert plan(10000, 1024, 1000, 2401, 0, 0, 1, 0) == [64, 1, -1, fl]        # SNK_TRACK_NO_FUSED_RESOLVE
+    assert plan(10000, 1024, 1000, 2401, 0, 4, 0, 0) == [64, 4, -1, fl]        # SNK_TRACK_FRAME_WGS
+    assert plan(10000, 1024, 1000, 2401, 1, 0, 0, 0) == [64, 0, -1, 0]         # SNK_TRACK_NO_FRAME_LDS: coarse_batch_kernel / fine_batch_kernel
+    assert plan(100, 8, 1000, 2401, 0, 0, 0, 0) == [1, 0, -1, 0]
+
+
+def test_orb_and_track_switch_lists_agree():
+    """OrbSwitches (dispatch.hpp), its reader (orb.hip), the driver's parser, tests/forms.py and the README name the same switches; orb.hip
+    reads the environment only there and for SNK_DEBUG, track.hip only in track_switches() (and SNK_GRID_NETWORK of the feature grid)."""
+    csrc = forms.ROOT / "snake_slam_amd" / "csrc"
+    header = (csrc / "dispatch.hpp").read_text()
+    struct = re.search(r"struct OrbSwitches\s*\{(.*?)\n\};", header, re.S).group(1)
+    fields = re.findall(r"^\s+(?:bool|int|size_t) \w+\s*=[^;]*;\s*// (\w+)", struct, re.M)
+    assert fields == forms.ORB_SWITCHES
+    orb = (csrc / "orb.hip").read_text()
+    reader = re.search(r"static const OrbSwitches& orb_switches\(\)\n\{(.*?)\n\}\n", orb, re.S).group(1)
+    assert sorted(set(re.findall(r'"SNK_ORB_(\w+)"', reader))) == sorted(forms.ORB_SWITCHES)
+    assert re.findall(r'getenv\((\w+|"\w+")\)', orb.replace(reader, "")) == ['"SNK_DEBUG"']
+    driver = (forms.ROOT / "tests" / "cpp" / "dispatch_driver.cpp").read_text()
+    assert sorted(re.findall(r'is\("(\w+)"\)', driver)) == sorted(forms.ORB_SWITCHES)
+    readme = (forms.ROOT / "README.md").read_text()
+    assert all(f"SNK_ORB_{n}" in readme for n in forms.ORB_SWITCHES) and all(f"SNK_TRACK_{n}" in readme for n in forms.TRACK_SWITCHES)
+    struct = re.search(r"struct TrackSwitches\s*\{(.*?)\n\};", header, re.S).group(1)
+    assert re.findall(r"// SNK_TRACK_(\w+)", struct) == forms.TRACK_SWITCHES
+    track = (csrc / "track.hip").read_text()
+    reader = re.search(r"const TrackSwitches& track_switches\(\)\n\{(.*?)\n\}\n", track, re.S).group(1)
+    assert sorted(re.findall(r'"SNK_TRACK_(\w+)"', reader)) == sorted(forms.TRACK_SWITCHES)
+    assert re.findall(r'getenv\((\w+|"\w+")\)', track.replace(reader, "")) == ['"SNK_GRID_NETWORK"']
