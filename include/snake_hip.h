@@ -50,6 +50,8 @@ typedef enum snk_status
 SNK_API const char* snk_last_error(void);  /* thread-local text of the last failure */
 SNK_API const char* snk_version(void);
 SNK_API int snk_device_count(void);        /* number of visible HIP devices (0 = none) */
+SNK_API int snk_debug_live_buffers(void);  /* device and pinned scratch buffers all handles of this process hold right now (leak checks) */
+SNK_API int snk_debug_buffer_allocations(void); /* such buffers allocated so far, never decreasing: it moves when a call grew a buffer */
 
 /* Run-time switches for choices this library had to DEFINE because the arithmetic lives in the absent saiga submodule
  * (reference .gitmodules:1-3): a maintainer who can read saiga selects the matching rule without editing a kernel.

@@ -39,6 +39,8 @@ SIGNATURES = {
     "snk_last_error": (C.c_char_p, []),
     "snk_version": (C.c_char_p, []),
     "snk_device_count": (i32, []),
+    "snk_debug_live_buffers": (i32, []),
+    "snk_debug_buffer_allocations": (i32, []),
     "snk_matcher_create": (i32, [i32, vp, C.POINTER(vp)]),
     "snk_matcher_destroy": (i32, [vp]),
     "snk_matcher_sync": (i32, [vp]),

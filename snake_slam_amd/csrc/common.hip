@@ -23,6 +23,14 @@ void set_error(const char* fmt, ...)
     va_end(ap);
 }
 
+static std::atomic<int> g_live_buffers{0}, g_buffer_allocations{0};
+
+void count_buffer(int delta)
+{
+    g_live_buffers.fetch_add(delta, std::memory_order_relaxed);
+    if (delta > 0) g_buffer_allocations.fetch_add(delta, std::memory_order_relaxed);
+}
+
 int set_max_lds_once(const void* kernel, int bytes)
 {
     // The attribute belongs to the kernel's function object ON THE CURRENT DEVICE (every entry point has called hipSetDevice
@@ -171,6 +179,14 @@ int snk_get_definition(const char* key, int* value)
     }
     *value = snk::g_defs[i].load();
     return SNK_OK;
+}
+int snk_debug_live_buffers(void)
+{
+    return snk::g_live_buffers.load(std::memory_order_relaxed);
+}
+int snk_debug_buffer_allocations(void)
+{
+    return snk::g_buffer_allocations.load(std::memory_order_relaxed);
 }
 int snk_device_count(void)
 {

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <string>
 
+#include "dispatch.hpp"
 #include "snake_hip.h"
 
 namespace snk
@@ -47,6 +48,11 @@ void set_error(const char* fmt, ...);
         }                                                                                           \
     } while (0)
 
+// Every allocation a DevBuf / HostBuf holds is counted (snk_debug_live_buffers): a handle type that forgets to release one of its
+// buffers shows as a count that does not come back, however small the buffer (the runtime's free-memory figure moves in large steps).
+// Every +1 also counts as an allocation made (snk_debug_buffer_allocations, never decreasing): a call that grew a buffer shows there.
+void count_buffer(int delta);
+
 // Grow-only device buffer.
 struct DevBuf
 {
@@ -55,11 +61,10 @@ struct DevBuf
     int reserve(size_t n)
     {
         if (n <= bytes) return SNK_OK;
-        if (p) (void)hipFree(p);
-        p     = nullptr;
-        bytes = 0;
-        size_t want = n + n / 4 + 256;
+        release();
+        size_t want = scratch_capacity(n);
         SNK_HIP_CHECK(hipMalloc(&p, want));
+        count_buffer(+1);
         bytes = want;
         // SNK_DEBUG_POISON=1: fill fresh scratch with a pattern so that a kernel relying on
         // zero-initialised memory fails reproducibly instead of depending on the allocator's history
@@ -75,7 +80,11 @@ struct DevBuf
     }
     void release()
     {
-        if (p) (void)hipFree(p);
+        if (p)
+        {
+            (void)hipFree(p);
+            count_buffer(-1);
+        }
         p     = nullptr;
         bytes = 0;
     }
@@ -95,17 +104,23 @@ struct HostBuf
     int reserve(size_t n)
     {
         if (n <= bytes) return SNK_OK;
-        if (p) (void)hipHostFree(p);
-        p     = nullptr;
-        bytes = 0;
-        size_t want = n + n / 4 + 256;
+        release();
+        size_t want = scratch_capacity(n);
         SNK_HIP_CHECK(hipHostMalloc(&p, want, hipHostMallocDefault));
+        count_buffer(+1);
         bytes = want;
+        // SNK_DEBUG_POISON=1, as DevBuf::reserve: a result block read beyond what the device wrote is 0xCD, not the allocator's zeros
+        static const bool poison = getenv("SNK_DEBUG_POISON") != nullptr;
+        if (poison) memset(p, 0xCD, want);
         return SNK_OK;
     }
     void release()
     {
-        if (p) (void)hipHostFree(p);
+        if (p)
+        {
+            (void)hipHostFree(p);
+            count_buffer(-1);
+        }
         p     = nullptr;
         bytes = 0;
     }

@@ -15,6 +15,15 @@
 
 namespace snk
 {
+// ---- the matcher handle's scratch as snk_matcher_create sizes it (matcher.hip): a call that needs more grows a buffer once -----------
+constexpr size_t MATCHER_SCRATCH_BYTES = 4u << 20;    // q, t, out, aux, aux2, view: any per-frame call up to ~40 000 features / map points
+constexpr size_t MATCHER_H_IN_BYTES    = 1u << 20;    // pinned input staging: 10 000 local-map points of the fine matcher
+constexpr size_t MATCHER_H_RES_BYTES   = 256u << 10;  // pinned result staging
+// What DevBuf::reserve(n) / HostBuf::reserve(n) allocate (common.hpp): a quarter more than asked for, so that a slowly growing call does
+// not reallocate every time.  A buffer sized at create holds scratch_capacity(MATCHER_*_BYTES); only a call that asks for more than that
+// frees and reallocates it.
+constexpr size_t scratch_capacity(size_t n) { return n + n / 4 + 256; }
+
 // ---- brute-force kNN-2 (launch_knn2) ----------------------------------------------------------------------------------------------
 constexpr int BF_MFMA_MIN      = 24;     // matrix-core kernel once a query block (32) and a train tile (32) are mostly full
 constexpr int BF_WIDE_MIN_WORK = 16384;  // batch * nq_cap from which a wavefront takes four queries (enough work for 256 CUs)

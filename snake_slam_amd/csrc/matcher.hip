@@ -915,15 +915,14 @@ int snk_matcher_create(int device, void* stream, snk_matcher** out)
     *out           = nullptr;
     snk_matcher* m = new snk_matcher();
     int rc         = m->init(device, stream);
-    // scratch for the per-frame (host pointer) calls is sized here -- 4 MB per buffer holds any call up to ~40 000
-    // features / map points -- so that the seams allocate nothing while other seams' threads are running
+    // scratch for the per-frame (host pointer) calls is sized here (dispatch.hpp: 4 MB per buffer holds any call up to ~40 000
+    // features / map points) so that the seams allocate nothing while other seams' threads are running
     // (hipMalloc / hipFree synchronise the whole device); larger calls still grow the buffers once
-    constexpr size_t SCRATCH = 4u << 20;
     for (snk::DevBuf* b : {&m->q, &m->t, &m->out, &m->aux, &m->aux2, &m->view})
-        if (rc == SNK_OK) rc = b->reserve(SCRATCH);
+        if (rc == SNK_OK) rc = b->reserve(MATCHER_SCRATCH_BYTES);
     if (rc == SNK_OK) rc = m->cnt.reserve(256);
-    if (rc == SNK_OK) rc = m->h_in.reserve(1u << 20);  // 10 000 local-map points of the fine matcher
-    if (rc == SNK_OK) rc = m->h_res.reserve(256u << 10);
+    if (rc == SNK_OK) rc = m->h_in.reserve(MATCHER_H_IN_BYTES);
+    if (rc == SNK_OK) rc = m->h_res.reserve(MATCHER_H_RES_BYTES);
     if (rc != SNK_OK)
     {
         snk_matcher_destroy(m);

@@ -27,6 +27,7 @@
 //   track_form:pts_cap:batch:cap:ncell1:no_frame_lds:ppw_env     track_plan:pts_cap:batch:cap:ncell1:no_frame_lds:frame_wgs:no_fused_resolve:ppw_env  "ppw,wgs,claim_off,lds"
 //   track_wgs:chunks:batch:forced                 track_claim:wgs:frame_lds:cap:off
 //   track_ppw:total_points:ppw_env                track_lds:cap:ncell1
+//   capacity:bytes                                what a scratch buffer asked for that many bytes holds
 //   const:NAME
 // Exit status 2 on an argument it cannot read.
 #include <cstdio>
@@ -314,6 +315,7 @@ int main(int argc, char** argv)
         else if (e == "track_claim" && n == 4) std::printf("%d\n", snk::track_fused_claim_offset((int)v[0], (size_t)v[1], (int)v[2], v[3] != 0));
         else if (e == "track_ppw" && n == 2) std::printf("%d\n", snk::track_points_per_wave(v[0], (int)v[1]));
         else if (e == "track_lds" && n == 2) std::printf("%zu\n", snk::track_frame_lds((int)v[0], (int)v[1]));
+        else if (e == "capacity" && n == 1) std::printf("%zu\n", snk::scratch_capacity((size_t)v[0]));
         else if (e == "const" && f.size() == 2)
         {
             const std::string& c = f[1];
@@ -356,6 +358,9 @@ int main(int argc, char** argv)
             else if (c == "ORB_DIST_LARGE_LDS_MAX") val = (int)snk::orb::DIST_LARGE_LDS_MAX;
             else if (c == "TRACK_FRAME_LDS_MAX") val = snk::TRACK_FRAME_LDS_MAX;
             else if (c == "TRACK_PPW_POINTS") val = snk::TRACK_PPW_POINTS;
+            else if (c == "MATCHER_SCRATCH_BYTES") val = (int)snk::MATCHER_SCRATCH_BYTES;
+            else if (c == "MATCHER_H_IN_BYTES") val = (int)snk::MATCHER_H_IN_BYTES;
+            else if (c == "MATCHER_H_RES_BYTES") val = (int)snk::MATCHER_H_RES_BYTES;
             else
             {
                 std::fprintf(stderr, "dispatch_driver: no constant %s\n", c.c_str());

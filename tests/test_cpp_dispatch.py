@@ -208,6 +208,26 @@ def test_orb_and_track_constants(driver):
     assert 2048 * 19 + 16 + 4 * 2048 + 16 < 8192 * 19 + 16 <= 160 * 1024
 
 
+MATCHER_CONSTANTS = {"MATCHER_SCRATCH_BYTES": 4 << 20, "MATCHER_H_IN_BYTES": 1 << 20, "MATCHER_H_RES_BYTES": 256 << 10}
+
+
+def test_matcher_scratch_constants(driver):
+    """What snk_matcher_create pre-sizes; tests/backend_cases.py computes its growth cases from the same header."""
+    import backend_cases
+
+    names = list(MATCHER_CONSTANTS)
+    assert dict(zip(names, map(int, forms.ask(driver, [("const", (n,)) for n in names])))) == MATCHER_CONSTANTS
+    got = backend_cases.matcher_constants()
+    assert {n: got[n] for n in names} == MATCHER_CONSTANTS
+    # a buffer holds a quarter more than it was asked for, plus 256 bytes (DevBuf / HostBuf::reserve use the same function)
+    assert [int(a) for a in forms.ask(driver, [("capacity", (n,)) for n in (0, 1000, 4 << 20)])] == [256, 1506, (5 << 20) + 256]
+    assert got["dev_capacity"] == (5 << 20) + 256 and got["h_in_capacity"] == 1310976 and got["h_res_capacity"] == 327936
+    common = (forms.ROOT / "snake_slam_amd" / "csrc" / "common.hpp").read_text()
+    assert common.count("size_t want = scratch_capacity(n);") == 2
+    src = (forms.ROOT / "snake_slam_amd" / "csrc" / "matcher.hip").read_text()
+    assert all(re.search(r"reserve\(%s\)" % n, src) for n in names), "snk_matcher_create sizes its buffers by the header's constants"
+
+
 def test_orb_thresholds_from_both_sides(driver):
     """Both neighbours of every threshold of orb_plan's parts."""
     ask = lambda *q: forms.ask(driver, list(q))
