@@ -865,6 +865,125 @@ SNK_API int snk_covis_vote_batch_dev(snk_matcher* m, const snk_covis_map* map_de
                                      snk_covis_conn* conn_dev, snk_covis_result* out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Local map of fine tracking (snk-lmap v1)
+ * ------------------------------------------------------------------------------------------ */
+
+#define SNK_LMAP_MAX_LOCAL_KF 256  /* kf_cap at most: local keyframes per set */
+#define SNK_LMAP_MAX_PTS 16384     /* pts_cap at most (the reference reserves 10 000, LocalMap.h:88): 32 768 four-byte slots of LDS */
+#define SNK_LMAP_MAX_NEIGHBOURS 16 /* [DEFINED] n_neighbours at most (the reference asks for 5) */
+
+#define SNK_LMAP_OK 0
+#define SNK_LMAP_EMPTY 1        /* the vote touched nothing (TrackingFine.cpp:254): no local keyframes; snk_lmap_gather adds the own points only */
+#define SNK_LMAP_TRUNCATED 2    /* the vote's list was cut by its cap (n_found > n_conn): the remaining and the marked keyframes are unknown */
+#define SNK_LMAP_KF_OVERFLOW 3  /* more than kf_cap local keyframes */
+#define SNK_LMAP_PTS_OVERFLOW 4 /* more than pts_cap distinct points */
+#define SNK_LMAP_BAD_INDEX 5    /* device forms: an id, a start or a count outside its range */
+
+typedef struct snk_lmap_params
+{
+    int32_t n_direct;        /* TrackingFine.cpp:223: 15 */
+    int32_t n_direct_prob;   /* :224: 5 */
+    int32_t n_indirect_prob; /* :225: 5 */
+    int32_t n_neighbours;    /* :301: 5.  0 .. SNK_LMAP_MAX_NEIGHBOURS */
+    int32_t kf_cap;          /* entries of local_kf per set, 1 .. SNK_LMAP_MAX_LOCAL_KF */
+    uint64_t seed;           /* of the draws; a set's draws depend on (seed, frame_id, position) only */
+} snk_lmap_params;
+
+/* One set of snk_lmap_select.  status != SNK_LMAP_OK: n_local = n_direct = n_indirect = 0, reference_kf = -1. */
+typedef struct snk_lmap_select_result
+{
+    int32_t n_local;      /* local_keyframes.size() */
+    int32_t n_direct;     /* min(params.n_direct, length of the vote's list) */
+    int32_t n_indirect;   /* indirect_neighbor.size(): the rejected of the first walk + the neighbours appended */
+    int32_t reference_kf; /* :268 */
+    int32_t status;
+} snk_lmap_select_result;
+
+/* One set of snk_lmap_gather.  status other than SNK_LMAP_OK / SNK_LMAP_EMPTY: all counts 0. */
+typedef struct snk_lmap_gather_result
+{
+    int32_t n_pts;        /* lm.points.size(), the return value of UpdateLocalPoints */
+    int32_t n_searchable; /* records with valid = 1 */
+    int32_t n_own_new;    /* own points that no local keyframe placed */
+    int32_t status;       /* SNK_LMAP_OK also where stage 1 said SNK_LMAP_EMPTY */
+} snk_lmap_gather_result;
+
+/* The keyframe side of the map and the per-point words snk_lmap_gather reads.  n_feat: length of feat_point (host forms: must equal
+ * feat_start[n_kf]). */
+typedef struct snk_lmap_map
+{
+    int32_t n_kf, n_points, n_feat;
+    const int32_t* feat_start;   /* [n_kf + 1], feat_start[0] = 0: the layout of snk_covis_update */
+    const int32_t* feat_point;   /* [n_feat] GetMapPointMatches() as point ids, -1: none */
+    const uint8_t* pt_flags;     /* [n_points] bit SNK_COVIS_PT_BAD */
+    const int32_t* pt_last_seen; /* [n_points] MapPoint::lastFrameSeen */
+} snk_lmap_map;
+
+/* What FineTrackingPoint's constructor copies (LocalMap.h:46-53), a row per point id; e.g. what snk_mappoint_refresh leaves. */
+typedef struct snk_lmap_points
+{
+    const double* pos;        /* [n_points][3] */
+    const double* normal;     /* [n_points][3] */
+    const uint64_t* desc;     /* [n_points][4] */
+    const float* ref_depth;   /* [n_points] */
+    const int32_t* ref_level; /* [n_points] */
+} snk_lmap_points;
+
+/* The local keyframes of Tracking::UpdateLocalKeyFrames2 behind the vote — Snake/Tracking/TrackingFine.cpp:272-323 — for n_sets
+ * frames.  conn [n_sets][vote_cap] and vote [n_sets] are what snk_covis_vote left (ascending by (count, id), read from the back);
+ * conn_start [n_kf + 1] / conn_list [conn_start[n_kf]] are every keyframe's connections, ascending by (weight, kf) as snk_covis_update
+ * emits them and KeyframeGraph.cpp:124 keeps them.  Vote SNK_COVIS_UNCHANGED: SNK_LMAP_EMPTY (:254); n_found > n_conn:
+ * SNK_LMAP_TRUNCATED.  Direct: the last min(n_direct, n_found) entries from the back (:272-276), reference_kf the last (:268).  The
+ * remaining R entries from the back (:282-295): entry j takes draw j against n_direct_prob / R; accepted ones join the local list,
+ * rejected ones `indirect`.  For every local keyframe so far, in order, the last min(n_neighbours, size) connections in ASCENDING
+ * order (KeyframeGraph.cpp:62 is a view): a neighbour that is not bad (:304) and not marked (:306) joins `indirect` and is marked;
+ * marked are all keyframes of the vote's list (:246-250) and the neighbours appended.  Entry j of `indirect` takes draw R + j against
+ * n_indirect_prob / indirect.size() (:316-323).  Bad keyframes of the vote's list are kept.  Draw c of a set [DEFINED]:
+ * h = mix(mix(key) ^ c), key = mix(mix(seed lo ^ 0x9e3779b9) ^ seed hi) ^ frame_id, accepted iff (u64)h * n < (u64)k << 32 (Saiga::Random
+ * is absent).  More than kf_cap local keyframes: SNK_LMAP_KF_OVERFLOW.  local_kf [n_sets][kf_cap] (-1 past n_local), out [n_sets].
+ * Everything is checked before anything is launched: a NULL array with a non-zero count, a start array that does not begin at 0 or
+ * decreases, an id or a vote count outside its range, n_kf > SNK_COVIS_MAX_KF, kf_cap outside [1, SNK_LMAP_MAX_LOCAL_KF], n_neighbours
+ * above SNK_LMAP_MAX_NEIGHBOURS, a parameter below 0: SNK_ERR_INVALID_ARG.  n_sets == 0 is valid. */
+SNK_API int snk_lmap_select(snk_matcher* m, int n_sets, const snk_covis_conn* conn, int vote_cap, const snk_covis_result* vote, int n_kf,
+                            const uint8_t* kf_bad, const int32_t* conn_start, const snk_covis_conn* conn_list, const int32_t* frame_id,
+                            const snk_lmap_params* params, int32_t* local_kf, snk_lmap_select_result* out);
+
+/* The same (TrackingFine.cpp:272-323) with every array on the device; n_list is the length of conn_list_dev.  Asynchronous on the
+ * handle's stream.  The kernel checks what the host cannot see: a vote record with counts outside [0, vote_cap] or a status it does not
+ * know, a keyframe id outside [0, n_kf), a conn_start entry that decreases or lies outside [0, n_list] give that set
+ * SNK_LMAP_BAD_INDEX, and nothing outside the ranges is read. */
+SNK_API int snk_lmap_select_batch_dev(snk_matcher* m, int n_sets, const snk_covis_conn* conn_dev, int vote_cap,
+                                      const snk_covis_result* vote_dev, int n_kf, const uint8_t* kf_bad_dev, const int32_t* conn_start_dev,
+                                      int n_list, const snk_covis_conn* conn_list_dev, const int32_t* frame_id_dev,
+                                      const snk_lmap_params* params, int32_t* local_kf_dev, snk_lmap_select_result* out_dev);
+
+/* Tracking::UpdateLocalPoints with LocalMap::addPoint — Snake/Tracking/TrackingFine.cpp:328-356, Snake/Map/LocalMap.h:139-154 — for
+ * n_sets frames.  local_kf [n_sets][kf_cap] and sel [n_sets] are what snk_lmap_select left.  For every local keyframe in list order and
+ * every feature in feature order: a point that is -1, bad or last seen in this frame (pt_last_seen[p] == frame_id[s], :338-339) is
+ * skipped, otherwise addPoint: a point already present keeps its first place (also twice inside one keyframe).  Then the frame's own
+ * points set_point[set_start[s] .. set_start[s + 1]) (the vote's arrays) in order, -1 and bad skipped: one already present has valid
+ * cleared in its record, a new one is appended with valid = 0 (:344-354).  More than pts_cap distinct points: SNK_LMAP_PTS_OVERFLOW.  A
+ * stage-1 status other than OK / EMPTY is passed through; EMPTY adds the own points only.  Outputs: lm_pts [n_sets][pts_cap] (pad bytes
+ * 0), lm_point [n_sets][pts_cap] point ids (-1 past n_pts; lm.points[i].mp), n_pts [n_sets] -- lm_pts, n_pts plug into
+ * snk_match_project_fine_batch_dev / _ro_dev --, out [n_sets]; records past n_pts are not written.  IncreaseVisible on the own points
+ * (:349) and clearing the frame's bad points (:237) stay with the caller.  Checks and errors as snk_lmap_select, pts_cap in
+ * [1, SNK_LMAP_MAX_PTS]. */
+SNK_API int snk_lmap_gather(snk_matcher* m, int n_sets, const snk_lmap_map* map, const snk_lmap_points* points, const int32_t* frame_id,
+                            const int32_t* local_kf, int kf_cap, const snk_lmap_select_result* sel, const int32_t* set_start,
+                            const int32_t* set_point, int pts_cap, snk_lm_fine* lm_pts, int32_t* lm_point, int32_t* n_pts,
+                            snk_lmap_gather_result* out);
+
+/* The same (TrackingFine.cpp:328-356, LocalMap.h:139-154) on the device; n_set_points is the length of set_point_dev.  Asynchronous.
+ * The kernel checks: a stage-1 count outside [0, kf_cap], a local keyframe outside [0, n_kf), a feature range outside [0, n_feat] or
+ * decreasing, a set range outside [0, n_set_points] or decreasing, a point id >= n_points or < -1, more than 2^30 candidates give that
+ * set SNK_LMAP_BAD_INDEX. */
+SNK_API int snk_lmap_gather_batch_dev(snk_matcher* m, int n_sets, const snk_lmap_map* map_dev, const snk_lmap_points* points_dev,
+                                      const int32_t* frame_id_dev, const int32_t* local_kf_dev, int kf_cap,
+                                      const snk_lmap_select_result* sel_dev, const int32_t* set_start_dev, int n_set_points,
+                                      const int32_t* set_point_dev, int pts_cap, snk_lm_fine* lm_pts_dev, int32_t* lm_point_dev,
+                                      int32_t* n_pts_dev, snk_lmap_gather_result* out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Pose refinement (the step after every projection matcher)
  * ------------------------------------------------------------------------------------------ */
 

@@ -82,6 +82,10 @@ SIGNATURES = {
     "snk_covis_update_batch_dev": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
     "snk_covis_vote": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
     "snk_covis_vote_batch_dev": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "snk_lmap_select": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "snk_lmap_select_batch_dev": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "snk_lmap_gather": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "snk_lmap_gather_batch_dev": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
     "snk_p3p_ransac": (i32, [vp, vp, vp, i32]),
     "snk_p3p_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "snk_p3p_ransac_frame_batch_dev": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),

@@ -940,6 +940,140 @@ class CovisibilityGraph
     snk_covis_params par_;
 };
 
+// The local map of fine tracking, semantics "snk-lmap v1": Select is the rest of Tracking::UpdateLocalKeyFrames2 behind the vote
+// (reference Snake/Tracking/TrackingFine.cpp:272-323), Gather is Tracking::UpdateLocalPoints with LocalMap::addPoint (:328-356,
+// Snake/Map/LocalMap.h:139-154), both for a list of frames.  The caller passes the vote's lists (CovisibilityGraph::VoteLocalKeyframes),
+// every keyframe's connections and the map as tables, and sets lm.points from Frame::points / ::ids:
+// mvpMapPoints[idx] = the MapPoint of ids[i].  The device forms run on arrays that are already in HBM and feed
+// snk_match_project_fine_batch_dev directly.
+class LocalMapBuilder
+{
+   public:
+    struct Graph  // every keyframe's connections, ascending by (weight, kf): KeyframeGraph.cpp:124
+    {
+        std::vector<uint8_t> kf_bad;
+        std::vector<int32_t> conn_start{0};
+        std::vector<snk_covis_conn> conn_list;
+        int AddKeyframe(bool bad, const std::vector<snk_covis_conn>& connections)
+        {
+            conn_list.insert(conn_list.end(), connections.begin(), connections.end());
+            conn_start.push_back((int32_t)conn_list.size());
+            kf_bad.push_back(bad ? 1 : 0);
+            return (int)kf_bad.size() - 1;
+        }
+    };
+    struct Points  // the keyframe side of the map and what FineTrackingPoint copies (LocalMap.h:46-53), a row per point id
+    {
+        std::vector<int32_t> feat_start{0}, feat_point;  // GetMapPointMatches() per keyframe slot as point ids, -1: none
+        std::vector<uint8_t> pt_flags;                   // SNK_COVIS_PT_BAD
+        std::vector<int32_t> pt_last_seen;               // MapPoint::lastFrameSeen
+        std::vector<double> pos, normal;                 // [n][3]
+        std::vector<uint64_t> desc;                      // [n][4]
+        std::vector<float> ref_depth;
+        std::vector<int32_t> ref_level;
+        snk_lmap_map map() const
+        {
+            return snk_lmap_map{(int32_t)feat_start.size() - 1, (int32_t)pt_flags.size(), (int32_t)feat_point.size(), feat_start.data(), feat_point.data(),
+                                pt_flags.data(), pt_last_seen.data()};
+        }
+        snk_lmap_points table() const { return snk_lmap_points{pos.data(), normal.data(), desc.data(), ref_depth.data(), ref_level.data()}; }
+    };
+    struct Selection  // [n_sets][kf_cap] local keyframes (-1 past n_local) and a record per set
+    {
+        std::vector<int32_t> local_kf;
+        std::vector<snk_lmap_select_result> result;
+    };
+    struct Frame  // one frame's local map: points[i] belongs to the map point ids[i]
+    {
+        std::vector<snk_lm_fine> points;
+        std::vector<int32_t> ids;
+        snk_lmap_gather_result result{};
+    };
+
+    explicit LocalMapBuilder(const snk_lmap_params& params, int device = 0) : par_(params)
+    {
+        check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create");
+    }
+    ~LocalMapBuilder() { snk_matcher_destroy(h_); }
+    LocalMapBuilder(const LocalMapBuilder&)            = delete;
+    LocalMapBuilder& operator=(const LocalMapBuilder&) = delete;
+
+    // votes[s] / frame_id[s]: the list of frame s as VoteLocalKeyframes returned it
+    Selection Select(const std::vector<CovisibilityGraph::List>& votes, const Graph& graph, const std::vector<int32_t>& frame_id)
+    {
+        if (votes.size() != frame_id.size()) throw std::invalid_argument("LocalMapBuilder: a frame id per vote");
+        size_t cap = 1;
+        for (const auto& v : votes) cap = std::max(cap, v.connections.size());
+        std::vector<snk_covis_conn> conn(votes.size() * cap, snk_covis_conn{-1, -1});
+        std::vector<snk_covis_result> res(votes.size());
+        for (size_t s = 0; s < votes.size(); ++s)
+        {
+            std::copy(votes[s].connections.begin(), votes[s].connections.end(), conn.begin() + (std::ptrdiff_t)(s * cap));
+            res[s] = snk_covis_result{votes[s].n_found, (int32_t)votes[s].connections.size(), votes[s].Best(), votes[s].status};
+        }
+        Selection out;
+        out.local_kf.assign(votes.size() * (size_t)par_.kf_cap, -1);
+        out.result.resize(votes.size());
+        check(snk_lmap_select(h_, (int)votes.size(), conn.data(), (int)cap, res.data(), (int)graph.kf_bad.size(), graph.kf_bad.data(), graph.conn_start.data(),
+                              graph.conn_list.data(), frame_id.data(), &par_, out.local_kf.data(), out.result.data()),
+              "snk_lmap_select");
+        return out;
+    }
+
+    // own[s]: frame s's mvpMapPoints as point ids, -1: none
+    std::vector<Frame> Gather(const Points& pts, const Selection& sel, const std::vector<int32_t>& frame_id, const std::vector<std::vector<int32_t>>& own,
+                              int pts_cap)
+    {
+        const size_t n = sel.result.size();
+        if (own.size() != n || frame_id.size() != n) throw std::invalid_argument("LocalMapBuilder: a frame id and a point list per set");
+        std::vector<int32_t> start{0}, point;
+        for (const auto& f : own)
+        {
+            point.insert(point.end(), f.begin(), f.end());
+            start.push_back((int32_t)point.size());
+        }
+        const snk_lmap_map m      = pts.map();
+        const snk_lmap_points tab = pts.table();
+        std::vector<snk_lm_fine> lm(n * (size_t)std::max(pts_cap, 1));
+        std::vector<int32_t> ids(n * (size_t)std::max(pts_cap, 1), -1), n_pts(n);
+        std::vector<snk_lmap_gather_result> res(n);
+        check(snk_lmap_gather(h_, (int)n, &m, &tab, frame_id.data(), sel.local_kf.data(), par_.kf_cap, sel.result.data(), start.data(), point.data(), pts_cap,
+                              lm.data(), ids.data(), n_pts.data(), res.data()),
+              "snk_lmap_gather");
+        std::vector<Frame> out(n);
+        for (size_t s = 0; s < n; ++s)
+        {
+            out[s].points.assign(lm.begin() + (std::ptrdiff_t)(s * (size_t)pts_cap), lm.begin() + (std::ptrdiff_t)(s * (size_t)pts_cap + (size_t)n_pts[s]));
+            out[s].ids.assign(ids.begin() + (std::ptrdiff_t)(s * (size_t)pts_cap), ids.begin() + (std::ptrdiff_t)(s * (size_t)pts_cap + (size_t)n_pts[s]));
+            out[s].result = res[s];
+        }
+        return out;
+    }
+
+    // the device forms: every pointer is device memory, nothing is copied, the call returns before the kernel has run
+    void SelectDev(int n_sets, const snk_covis_conn* conn_dev, int vote_cap, const snk_covis_result* vote_dev, int n_kf, const uint8_t* kf_bad_dev,
+                   const int32_t* conn_start_dev, int n_list, const snk_covis_conn* conn_list_dev, const int32_t* frame_id_dev, int32_t* local_kf_dev,
+                   snk_lmap_select_result* out_dev)
+    {
+        check(snk_lmap_select_batch_dev(h_, n_sets, conn_dev, vote_cap, vote_dev, n_kf, kf_bad_dev, conn_start_dev, n_list, conn_list_dev, frame_id_dev, &par_,
+                                        local_kf_dev, out_dev),
+              "snk_lmap_select_batch_dev");
+    }
+    void GatherDev(int n_sets, const snk_lmap_map& map_dev, const snk_lmap_points& points_dev, const int32_t* frame_id_dev, const int32_t* local_kf_dev,
+                   const snk_lmap_select_result* sel_dev, const int32_t* set_start_dev, int n_set_points, const int32_t* set_point_dev, int pts_cap,
+                   snk_lm_fine* lm_pts_dev, int32_t* lm_point_dev, int32_t* n_pts_dev, snk_lmap_gather_result* out_dev)
+    {
+        check(snk_lmap_gather_batch_dev(h_, n_sets, &map_dev, &points_dev, frame_id_dev, local_kf_dev, par_.kf_cap, sel_dev, set_start_dev, n_set_points,
+                                        set_point_dev, pts_cap, lm_pts_dev, lm_point_dev, n_pts_dev, out_dev),
+              "snk_lmap_gather_batch_dev");
+    }
+    void Sync() { check(snk_matcher_sync(h_), "snk_matcher_sync"); }
+
+   private:
+    snk_matcher* h_ = nullptr;
+    snk_lmap_params par_;
+};
+
 // Saiga::P3PRansac as Tracking::TrackBruteForce uses it -- Snake/Tracking/TrackingCoarse.cpp:403-440, semantics "snk-p3p v1":
 //   RansacParameters params; params.maxIterations = 250; params.residualThreshold = chi1 * chi1;
 //   P3PRansac pnp2(params);  inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask);

@@ -1,4 +1,4 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, ba.hip,
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, localmap.hip, ba.hip,
 // orb.hip (the extractor's whole launch plan, over the geometry of orb_layout.hpp) and track.hip (the projection matchers) live.
 // Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every
 // shape of the GPU tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
@@ -180,6 +180,34 @@ constexpr int covis_sort_len(int n_kf, int cap)
 constexpr size_t covis_carve(int n_kf, int cap)
 {
     return (size_t)((n_kf + 3) & ~3) * 4 + (size_t)covis_sort_len(n_kf, cap) * 4 + (size_t)COVIS_THREADS * 4 + (size_t)COVIS_MISC * 4;
+}
+
+// ---- local map of fine tracking (localmap.hip: snk_lmap_select, snk_lmap_gather and their _batch_dev forms) --------------------------
+// One form each.  lmap_select_kernel: a workgroup per set; the marks are a bit per keyframe, the neighbour candidates (a slot per local
+// keyframe and neighbour rank) are sorted by kf << bits | slot.  lmap_gather_kernel: a workgroup per set; an open-addressing table of
+// four-byte slots (candidate order + 1, bit 31 = "also an own point") over the point ids.
+constexpr int LMAP_THREADS = 256;  // four wavefronts; a scan chunk is one candidate per lane
+constexpr int LMAP_MISC    = 32;   // u32 words of flags, counts and the per-wavefront partial sums (two banks)
+
+constexpr int lmap_pow2_at_least(int n, int least)
+{
+    int p = least;
+    while (p < n) p <<= 1;
+    return p;
+}
+// keys the neighbour sort holds: a slot per (local keyframe, neighbour rank), rounded up to a power of two
+constexpr int lmap_sort_len(int kf_cap, int n_neighbours) { return lmap_pow2_at_least(kf_cap * n_neighbours, 4); }
+// slots of the point table: load at most 0.5 at pts_cap, and room for the claims in flight when the count passes pts_cap (one per lane)
+constexpr int lmap_table_slots(int pts_cap) { return lmap_pow2_at_least(2 * pts_cap, 2 * LMAP_THREADS); }
+// LDS carve of lmap_select_kernel: the marks, the local list, the sort keys, the neighbour firsts by slot, the words above
+constexpr size_t lmap_select_carve(int n_kf, int kf_cap, int n_neighbours)
+{
+    return (size_t)((n_kf + 31) / 32 + 1) * 4 + (size_t)kf_cap * 4 + (size_t)lmap_sort_len(kf_cap, n_neighbours) * 8 + (size_t)LMAP_MISC * 4;
+}
+// LDS carve of lmap_gather_kernel: the table, the prefix sums of the feature ranges (kf_cap + 1), their starts (kf_cap), the words above
+constexpr size_t lmap_gather_carve(int kf_cap, int pts_cap)
+{
+    return (size_t)lmap_table_slots(pts_cap) * 4 + (size_t)(2 * kf_cap + 1) * 4 + (size_t)LMAP_MISC * 4;
 }
 
 // ---- bundle adjustment (ba.hip: ba_plan_pcg, enqueue_lm, snk_ba_solve_async, snk_ba_pcg_form; the hand-over asks ba_sets_will_run) --
