@@ -865,6 +865,146 @@ SNK_API int snk_covis_vote_batch_dev(snk_matcher* m, const snk_covis_map* map_de
                                      snk_covis_conn* conn_dev, snk_covis_result* out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Local BA windows (snk-scene v1)
+ * ------------------------------------------------------------------------------------------ */
+
+#define SNK_SCENE_MAX_WINDOW 64    /* n_neighbours + 1 + n_last at most, win_cap at most */
+#define SNK_SCENE_MAX_IMG 4096     /* [DEFINED] img_cap at most */
+#define SNK_SCENE_MAX_OBS 4194304  /* [DEFINED] obs_cap at most */
+
+#define SNK_SCENE_OK 0
+#define SNK_SCENE_SKIPPED 1         /* the query keyframe is bad (LocalBundleAdjustment.cpp:77) */
+#define SNK_SCENE_WINDOW_OVERFLOW 2 /* more than win_cap window keyframes */
+#define SNK_SCENE_PTS_OVERFLOW 3    /* more than pt_cap distinct points */
+#define SNK_SCENE_IMG_OVERFLOW 4    /* more than img_cap images */
+#define SNK_SCENE_OBS_OVERFLOW 5    /* more than obs_cap observation records */
+#define SNK_SCENE_BAD_INDEX 6       /* device forms: an id, a start or a count outside its range */
+
+#define SNK_SCENE_PT_CONST 4 /* pt_flags bit 2: mp->constant (beside SNK_COVIS_PT_BAD, SNK_COVIS_PT_FAR) */
+
+struct snk_ba_rpc; /* defined with the bundle adjustment below */
+
+/* The map as tables: the layouts and names of snk_covis_map / snk_lmap_map where they exist.  Host pointers for snk_scene_gather, device
+ * pointers for the _batch_dev form.  The IMU tables are either all NULL (no constraints) or all present. */
+typedef struct snk_scene_map
+{
+    int32_t n_kf, n_points, n_obs, n_feat, n_levels;
+    const uint8_t* kf_bad;           /* [n_kf] */
+    const int32_t* kf_prev;          /* [n_kf] previousKF as a slot, -1: none.  Not read by snk_scene_gather */
+    const double* kf_pose;           /* [n_kf][7] world -> camera: qx qy qz qw tx ty tz */
+    const int32_t* feat_start;       /* [n_kf + 1], feat_start[0] = 0 */
+    const int32_t* feat_point;       /* [n_feat] point ids, -1: none */
+    const float* feat_depth;         /* [n_feat] frame->depth[i] */
+    const float* feat_uv;            /* [n_feat][2] undistorted_keypoints[i].point */
+    const int32_t* feat_octave;      /* [n_feat] undistorted_keypoints[i].octave, 0 .. n_levels - 1 */
+    const int32_t* obs_start;        /* [n_points + 1], obs_start[0] = 0 */
+    const int32_t (*obs)[2];         /* [n_obs] GetObservationList() in list order as (kf, feature index inside the keyframe) */
+    const uint8_t* pt_flags;         /* [n_points] SNK_COVIS_PT_BAD | SNK_SCENE_PT_CONST */
+    const double* pt_pos;            /* [n_points][3] */
+    const float* level_inv_sq_scale; /* [n_levels] scalePyramid.InverseSquaredScale */
+    const double* kf_time;           /* [n_kf] frame->timeStamp */
+    const double* kf_imu_begin;      /* [n_kf] imudata.time_begin */
+    const double* kf_imu_end;        /* [n_kf] imudata.time_end */
+    const uint8_t* kf_preint_valid;  /* [n_kf] */
+    const struct snk_ba_rpc* kf_rpc; /* [n_kf] kf->rpc: only rel_pose and weight_translation are read */
+} snk_scene_map;
+
+typedef struct snk_scene_params
+{
+    int32_t n_neighbours; /* :126: 15 */
+    int32_t n_last;       /* :132: 20.  n_neighbours + 1 + n_last <= SNK_SCENE_MAX_WINDOW */
+    double gyro_weight;   /* current_gyro_weight: constraints only if > 0 and the IMU tables are present */
+    double acc_weight;    /* current_acc_weight */
+} snk_scene_params;
+
+/* One query of snk_scene_window.  status != SNK_SCENE_OK: n_window = 0. */
+typedef struct snk_scene_window_result
+{
+    int32_t n_window;
+    int32_t status;
+} snk_scene_window_result;
+
+/* One query of snk_scene_gather.  status != SNK_SCENE_OK: all counts 0. */
+typedef struct snk_scene_result
+{
+    int32_t n_window; /* the first n_window images are the window keyframes (constant = 0) */
+    int32_t n_img, n_pt, n_obs, n_rpc;
+    int32_t status;
+} snk_scene_result;
+
+/* The outputs of snk_scene_gather, row s for query s, laid out as snk_ba_problem takes them.  Rows past a query's counts are not
+ * written, except pt_id, which is -1 past n_pt (all of it where status != SNK_SCENE_OK). */
+typedef struct snk_scene_out
+{
+    int32_t win_cap, pt_cap, img_cap, obs_cap;
+    int32_t* img_kf;         /* [n_q][img_cap] kfmapinv */
+    double* pose;            /* [n_q][img_cap][7] */
+    uint8_t* img_const;      /* [n_q][img_cap] */
+    int32_t* pt_id;          /* [n_q][pt_cap] mpmapinv */
+    double* pt;              /* [n_q][pt_cap][3] */
+    uint8_t* pt_const;       /* [n_q][pt_cap] */
+    uint8_t* pt_valid;       /* [n_q][pt_cap] wp.valid = nEdges > 0 (:292) */
+    int32_t* obs_img;        /* [n_q][obs_cap] */
+    int32_t* obs_pt;         /* [n_q][obs_cap] */
+    double* obs_uv;          /* [n_q][obs_cap][2] */
+    double* obs_depth;       /* [n_q][obs_cap] */
+    double* obs_weight;      /* [n_q][obs_cap] */
+    int32_t* obs_src;        /* [n_q][obs_cap][2] (kf, feature index inside the keyframe): where an outlier flag goes in the map */
+    struct snk_ba_rpc* rpc;  /* [n_q][win_cap]; may be NULL where no constraints can be emitted */
+    snk_scene_result* result; /* [n_q] */
+} snk_scene_out;
+
+/* The window of LocalBundleAdjustment::MakeLocalScene — Snake/Optimizer/LocalBundleAdjustment.cpp:124-151 — for the n_q keyframes
+ * q[0 .. n_q).  conn_start [n_kf + 1] / conn_list are every keyframe's connections ascending by (weight, kf), the arguments of
+ * snk_lmap_select.  Candidates: the last min(n_neighbours, size) connections of q, q itself, then k = kf_prev[q], kf_prev[k], ... for at
+ * most n_last steps, stopping at -1; a bad keyframe of the chain counts as a step and is walked through.  Duplicates (:142) and bad
+ * keyframes (:145) are dropped, the rest is sorted ascending ([DEFINED] the slot stands for Keyframe::id(), as in snk-covis v1).
+ * window_kf [n_q][win_cap] (-1 past n_window), out [n_q].  q bad (:77): SNK_SCENE_SKIPPED; more than win_cap survivors:
+ * SNK_SCENE_WINDOW_OVERFLOW.  map.KeyFramesInMap() < 2 (:113) stays with the caller.  Everything is checked before anything is launched: a
+ * NULL array with a non-zero count, a start array that does not begin at 0 or decreases, a keyframe outside its range (q, kf_prev
+ * outside [-1, n_kf), a connection), n_kf > SNK_COVIS_MAX_KF, win_cap outside [1, SNK_SCENE_MAX_WINDOW], a parameter below 0,
+ * n_neighbours + 1 + n_last > SNK_SCENE_MAX_WINDOW: SNK_ERR_INVALID_ARG.  n_q == 0 is valid. */
+SNK_API int snk_scene_window(snk_matcher* m, int n_q, const int32_t* q, int n_kf, const uint8_t* kf_bad, const int32_t* kf_prev,
+                             const int32_t* conn_start, const snk_covis_conn* conn_list, const snk_scene_params* params, int win_cap,
+                             int32_t* window_kf, snk_scene_window_result* out);
+
+/* The same (:124-151) with every array on the device; n_list is the length of conn_list_dev.  Asynchronous on the handle's stream.  The
+ * kernel checks what the host cannot see: a query outside [0, n_kf), a kf_prev outside [-1, n_kf), a conn_start range outside
+ * [0, n_list] or decreasing, a connection's keyframe outside [0, n_kf) give that query SNK_SCENE_BAD_INDEX (before SKIPPED is looked
+ * at only for the query itself), and nothing outside the ranges is read. */
+SNK_API int snk_scene_window_batch_dev(snk_matcher* m, int n_q, const int32_t* q_dev, int n_kf, const uint8_t* kf_bad_dev,
+                                       const int32_t* kf_prev_dev, const int32_t* conn_start_dev, int n_list,
+                                       const snk_covis_conn* conn_list_dev, const snk_scene_params* params, int win_cap,
+                                       int32_t* window_kf_dev, snk_scene_window_result* out_dev);
+
+/* The scene of MakeLocalScene — LocalBundleAdjustment.cpp:154-346 — for n_q windows.  window_kf [n_q][out->win_cap] and win [n_q] are
+ * what snk_scene_window left; a stage-1 status other than OK is passed through.  Points (:154-167): the window keyframes in order, their
+ * features in order, -1 and bad points skipped, first appearances only.  Fixed cameras (:170-184): the points in that order, their
+ * observations in list order; every keyframe that is neither bad nor in the window, in order of first appearance.  Images (:200-244):
+ * the window (constant 0), then the fixed cameras (constant 1).  World points (:246-254) in point order; pt_valid = the point has an
+ * observation by a keyframe that is not bad (:292).  Observation records (:258-291): a bad keyframe's are skipped, so are those whose
+ * image and point are both constant; the rest is {image, point, uv, depth, weight = level_inv_sq_scale[octave]} widened to double,
+ * ordered as the flattened img.stereoPoints: image by image, inside an image ascending by (point index, list position).  Constraints
+ * (:295-346), only with the IMU tables and gyro_weight > 0: consecutive window keyframes (a, b) at images i - 1, i with
+ * kf_time[a] == kf_imu_begin[b], kf_time[b] == kf_imu_end[b], kf_preint_valid[b] give {i - 1, i, kf_rpc[b].rel_pose, gyro_weight / dt,
+ * kf_rpc[b].weight_translation * acc_weight / dt}, dt = kf_time[b] - kf_time[a], both weights 0 for dt > 2 ([DEFINED] the record's own
+ * img1 / img2 are not read).  Overflows are reported in the order PTS, IMG, OBS.  [DEFINED] the observations of a window's points are at
+ * most 2^30, its features too.  perKeyframeData / perPointData, stateBefore and UpdateLocalScene stay with the caller.
+ * Everything is checked before anything is launched: NULL arrays, caps outside [1, limit] (pt_cap <= SNK_LMAP_MAX_PTS), starts that do
+ * not begin at 0 or decrease, a point id outside [-1, n_points), an observation's keyframe outside [0, n_kf) or feature outside its
+ * keyframe's range, an octave outside [0, n_levels), a window that is not strictly ascending or out of range, IMU tables partly
+ * present: SNK_ERR_INVALID_ARG. */
+SNK_API int snk_scene_gather(snk_matcher* m, int n_q, const snk_scene_map* map, const int32_t* window_kf,
+                             const snk_scene_window_result* win, const snk_scene_params* params, const snk_scene_out* out);
+
+/* The same (:154-346) with every table and every output on the device.  Asynchronous.  The kernel checks the same and answers
+ * SNK_SCENE_BAD_INDEX for that query alone; the range checks of a phase come before its overflow, so a status does not depend on
+ * timing.  Only the ranges a query reaches are checked. */
+SNK_API int snk_scene_gather_batch_dev(snk_matcher* m, int n_q, const snk_scene_map* map_dev, const int32_t* window_kf_dev,
+                                       const snk_scene_window_result* win_dev, const snk_scene_params* params,
+                                       const snk_scene_out* out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Local map of fine tracking (snk-lmap v1)
  * ------------------------------------------------------------------------------------------ */
 

@@ -1074,6 +1074,140 @@ class LocalMapBuilder
     snk_lmap_params par_;
 };
 
+// LocalBundleAdjustment::MakeLocalScene, semantics "snk-scene v1" (reference Snake/Optimizer/LocalBundleAdjustment.cpp:94-346), for a
+// list of keyframes: Window picks the keyframes (:124-151), Gather builds the scene (:154-346).  Scenes holds the rows as
+// snk_ba_problem takes them; Problem(s, K, bf) points one at row s, to be handed to snk_ba_set_problem(s) while Scenes is alive.
+// img_kf / pt_id / obs_src are kfmapinv, mpmapinv and the place of an observation in the map, for UpdateLocalScene.
+class LocalSceneBuilder
+{
+   public:
+    struct Map  // the tables of snk_scene_map and every keyframe's connections (LocalMapBuilder::Graph's layout); imu: all five or none
+    {
+        std::vector<uint8_t> kf_bad;
+        std::vector<int32_t> kf_prev;
+        std::vector<double> kf_pose;  // [n_kf][7]
+        std::vector<int32_t> conn_start{0};
+        std::vector<snk_covis_conn> conn_list;
+        std::vector<int32_t> feat_start{0}, feat_point, feat_octave;
+        std::vector<float> feat_depth, feat_uv;  // feat_uv [n_feat][2]
+        std::vector<int32_t> obs_start{0}, obs;  // obs [n_obs][2]
+        std::vector<uint8_t> pt_flags;
+        std::vector<double> pt_pos;  // [n_points][3]
+        std::vector<float> level_inv_sq_scale;
+        bool imu = false;
+        std::vector<double> kf_time, kf_imu_begin, kf_imu_end;
+        std::vector<uint8_t> kf_preint_valid;
+        std::vector<snk_ba_rpc> kf_rpc;
+        snk_scene_map map() const
+        {
+            snk_scene_map m{};
+            m.n_kf = (int32_t)kf_bad.size(), m.n_points = (int32_t)pt_flags.size(), m.n_obs = (int32_t)obs.size() / 2, m.n_feat = (int32_t)feat_point.size();
+            m.n_levels = (int32_t)level_inv_sq_scale.size();
+            m.kf_bad = kf_bad.data(), m.kf_prev = kf_prev.data(), m.kf_pose = kf_pose.data(), m.feat_start = feat_start.data(), m.feat_point = feat_point.data();
+            m.feat_depth = feat_depth.data(), m.feat_uv = feat_uv.data(), m.feat_octave = feat_octave.data(), m.obs_start = obs_start.data();
+            m.obs = reinterpret_cast<const int32_t(*)[2]>(obs.data()), m.pt_flags = pt_flags.data(), m.pt_pos = pt_pos.data();
+            m.level_inv_sq_scale = level_inv_sq_scale.data();
+            if (imu)
+            {
+                m.kf_time = kf_time.data(), m.kf_imu_begin = kf_imu_begin.data(), m.kf_imu_end = kf_imu_end.data();
+                m.kf_preint_valid = kf_preint_valid.data(), m.kf_rpc = kf_rpc.data();
+            }
+            return m;
+        }
+    };
+    struct Windows  // [n_q][win_cap] window keyframes (-1 past n_window) and a record per query
+    {
+        std::vector<int32_t> window_kf;
+        std::vector<snk_scene_window_result> result;
+    };
+    struct Scenes  // the rows of snk_scene_out for n_q queries
+    {
+        int32_t win_cap = 0, pt_cap = 0, img_cap = 0, obs_cap = 0;
+        std::vector<int32_t> img_kf, pt_id, obs_img, obs_pt, obs_src;
+        std::vector<double> pose, pt, obs_uv, obs_depth, obs_weight;
+        std::vector<uint8_t> img_const, pt_const, pt_valid;
+        std::vector<snk_ba_rpc> rpc;
+        std::vector<snk_scene_result> result;
+        snk_scene_out out()
+        {
+            return snk_scene_out{win_cap,         pt_cap,          img_cap,       obs_cap,        img_kf.data(),  pose.data(),      img_const.data(),
+                                 pt_id.data(),    pt.data(),       pt_const.data(), pt_valid.data(), obs_img.data(), obs_pt.data(),  obs_uv.data(),
+                                 obs_depth.data(), obs_weight.data(), obs_src.data(), rpc.data(),     result.data()};
+        }
+        // a snk_ba_problem over row s (status SNK_SCENE_OK); K = fx fy cx cy
+        snk_ba_problem Problem(size_t s, const double K[4], double bf)
+        {
+            if (s >= result.size() || result[s].status != SNK_SCENE_OK) throw std::invalid_argument("LocalSceneBuilder: no scene in this row");
+            snk_ba_problem p{};
+            p.n_img = result[s].n_img, p.n_pt = result[s].n_pt, p.n_obs = result[s].n_obs, p.n_rpc = result[s].n_rpc;
+            p.pose      = reinterpret_cast<double(*)[7]>(pose.data() + s * (size_t)img_cap * 7);
+            p.img_const = img_const.data() + s * (size_t)img_cap;
+            p.pt        = reinterpret_cast<double(*)[3]>(pt.data() + s * (size_t)pt_cap * 3);
+            p.pt_const  = pt_const.data() + s * (size_t)pt_cap;
+            p.obs_img = obs_img.data() + s * (size_t)obs_cap, p.obs_pt = obs_pt.data() + s * (size_t)obs_cap;
+            p.obs_uv    = reinterpret_cast<const double(*)[2]>(obs_uv.data() + s * (size_t)obs_cap * 2);
+            p.obs_depth = obs_depth.data() + s * (size_t)obs_cap, p.obs_weight = obs_weight.data() + s * (size_t)obs_cap;
+            for (int i = 0; i < 4; ++i) p.K[i] = K[i];
+            p.bf  = bf;
+            p.rpc = p.n_rpc ? rpc.data() + s * (size_t)win_cap : nullptr;
+            return p;
+        }
+    };
+
+    explicit LocalSceneBuilder(const snk_scene_params& params, int win_cap = 36, int device = 0) : par_(params), win_cap_(win_cap)
+    {
+        check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create");
+    }
+    ~LocalSceneBuilder() { snk_matcher_destroy(h_); }
+    LocalSceneBuilder(const LocalSceneBuilder&)            = delete;
+    LocalSceneBuilder& operator=(const LocalSceneBuilder&) = delete;
+
+    Windows Window(const Map& map, const std::vector<int32_t>& q)
+    {
+        Windows out;
+        out.window_kf.assign(q.size() * (size_t)win_cap_, -1);
+        out.result.resize(q.size());
+        check(snk_scene_window(h_, (int)q.size(), q.data(), (int)map.kf_bad.size(), map.kf_bad.data(), map.kf_prev.data(), map.conn_start.data(),
+                               map.conn_list.data(), &par_, win_cap_, out.window_kf.data(), out.result.data()),
+              "snk_scene_window");
+        return out;
+    }
+
+    Scenes Gather(const Map& map, const Windows& win, int pt_cap, int img_cap, int obs_cap)
+    {
+        const size_t n = win.result.size(), pc = (size_t)std::max(pt_cap, 1), ic = (size_t)std::max(img_cap, 1), oc = (size_t)std::max(obs_cap, 1);
+        Scenes s;
+        s.win_cap = win_cap_, s.pt_cap = pt_cap, s.img_cap = img_cap, s.obs_cap = obs_cap;
+        s.img_kf.assign(n * ic, -1), s.pose.assign(n * ic * 7, 0.0), s.img_const.assign(n * ic, 0);
+        s.pt_id.assign(n * pc, -1), s.pt.assign(n * pc * 3, 0.0), s.pt_const.assign(n * pc, 0), s.pt_valid.assign(n * pc, 0);
+        s.obs_img.assign(n * oc, -1), s.obs_pt.assign(n * oc, -1), s.obs_uv.assign(n * oc * 2, 0.0), s.obs_depth.assign(n * oc, 0.0);
+        s.obs_weight.assign(n * oc, 0.0), s.obs_src.assign(n * oc * 2, -1), s.rpc.assign(n * (size_t)win_cap_, snk_ba_rpc{}), s.result.resize(n);
+        const snk_scene_map m = map.map();
+        const snk_scene_out o = s.out();
+        check(snk_scene_gather(h_, (int)n, &m, win.window_kf.data(), win.result.data(), &par_, &o), "snk_scene_gather");
+        return s;
+    }
+
+    // the device forms: every pointer is device memory, nothing is copied, the call returns before the kernel has run
+    void WindowDev(int n_q, const int32_t* q_dev, int n_kf, const uint8_t* kf_bad_dev, const int32_t* kf_prev_dev, const int32_t* conn_start_dev, int n_list,
+                   const snk_covis_conn* conn_list_dev, int32_t* window_kf_dev, snk_scene_window_result* out_dev)
+    {
+        check(snk_scene_window_batch_dev(h_, n_q, q_dev, n_kf, kf_bad_dev, kf_prev_dev, conn_start_dev, n_list, conn_list_dev, &par_, win_cap_, window_kf_dev,
+                                         out_dev),
+              "snk_scene_window_batch_dev");
+    }
+    void GatherDev(int n_q, const snk_scene_map& map_dev, const int32_t* window_kf_dev, const snk_scene_window_result* win_dev, const snk_scene_out& out_dev)
+    {
+        check(snk_scene_gather_batch_dev(h_, n_q, &map_dev, window_kf_dev, win_dev, &par_, &out_dev), "snk_scene_gather_batch_dev");
+    }
+    void Sync() { check(snk_matcher_sync(h_), "snk_matcher_sync"); }
+
+   private:
+    snk_matcher* h_ = nullptr;
+    snk_scene_params par_;
+    int win_cap_;
+};
+
 // Saiga::P3PRansac as Tracking::TrackBruteForce uses it -- Snake/Tracking/TrackingCoarse.cpp:403-440, semantics "snk-p3p v1":
 //   RansacParameters params; params.maxIterations = 250; params.residualThreshold = chi1 * chi1;
 //   P3PRansac pnp2(params);  inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask);

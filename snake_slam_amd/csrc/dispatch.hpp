@@ -1,4 +1,4 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, localmap.hip, ba.hip,
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, localmap.hip, scene.hip, ba.hip,
 // orb.hip (the extractor's whole launch plan, over the geometry of orb_layout.hpp) and track.hip (the projection matchers) live.
 // Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every
 // shape of the GPU tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
@@ -208,6 +208,34 @@ constexpr size_t lmap_select_carve(int n_kf, int kf_cap, int n_neighbours)
 constexpr size_t lmap_gather_carve(int kf_cap, int pts_cap)
 {
     return (size_t)lmap_table_slots(pts_cap) * 4 + (size_t)(2 * kf_cap + 1) * 4 + (size_t)LMAP_MISC * 4;
+}
+
+// ---- local BA windows (scene.hip: snk_scene_window, snk_scene_gather and their _batch_dev forms) -------------------------------------
+// One form each, a workgroup per query.  scene_window_kernel: one wavefront, a lane per candidate.  scene_gather_kernel: four wavefronts;
+// its carve is used twice: first the point table of lmap_gather_kernel (four-byte slots), then, the point list being in the pt_id row,
+// the fixed-camera table (a key and a value per slot), the sort keys of the fixed cameras, a base per image and the words of a chunk.
+constexpr int SCENE_WIN_THREADS = 64;   // one wavefront: a lane per candidate (SCENE_MAX_WINDOW)
+constexpr int SCENE_THREADS     = 256;  // four wavefronts; a chunk is one point or one observation per lane
+constexpr int SCENE_MISC        = 32;   // u32 words of flags, counts and the per-wavefront partial sums (two banks)
+constexpr int SCENE_WIN_SLOTS   = 64;   // window keyframes kept in LDS (SCENE_MAX_WINDOW)
+
+constexpr size_t scene_window_carve() { return (size_t)(SCENE_WIN_SLOTS + 4) * 4; }
+// slots of the fixed-camera table: load at most 0.5 at img_cap, room for a claim per lane in flight
+constexpr int scene_img_slots(int img_cap) { return lmap_pow2_at_least(2 * img_cap, 2 * SCENE_THREADS); }
+constexpr int scene_sort_len(int img_cap) { return lmap_pow2_at_least(img_cap, 4); }
+// phase 1: the point table, the prefix sums (65) and the starts (64) of the window's feature ranges
+constexpr size_t scene_points_carve(int pt_cap) { return (size_t)lmap_table_slots(pt_cap) * 4 + (size_t)(2 * SCENE_WIN_SLOTS + 1) * 4; }
+// phase 2: key and value per slot, the sort keys, a base per image, per chunk: the points' stream starts (257), their observation starts,
+// their ids and constant flags packed (256), the images of a chunk's records (256)
+constexpr size_t scene_obs_carve(int img_cap)
+{
+    return (size_t)scene_img_slots(img_cap) * 8 + (size_t)scene_sort_len(img_cap) * 4 + (size_t)img_cap * 4 + (size_t)(4 * SCENE_THREADS + 1) * 4;
+}
+// LDS carve of scene_gather_kernel: the window keyframes and the words above, then the larger of the two phases
+constexpr size_t scene_gather_carve(int pt_cap, int img_cap)
+{
+    const size_t a = scene_points_carve(pt_cap), b = scene_obs_carve(img_cap);
+    return (size_t)(SCENE_WIN_SLOTS + SCENE_MISC) * 4 + (a > b ? a : b);
 }
 
 // ---- bundle adjustment (ba.hip: ba_plan_pcg, enqueue_lm, snk_ba_solve_async, snk_ba_pcg_form; the hand-over asks ba_sets_will_run) --
