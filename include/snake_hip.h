@@ -311,7 +311,9 @@ SNK_API int snk_feature_grid(snk_matcher* m, const snk_kp64* undistorted, int n,
 
 /* Batched, device-resident Preprocess::computeFeatureGrid (Preprocess.cpp:244-266): builds the grid
  * of every image and scatters its rectified keypoints and descriptors into grid order
- * (kps_out / desc_out); perm_dev [batch][cap], cell_start_dev [batch][cols*rows + 1]. */
+ * (kps_out / desc_out); perm_dev [batch][cap], cell_start_dev [batch][cols*rows + 1].
+ * n_dev[b] is a device-side count that the host cannot validate: it is read as min(max(n_dev[b], 0), cap), and
+ * entries of perm / kps_out / desc_out past that count are left as they were. */
 SNK_API int snk_feature_grid_batch_dev(snk_matcher* m, const snk_grid_bounds* bounds, const snk_kp64* kps_dev,
                                        const uint64_t* desc_dev, const int32_t* n_dev, int cap, int batch,
                                        snk_kp64* kps_out_dev, uint64_t* desc_out_dev, int32_t* perm_dev,
@@ -493,14 +495,17 @@ typedef struct snk_frames_dev
 /* SearchByProjectionFrameFrame2 for every frame of the batch (same rules and results as snk_match_project_coarse).
  * poses_dev: [batch][7] doubles ON THE DEVICE (qx qy qz qw tx ty tz; e.g. left there by the previous frame's pose
  * refinement); pts_dev [batch][pts_cap], n_pts_dev [batch]; outputs match_idx_dev [batch][pts_cap] (-1 = none, also for
- * entries past n_pts) and n_matches_dev [batch].  Asynchronous on the handle's stream. */
+ * entries past n_pts) and n_matches_dev [batch].  Asynchronous on the handle's stream.
+ * The device-side counts cannot be validated by the host, so every batched entry below (coarse, fine, fine_ro, mark_taken) reads
+ * n_pts_dev[b] as min(max(n_pts_dev[b], 0), pts_cap) and frames->n[b] as min(max(n[b], 0), cap): a count out of range gives the
+ * results of the clamped count and no access outside the frame's rows. */
 SNK_API int snk_match_project_coarse_batch_dev(snk_matcher* m, const snk_frames_dev* frames, const snk_camera* cam,
                                                const double* poses_dev, const snk_lm_coarse* pts_dev,
                                                const int32_t* n_pts_dev, int pts_cap, float th, int feature_error,
                                                int direction, const float* level_scale, int n_levels,
                                                int32_t* match_idx_dev, int32_t* n_matches_dev);
 
-/* SearchByProjection2 for every frame of the batch (same rules and results as snk_match_project_fine; pts_dev[..].valid is
+/* SearchByProjection2 (SnakeORBMatcher.cpp:365-526) for every frame of the batch (same rules and results as snk_match_project_fine; pts_dev[..].valid is
  * updated in place, visible_dev [batch][pts_cap]). */
 SNK_API int snk_match_project_fine_batch_dev(snk_matcher* m, const snk_frames_dev* frames, const snk_camera* cam,
                                              const double* poses_dev, snk_lm_fine* pts_dev, const int32_t* n_pts_dev,

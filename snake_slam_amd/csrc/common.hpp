@@ -16,6 +16,9 @@ namespace snk
 {
 void set_error(const char* fmt, ...);
 
+// SNK_DEBUG: the launch plan of a call on stderr.  Read at every call: a test switches it on inside its process.
+inline bool debug_plan_lines() { return getenv("SNK_DEBUG") != nullptr; }
+
 #define SNK_HIP_CHECK(expr)                                                                      \
     do                                                                                           \
     {                                                                                            \

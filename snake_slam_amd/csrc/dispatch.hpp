@@ -909,4 +909,34 @@ inline TrackBatchPlan track_batch_plan(int pts_cap, int batch, int cap, int ncel
     P.lds       = P.claim_off >= 0 ? (size_t)P.claim_off + (size_t)cap * 4 : flds;
     return P;
 }
+
+// The separate resolution (resolve_batch_kernel) keeps the claims of a frame's features in LDS up to this capacity (128 KB of ints,
+// 1024 threads per frame) and in global memory beyond it.
+constexpr int TRACK_RESOLVE_LDS_FEATURES = 32768;
+inline bool track_resolve_in_lds(int cap) { return cap <= TRACK_RESOLVE_LDS_FEATURES; }
+
+// Where a batched matcher's claims are resolved: fused = in the frame kernel itself; lds / global: resolve_batch_kernel<true / false>
+enum class TrackResolve { fused, lds, global };
+inline const char* track_name(TrackResolve r) { return r == TrackResolve::fused ? "fused" : (r == TrackResolve::lds ? "lds" : "global"); }
+inline TrackResolve track_resolve_form(const TrackBatchPlan& P, int cap)
+{
+    if (P.form == TrackForm::frame && P.claim_off >= 0) return TrackResolve::fused;
+    return track_resolve_in_lds(cap) ? TrackResolve::lds : TrackResolve::global;
+}
+
+// ---- feature grid (track.hip: snk_feature_grid, snk_feature_grid_batch_dev) -----------------------------------------------------------
+constexpr int GRID_MAX_FEATURES  = 16384;      // features of a frame: the bitonic network sorts (cell << 16 | index) keys in 64 KB of LDS
+constexpr int GRID_COUNT_LDS_MAX = 96 * 1024;  // LDS carve of the counting form
+
+// LDS of grid_count_kernel: counts / starts and the fill cursors of ncell + 1 cells, the cell and the segment slot of n features
+constexpr size_t grid_count_lds(int n, int ncell) { return ((size_t)2 * ((size_t)ncell + 1) + (size_t)2 * (size_t)n) * 4; }
+
+// count: grid_count_kernel (histogram, scan, rank inside the cell: five barriers);  network: grid_kernel (bitonic sort), where the
+// counting form's LDS does not fit.  network_env: SNK_GRID_NETWORK (A/B, tests: the network also where the counting form fits)
+enum class GridForm { count, network };
+inline const char* grid_name(GridForm f) { return f == GridForm::count ? "count" : "network"; }
+inline GridForm grid_form(int cap, int ncell, bool network_env)
+{
+    return (grid_count_lds(cap, ncell) <= (size_t)GRID_COUNT_LDS_MAX && !network_env) ? GridForm::count : GridForm::network;
+}
 }  // namespace snk

@@ -220,10 +220,14 @@ struct FramesDev
     double min_x, min_y, max_x, max_y;
 };
 
+// A count read from device memory (features of a frame, points of a local map) cannot be validated by the host: every kernel reads it
+// through here, so it is never negative and never past the row / the LDS carve sized for `cap`
+__device__ __forceinline__ int clamp_count(int n, int cap) { return min(max(n, 0), cap); }
+
 __device__ __forceinline__ FrameDev frame_of(const FramesDev& B, int b)
 {
     FrameDev F;
-    F.n            = min(max(B.n[b], 0), B.cap);  // device-side counts cannot be validated by the host: never past the frame's slab / LDS carve
+    F.n            = clamp_count(B.n[b], B.cap);
     F.cols         = B.cols;
     F.rows         = B.rows;
     F.kps          = B.kps + (size_t)b * B.cap;
@@ -418,7 +422,7 @@ __global__ __launch_bounds__(256) void coarse_batch_kernel(FramesDev Fb, const C
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.y, i0 = (blockIdx.x * 4 + wave) * ppw;
-    const int m = min(m_dev[b], m_cap);
+    const int m = clamp_count(m_dev[b], m_cap);
     if (i0 >= m) return;
     const FrameDev F = frame_of(Fb, b);
     const CamDev C   = cams[b];
@@ -539,7 +543,7 @@ __global__ __launch_bounds__(256) void fine_batch_kernel(FramesDev Fb, const Cam
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.y, i0 = (blockIdx.x * 4 + wave) * ppw;
-    const int m = min(m_dev[b], m_cap);
+    const int m = clamp_count(m_dev[b], m_cap);
     if (i0 >= m) return;
     const FrameDev F = frame_of(Fb, b);
     const CamDev C   = cams[b];
@@ -634,8 +638,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const int* __restrict__ be
     resolve_body(best, bins, m, taken, claim, n_feat, with_rotation, match_idx, n_out);
 }
 
-// LDS_CLAIM: dynamic LDS of Fb.cap ints holds the claims (frames up to RESOLVE_LDS_FEATURES features); 1024 threads per frame
-constexpr int RESOLVE_LDS_FEATURES = 32768;
+// LDS_CLAIM: dynamic LDS of Fb.cap ints holds the claims (track_resolve_in_lds, dispatch.hpp); 1024 threads per frame
 template <bool LDS_CLAIM>
 __global__ __launch_bounds__(1024) void resolve_batch_kernel(const int* __restrict__ best, const int* __restrict__ bins,
                                                              const int* __restrict__ m_dev, int m_cap, FramesDev Fb,
@@ -644,13 +647,13 @@ __global__ __launch_bounds__(1024) void resolve_batch_kernel(const int* __restri
 {
     extern __shared__ __attribute__((aligned(16))) int s_claim[];
     const int b = blockIdx.x;
-    const int m = min(m_dev[b], m_cap);
+    const int m = clamp_count(m_dev[b], m_cap);
     if constexpr (LDS_CLAIM)
         resolve_body(best + (size_t)b * m_cap, bins ? bins + (size_t)b * m_cap : nullptr, m, Fb.taken + (size_t)b * Fb.cap, s_claim,
-                     min(Fb.n[b], Fb.cap), with_rotation, match_idx + (size_t)b * m_cap, n_out + b);
+                     clamp_count(Fb.n[b], Fb.cap), with_rotation, match_idx + (size_t)b * m_cap, n_out + b);
     else
         resolve_body(best + (size_t)b * m_cap, bins ? bins + (size_t)b * m_cap : nullptr, m, Fb.taken + (size_t)b * Fb.cap,
-                     claim + (size_t)b * Fb.cap, min(Fb.n[b], Fb.cap), with_rotation, match_idx + (size_t)b * m_cap, n_out + b);
+                     claim + (size_t)b * Fb.cap, clamp_count(Fb.n[b], Fb.cap), with_rotation, match_idx + (size_t)b * m_cap, n_out + b);
     // entries past the frame's point count read as "no match"
     for (int i = m + threadIdx.x; i < m_cap; i += blockDim.x) match_idx[(size_t)b * m_cap + i] = -1;
 }
@@ -676,7 +679,7 @@ __global__ __launch_bounds__(1024, SNK_TRACK_FRAME_WAVES_PER_EU) void coarse_fra
     extern __shared__ __attribute__((aligned(16))) unsigned char frame_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.y;
-    const int m = min(m_dev[b], m_cap);
+    const int m = clamp_count(m_dev[b], m_cap);
     const bool fused = claim_off >= 0;
     if (!fused && blockIdx.x * 1024 >= m) return;  // whole workgroup
     int* claim = fused ? reinterpret_cast<int*>(frame_lds + claim_off) : nullptr;
@@ -713,7 +716,7 @@ __global__ __launch_bounds__(1024, SNK_TRACK_FRAME_WAVES_PER_EU) void fine_frame
     extern __shared__ __attribute__((aligned(16))) unsigned char frame_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.y;
-    const int m = min(m_dev[b], m_cap);
+    const int m = clamp_count(m_dev[b], m_cap);
     const bool fused = claim_off >= 0;
     if (!fused && blockIdx.x * 1024 >= m) return;  // whole workgroup
     // The frame (65 KB for 1000 features) is staged ONCE per workgroup and the workgroup walks the chunks blockIdx.x, + gridDim.x, ...
@@ -771,7 +774,7 @@ __global__ void mark_taken_kernel(const int* __restrict__ match_idx, const int* 
                                   int cap)
 {
     const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= min(m_dev[b], m_cap)) return;
+    if (i >= clamp_count(m_dev[b], m_cap)) return;
     const int f = match_idx[(size_t)b * m_cap + i];
     if (f >= 0 && f < cap) taken[(size_t)b * cap + f] = 1;
 }
@@ -828,8 +831,7 @@ __global__ __launch_bounds__(256) void grid_kernel(const snk_kp64* __restrict__ 
     u32* keys     = reinterpret_cast<u32*>(gsm);
     const int tid = threadIdx.x;
     const int b   = blockIdx.x;
-    int n         = n_dev ? n_dev[b] : n_host;
-    n             = n < cap ? n : cap;
+    const int n   = clamp_count(n_dev ? n_dev[b] : n_host, cap);
     int n_pow2    = 2;
     while (n_pow2 < n) n_pow2 <<= 1;
     kps += (size_t)b * cap;
@@ -883,8 +885,7 @@ __global__ __launch_bounds__(256) void grid_kernel(const snk_kp64* __restrict__ 
 // cell's segment in arrival order, final position of a feature = segment start + number of members with a smaller index (cells hold
 // one or two features on average).  Five barriers instead of the 55 compare-exchange stages of the bitonic network: 22 -> ~5 us for
 // the one frame of a per-frame call (the network's time is latency, not work).  Same perm / order / cell_start.  LDS: 2 (ncell + 1)
-// + 2 n ints (GRID_COUNT_LDS_MAX bounds it; larger grids keep the network).
-constexpr int GRID_COUNT_LDS_MAX = 96 * 1024;
+// + 2 n ints (grid_count_lds; grid_form of dispatch.hpp keeps the network where that exceeds GRID_COUNT_LDS_MAX).
 __global__ __launch_bounds__(256) void grid_count_kernel(const snk_kp64* __restrict__ kps, const int* __restrict__ n_dev, int n_host, int cap,
                                                          double min_x, double min_y, int cols, int rows, int* __restrict__ perm,
                                                          int* __restrict__ order, int* __restrict__ cell_start)
@@ -893,8 +894,7 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const snk_kp64* __restr
     __shared__ int s_wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b   = blockIdx.x;
-    int n         = n_dev ? n_dev[b] : n_host;
-    n             = n < cap ? n : cap;
+    const int n   = clamp_count(n_dev ? n_dev[b] : n_host, cap);
     kps += (size_t)b * cap;
     perm += (size_t)b * cap;
     if (order) order += (size_t)b * cap;
@@ -947,7 +947,16 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const snk_kp64* __restr
         if (order) order[r] = i;
     }
 }
-bool grid_count_fits(int n, int ncell) { return ((size_t)2 * (ncell + 1) + (size_t)2 * n) * 4 <= (size_t)GRID_COUNT_LDS_MAX; }
+// SNK_DEBUG: the plan of a launch on stderr, one line per call (tests/forms.py reads them: grid_plan_lines, track_plan_lines)
+void print_grid_plan(int cap, int ncell, int batch, GridForm form)
+{
+    fprintf(stderr, "snake_hip: grid plan cap=%d ncell=%d batch=%d form=%s\n", cap, ncell, batch, grid_name(form));
+}
+void print_track_plan(const char* entry, int pts_cap, int batch, int cap, int ncell1, const TrackBatchPlan& P)
+{
+    fprintf(stderr, "snake_hip: track plan entry=%s pts_cap=%d batch=%d cap=%d ncell1=%d form=%s ppw=%d wgs=%d resolve=%s\n", entry, pts_cap, batch, cap,
+            ncell1, track_name(P.form), P.ppw, P.wgs, track_name(track_resolve_form(P, cap)));
+}
 bool grid_use_network()
 {
     static const bool v = getenv("SNK_GRID_NETWORK") != nullptr;  // A/B, tests: the bitonic network also where the counting form fits
@@ -960,8 +969,7 @@ __global__ __launch_bounds__(256) void reorder_kernel(const int* __restrict__ or
                                                       snk_kp64* __restrict__ kout, uint4* __restrict__ dout)
 {
     const int b = blockIdx.y;
-    int n       = n_dev[b];
-    n           = n < cap ? n : cap;
+    const int n = clamp_count(n_dev[b], cap);
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const size_t base = (size_t)b * cap;
@@ -1444,7 +1452,7 @@ int snk_feature_grid(snk_matcher* m, const snk_kp64* undistorted, int n, const s
                      int32_t* cell_start, int* cols_out, int* rows_out)
 {
     SNK_REQUIRE(m != nullptr && bounds != nullptr && cell_start != nullptr, "NULL argument");
-    SNK_REQUIRE(n >= 0 && n <= 16384, "feature count must be 0..16384");
+    SNK_REQUIRE(n >= 0 && n <= GRID_MAX_FEATURES, "feature count must be 0..16384");
     SNK_REQUIRE(n == 0 || (undistorted && perm), "NULL buffer");
     int cols, rows;
     grid_dims(bounds, &cols, &rows);
@@ -1468,16 +1476,18 @@ int snk_feature_grid(snk_matcher* m, const snk_kp64* undistorted, int n, const s
         memcpy(m->h_in.p, undistorted, (size_t)n * sizeof(snk_kp64));  // pinned staging: see matcher_handle.hpp
         SNK_HIP_CHECK(hipMemcpyAsync(m->aux.p, m->h_in.p, (size_t)n * sizeof(snk_kp64), hipMemcpyHostToDevice, m->stream));
     }
-    if (grid_count_fits(n, cols * rows) && !grid_use_network())
+    const GridForm form = grid_form(n, cols * rows, grid_use_network());
+    if (debug_plan_lines()) print_grid_plan(n, cols * rows, 1, form);
+    if (form == GridForm::count)
     {
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_count_kernel), GRID_COUNT_LDS_MAX)) != SNK_OK) return rc;
-        hipLaunchKernelGGL(grid_count_kernel, dim3(1), dim3(256), ((size_t)2 * (cols * rows + 1) + (size_t)2 * n) * 4, m->stream,
+        hipLaunchKernelGGL(grid_count_kernel, dim3(1), dim3(256), grid_count_lds(n, cols * rows), m->stream,
                            m->aux.as<snk_kp64>(), (const int*)nullptr, n, n > 0 ? n : 1, bounds->min_x, bounds->min_y, cols, rows, d_perm,
                            (int*)nullptr, d_cs);
     }
     else
     {
-        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_kernel), 16384 * 4)) != SNK_OK) return rc;
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_kernel), GRID_MAX_FEATURES * 4)) != SNK_OK) return rc;
         hipLaunchKernelGGL(grid_kernel, dim3(1), dim3(256), (size_t)n_pow2 * 4, m->stream, m->aux.as<snk_kp64>(), (const int*)nullptr,
                            n, n > 0 ? n : 1, bounds->min_x, bounds->min_y, cols, rows, d_perm, (int*)nullptr, d_cs);
     }
@@ -1496,7 +1506,7 @@ int snk_feature_grid_batch_dev(snk_matcher* m, const snk_grid_bounds* bounds, co
                                uint64_t* desc_out_dev, int32_t* perm_dev, int32_t* cell_start_dev)
 {
     SNK_REQUIRE(m != nullptr && bounds != nullptr, "NULL argument");
-    SNK_REQUIRE(batch >= 0 && cap >= 1 && cap <= 16384, "cap must be 1..16384");
+    SNK_REQUIRE(batch >= 0 && cap >= 1 && cap <= GRID_MAX_FEATURES, "cap must be 1..16384");
     SNK_REQUIRE(kps_dev && desc_dev && n_dev && kps_out_dev && desc_out_dev && perm_dev && cell_start_dev, "NULL device buffer");
     int cols, rows;
     grid_dims(bounds, &cols, &rows);
@@ -1507,15 +1517,17 @@ int snk_feature_grid_batch_dev(snk_matcher* m, const snk_grid_bounds* bounds, co
     if ((rc = m->aux2.reserve((size_t)batch * cap * 4)) != SNK_OK) return rc;
     int cap_pow2 = 2;
     while (cap_pow2 < cap) cap_pow2 <<= 1;
-    if (grid_count_fits(cap, cols * rows) && !grid_use_network())
+    const GridForm form = grid_form(cap, cols * rows, grid_use_network());
+    if (debug_plan_lines()) print_grid_plan(cap, cols * rows, batch, form);
+    if (form == GridForm::count)
     {
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_count_kernel), GRID_COUNT_LDS_MAX)) != SNK_OK) return rc;
-        hipLaunchKernelGGL(grid_count_kernel, dim3(batch), dim3(256), ((size_t)2 * (cols * rows + 1) + (size_t)2 * cap) * 4, m->stream, kps_dev,
+        hipLaunchKernelGGL(grid_count_kernel, dim3(batch), dim3(256), grid_count_lds(cap, cols * rows), m->stream, kps_dev,
                            n_dev, 0, cap, bounds->min_x, bounds->min_y, cols, rows, perm_dev, m->aux2.as<int>(), cell_start_dev);
     }
     else
     {
-        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_kernel), 16384 * 4)) != SNK_OK) return rc;
+        if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_kernel), GRID_MAX_FEATURES * 4)) != SNK_OK) return rc;
         hipLaunchKernelGGL(grid_kernel, dim3(batch), dim3(256), (size_t)cap_pow2 * 4, m->stream, kps_dev, n_dev, 0, cap, bounds->min_x,
                            bounds->min_y, cols, rows, perm_dev, m->aux2.as<int>(), cell_start_dev);
     }
@@ -1682,9 +1694,9 @@ int batch_scratch(snk_matcher* m, int batch, int m_cap, int cap, const snk_camer
 static int launch_resolve_batch(snk_matcher* m, int batch, int cap, const int* best, const int* bins, const int* n_pts_dev, int pts_cap,
                                 const FramesDev& F, int* claim, int with_rotation, int* match_idx_dev, int* n_matches_dev)
 {
-    if (cap <= RESOLVE_LDS_FEATURES)
+    if (track_resolve_in_lds(cap))
     {
-        int rc = set_max_lds_once(reinterpret_cast<const void*>(resolve_batch_kernel<true>), RESOLVE_LDS_FEATURES * (int)sizeof(int) + 1024);
+        int rc = set_max_lds_once(reinterpret_cast<const void*>(resolve_batch_kernel<true>), TRACK_RESOLVE_LDS_FEATURES * (int)sizeof(int) + 1024);
         if (rc != SNK_OK) return rc;
         hipLaunchKernelGGL(resolve_batch_kernel<true>, dim3(batch), dim3(1024), (size_t)cap * sizeof(int), m->stream, best, bins, n_pts_dev,
                            pts_cap, F, claim, with_rotation, match_idx_dev, n_matches_dev);
@@ -1717,6 +1729,7 @@ int snk_match_project_coarse_batch_dev(snk_matcher* m, const snk_frames_dev* fra
     int *best, *bins, *claim;
     if ((rc = batch_scratch(m, batch, pts_cap, F.cap, cam, poses_dev, &cams, &best, &bins, &claim)) != SNK_OK) return rc;
     const TrackBatchPlan P = track_batch_plan(pts_cap, batch, F.cap, F.cols * F.rows + 1, track_switches());
+    if (debug_plan_lines()) print_track_plan("coarse", pts_cap, batch, F.cap, F.cols * F.rows + 1, P);
     if (P.form == TrackForm::frame)
     {
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(coarse_frame_kernel), TRACK_FRAME_LDS_MAX)) != SNK_OK) return rc;
@@ -1756,6 +1769,7 @@ static int fine_batch_impl(snk_matcher* m, const snk_frames_dev* frames, const s
     if ((rc = batch_scratch(m, batch, pts_cap, F.cap, cam, poses_dev, &cams, &best, &bins, &claim)) != SNK_OK) return rc;
     SNK_HIP_CHECK(hipMemsetAsync(visible_dev, 0, (size_t)batch * pts_cap, m->stream));
     const TrackBatchPlan P = track_batch_plan(pts_cap, batch, F.cap, F.cols * F.rows + 1, track_switches());
+    if (debug_plan_lines()) print_track_plan(write_valid ? "fine" : "fine_ro", pts_cap, batch, F.cap, F.cols * F.rows + 1, P);
     const int ppw          = P.ppw;
     if (P.form == TrackForm::frame)
     {

@@ -27,6 +27,9 @@
 //   track_form:pts_cap:batch:cap:ncell1:no_frame_lds:ppw_env     track_plan:pts_cap:batch:cap:ncell1:no_frame_lds:frame_wgs:no_fused_resolve:ppw_env  "ppw,wgs,claim_off,lds"
 //   track_wgs:chunks:batch:forced                 track_claim:wgs:frame_lds:cap:off
 //   track_ppw:total_points:ppw_env                track_lds:cap:ncell1
+//   track_launch:pts_cap:batch:cap:ncell1:no_frame_lds:frame_wgs:no_fused_resolve:ppw_env    "form/wgs/resolve" as the plan line of a batched matcher names them
+//   track_resolve_lds:cap                         1: the separate resolution keeps its claims in LDS
+//   grid_form:cap:ncell:network_env               grid_lds:n:ncell (the counting form's LDS)
 //   capacity:bytes                                what a scratch buffer asked for that many bytes holds
 //   const:NAME
 // Exit status 2 on an argument it cannot read.
@@ -311,6 +314,16 @@ int main(int argc, char** argv)
             if (e == "track_form") std::printf("%s\n", snk::track_name(P.form));
             else std::printf("%d,%d,%d,%zu\n", P.ppw, P.wgs, P.claim_off, P.lds);
         }
+        else if (e == "track_launch" && n == 8)
+        {
+            snk::TrackSwitches ts;
+            ts.no_frame_lds = v[4] != 0, ts.frame_wgs = (int)v[5], ts.no_fused_resolve = v[6] != 0, ts.ppw = (int)v[7];
+            const snk::TrackBatchPlan P = snk::track_batch_plan((int)v[0], (int)v[1], (int)v[2], (int)v[3], ts);
+            std::printf("%s/%d/%s\n", snk::track_name(P.form), P.wgs, snk::track_name(snk::track_resolve_form(P, (int)v[2])));
+        }
+        else if (e == "track_resolve_lds" && n == 1) std::printf("%d\n", (int)snk::track_resolve_in_lds((int)v[0]));
+        else if (e == "grid_form" && n == 3) std::printf("%s\n", snk::grid_name(snk::grid_form((int)v[0], (int)v[1], v[2] != 0)));
+        else if (e == "grid_lds" && n == 2) std::printf("%zu\n", snk::grid_count_lds((int)v[0], (int)v[1]));
         else if (e == "track_wgs" && n == 3) std::printf("%d\n", snk::track_frame_wgs((int)v[0], (int)v[1], (int)v[2]));
         else if (e == "track_claim" && n == 4) std::printf("%d\n", snk::track_fused_claim_offset((int)v[0], (size_t)v[1], (int)v[2], v[3] != 0));
         else if (e == "track_ppw" && n == 2) std::printf("%d\n", snk::track_points_per_wave(v[0], (int)v[1]));
@@ -358,6 +371,10 @@ int main(int argc, char** argv)
             else if (c == "ORB_DIST_LARGE_LDS_MAX") val = (int)snk::orb::DIST_LARGE_LDS_MAX;
             else if (c == "TRACK_FRAME_LDS_MAX") val = snk::TRACK_FRAME_LDS_MAX;
             else if (c == "TRACK_PPW_POINTS") val = snk::TRACK_PPW_POINTS;
+            else if (c == "TRACK_CHUNK_POINTS") val = snk::TRACK_CHUNK_POINTS;
+            else if (c == "TRACK_RESOLVE_LDS_FEATURES") val = snk::TRACK_RESOLVE_LDS_FEATURES;
+            else if (c == "GRID_MAX_FEATURES") val = snk::GRID_MAX_FEATURES;
+            else if (c == "GRID_COUNT_LDS_MAX") val = snk::GRID_COUNT_LDS_MAX;
             else if (c == "MATCHER_SCRATCH_BYTES") val = (int)snk::MATCHER_SCRATCH_BYTES;
             else if (c == "MATCHER_H_IN_BYTES") val = (int)snk::MATCHER_H_IN_BYTES;
             else if (c == "MATCHER_H_RES_BYTES") val = (int)snk::MATCHER_H_RES_BYTES;

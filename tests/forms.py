@@ -21,6 +21,9 @@ A row is (entry, shape, form).  entry names a function of dispatch.hpp, shape is
                 fields of run_part's plan line (a level: rows per band, "r" resize_kernel first, "t" tiny, "u" unaligned, "+" also
                 writes level l + 1, "-" no pixels)
   track_form    (pts_cap, batch, cap, ncell1, no_frame_lds, ppw_env)   a batched projection matcher
+  track_launch  (pts_cap, batch, cap, ncell1, no_frame_lds, frame_wgs, no_fused_resolve, ppw_env)   the whole plan of a batched projection
+                matcher, "form/workgroups per frame/resolution" as its plan line names them (tests/test_track_forms_gpu.py)
+  grid_form     (cap, ncell, network_env)                    the feature grid: counting form or bitonic network
 """
 import re
 import subprocess
@@ -28,6 +31,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 NT_MAX = (1 << 20) - 2  # documented maximum of the train set: the index field of the packed key holds 20 bits, all ones = "none"
+NCELL1 = 40 * 26 + 1    # cells + 1 of the 20-pixel grid over track_helpers.BOUNDS
 N_CU = 256              # compute units of an MI355X; no row below is within reach of the batch > 2 * n_cu rule except the one that names it
 
 # ---- bundle adjustment: a shape is BaShape's fields in this order, then `recording`, then the switches ("NAME=VALUE,..." without SNK_BA_)
@@ -199,6 +203,28 @@ FORMS = [
     ("track_form", (10000, 1024, 2259, 2401, 0, 0), "batch"),  # ... 147492 > 144 KB = 147456
     ("track_form", (512, 1024, 1000, 2401, 1, 0), "batch"),   # SNK_TRACK_NO_FRAME_LDS
     ("track_form", (512, 8, 1000, 2401, 0, 64), "frame"),     # SNK_TRACK_PPW=64
+    # ---- the whole plan, on the 40 x 26 grid of track_helpers.BOUNDS.  512 frames: the edge of 64 points per wavefront by size alone
+    ("track_launch", (1024, 512, 333, NCELL1, 0, 0, 0, 0), "frame/1/fused"),   # 524288 points, one chunk
+    ("track_launch", (1023, 512, 333, NCELL1, 0, 0, 0, 0), "batch/0/lds"),     # 523776 points: 63 per wavefront
+    ("track_launch", (2048, 512, 333, NCELL1, 0, 0, 0, 0), "frame/2/lds"),     # two chunks, two workgroups per frame: no fused resolution
+    # the LDS limits (SNK_TRACK_PPW=64, one workgroup per frame): frame + claims end at 147452 of 147456 bytes, frame alone at 147412
+    ("track_launch", (2049, 7, 2203, NCELL1, 0, 1, 0, 64), "frame/1/fused"),
+    ("track_launch", (2049, 7, 2204, NCELL1, 0, 1, 0, 64), "frame/1/lds"),
+    ("track_launch", (2049, 7, 2347, NCELL1, 0, 1, 0, 64), "frame/1/lds"),
+    ("track_launch", (2049, 7, 2348, NCELL1, 0, 1, 0, 64), "batch/0/lds"),
+    ("track_launch", (2049, 7, 2203, NCELL1, 0, 2, 0, 64), "frame/2/lds"),     # three chunks on two workgroups
+    # the separate resolution: claims in LDS up to 32768 features
+    ("track_launch", (1200, 3, 32768, NCELL1, 0, 0, 0, 0), "batch/0/lds"),
+    ("track_launch", (1200, 3, 32769, NCELL1, 0, 0, 0, 0), "batch/0/global"),
+    ("track_launch", (300, 4, 400, NCELL1, 0, 0, 0, 0), "batch/0/lds"),       # counts out of range in the default form of a small call
+    # ---- feature grid: the counting form while 2 (ncell + 1) + 2 cap ints fit 96 KB
+    ("grid_form", (11247, NCELL1 - 1, 0), "count"),   # 98304 bytes exactly
+    ("grid_form", (11248, NCELL1 - 1, 0), "network"),
+    ("grid_form", (16384, NCELL1 - 1, 0), "network"),  # the documented maximum
+    ("grid_form", (287, 12000, 0), "count"),          # 120 x 100 cells
+    ("grid_form", (288, 12000, 0), "network"),
+    ("grid_form", (400, 65532, 0), "network"),        # 254 x 258 cells: the largest grid but two
+    ("grid_form", (1100, NCELL1 - 1, 1), "network"),  # SNK_GRID_NETWORK (tests/test_zx_frontend_variants_gpu.py)
 ]
 
 # the values of the enums of dispatch.hpp (the CPU test reads the header and compares)
@@ -213,12 +239,13 @@ ENUMS = {"Knn2Form": ["vector1", "vector4", "mfma"], "StereoForm": ["frame", "co
          "OrbBandForm": ["bh64", "bh22", "bh8"], "OrbFastForm": ["single0", "single3", "single4", "loop0", "loop3", "loop4"],
          "OrbHarrisForm": ["none", "per_cell", "dense"], "OrbDistForm": ["one_full", "one_small", "small_drain"],
          "OrbDescForm": ["registers", "blur_in", "dma", "dma_tiled"], "OrbSchedule": ["one_chain", "chains", "staggered"],
-         "TrackForm": ["frame", "batch"]}
+         "TrackForm": ["frame", "batch"], "TrackResolve": ["fused", "lds", "global"], "GridForm": ["count", "network"]}
 # the enum of an entry's form; an entry whose form is "a/b/..." names one enum per part
 ENUM_OF = {"knn2": "Knn2Form", "stereo_host": "StereoForm", "stereo_batch": "StereoForm", "pose_host": "PoseForm", "pose_batch": "PoseForm",
            "ba_lm": ("BaLinForm", "BaCamForm", "BaSchurForm", "BaPcgForm", "BaUpdateForm"),
            "orb_band": "OrbBandForm", "orb_fast": "OrbFastForm", "orb_harris": "OrbHarrisForm", "orb_dist": "OrbDistForm", "orb_desc": "OrbDescForm",
-           "orb_sched": "OrbSchedule", "orb_plan": (None, None, "OrbHarrisForm", "OrbDistForm", "OrbDescForm"), "track_form": "TrackForm"}
+           "orb_sched": "OrbSchedule", "orb_plan": (None, None, "OrbHarrisForm", "OrbDistForm", "OrbDescForm"), "track_form": "TrackForm",
+           "track_launch": ("TrackForm", None, "TrackResolve"), "grid_form": "GridForm"}
 # forms that no shape selects (test_match_forms_gpu.py / test_pose_forms_gpu.py run each once in a child process under its switch;
 # the BA forms: the rows of tests/test_zy_ba_variants_gpu.py)
 ENV_ONLY = {("PoseForm", "wave4_global"), ("StereoForm", "sort16"),
@@ -233,7 +260,8 @@ def parts(entry, form):
     enums = ENUM_OF[entry]
     if isinstance(enums, str):
         return [(enums, form)]
-    # "a/b/..." names one enum per part; the extractor's "levels;cpw/quads;a;b;c" has two parts that are no enum (None)
+    # "a/b/..." names one enum per part; the extractor's "levels;cpw/quads;a;b;c" has two parts that are no enum (None), and so has the
+    # workgroup count of "form/wgs/resolve"
     return [(e, v) for e, v in zip(enums, form.split(";" if entry == "orb_plan" else "/"), strict=True) if e is not None]
 
 
@@ -276,6 +304,32 @@ def orb_plan_lines(stderr):
     return out
 
 
+TRACK_LAUNCH_FIELDS = ("pts_cap", "batch", "cap", "ncell1")
+
+
+def track_plan_lines(stderr):
+    """The plan lines of the batched projection matchers under SNK_DEBUG ("snake_hip: track plan entry=... resolve=..."), each as
+    (entry, (pts_cap, batch, cap, ncell1), ppw, "form/wgs/resolve")."""
+    out = []
+    for ln in stderr.splitlines():
+        if not ln.startswith("snake_hip: track plan "):
+            continue
+        kv = dict(re.findall(r"(\w+)=(\S+)", ln))
+        out.append((kv["entry"], tuple(int(kv[f]) for f in TRACK_LAUNCH_FIELDS), int(kv["ppw"]), "/".join(kv[k] for k in ("form", "wgs", "resolve"))))
+    return out
+
+
+def grid_plan_lines(stderr):
+    """The plan lines of the feature grid under SNK_DEBUG ("snake_hip: grid plan cap=... form=..."), each as ((cap, ncell), batch, form)."""
+    out = []
+    for ln in stderr.splitlines():
+        if not ln.startswith("snake_hip: grid plan "):
+            continue
+        kv = dict(re.findall(r"(\w+)=(\S+)", ln))
+        out.append(((int(kv["cap"]), int(kv["ncell"])), int(kv["batch"]), kv["form"]))
+    return out
+
+
 def shapes(entry, form):
     """Every shape of the table that `entry` maps to `form`, in table order."""
     return [s for e, s, f in FORMS if e == entry and f == form]
@@ -285,6 +339,24 @@ def shape(entry, wanted, form):
     """`wanted` if the table pins it to `form` -- the GPU tests pass every launch shape through here."""
     assert (entry, tuple(wanted), form) in FORMS, f"{entry}{tuple(wanted)} -> {form} is not a row of tests/forms.py"
     return tuple(wanted)
+
+
+def track_plan_edges(exe, pts_cap, batch, ncell1, frame_wgs, ppw_env, caps=range(1, 4001)):
+    """(last capacity with the fused resolution, last capacity of the frame form) of a batched matcher's plan, found by asking the
+    driver for every capacity of `caps`; each form must hold one unbroken range of capacities."""
+    plans = ask(exe, [("track_launch", (pts_cap, batch, c, ncell1, 0, frame_wgs, 0, ppw_env)) for c in caps])
+    kinds = [("fused" if p.endswith("/fused") else p.split("/")[0]) for p in plans]
+    n_fused, n_frame = kinds.count("fused"), kinds.count("frame")
+    assert kinds == ["fused"] * n_fused + ["frame"] * n_frame + ["batch"] * (len(kinds) - n_fused - n_frame) and n_fused and n_frame and kinds[-1] == "batch"
+    return caps[n_fused - 1], caps[n_fused + n_frame - 1]
+
+
+def grid_form_edge(exe, ncell, caps=range(1, 16385)):
+    """The last capacity at which a grid of ncell cells takes the counting form."""
+    got = ask(exe, [("grid_form", (c, ncell, 0)) for c in caps])
+    n = got.count("count")
+    assert got == ["count"] * n + ["network"] * (len(got) - n) and 0 < n < len(got)
+    return caps[n - 1]
 
 
 def build_driver(directory):

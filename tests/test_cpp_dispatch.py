@@ -10,7 +10,7 @@ from forms import ENUM_OF, ENUMS, ENV_ONLY, FORMS
 
 SWITCH_ARGS = {"knn2": [3], "stereo_host": [1], "stereo_batch": [2, 3], "pose_host": [2], "pose_batch": [3, 4],
                "ba_lm": [len(forms.BA_FIELDS)], "orb_band": [3], "orb_fast": [], "orb_harris": [2], "orb_dist": [], "orb_desc": [0], "orb_sched": [4],
-               "orb_plan": [len(forms.ORB_FIELDS)], "track_form": [4, 5]}  # environment switches in a shape
+               "orb_plan": [len(forms.ORB_FIELDS)], "track_form": [4, 5], "track_launch": [4, 5, 6, 7], "grid_form": [2]}  # environment switches in a shape
 
 
 @pytest.fixture(scope="module")
@@ -316,6 +316,39 @@ def test_track_thresholds_from_both_sides(driver):
     assert plan(10000, 1024, 1000, 2401, 0, 4, 0, 0) == [64, 4, -1, fl]        # SNK_TRACK_FRAME_WGS
     assert plan(10000, 1024, 1000, 2401, 1, 0, 0, 0) == [64, 0, -1, 0]         # SNK_TRACK_NO_FRAME_LDS: coarse_batch_kernel / fine_batch_kernel
     assert plan(100, 8, 1000, 2401, 0, 0, 0, 0) == [1, 0, -1, 0]
+
+
+def test_track_launch_and_grid_thresholds_from_both_sides(driver):
+    """The resolution of a batched matcher and the form of the feature grid: both neighbours of every threshold, and the capacities at
+    which the plan of the 40 x 26 grid changes, found by asking for every capacity (tests/test_track_forms_gpu.py runs there)."""
+    ask = lambda *q: forms.ask(driver, list(q))
+    names = ["TRACK_RESOLVE_LDS_FEATURES", "TRACK_CHUNK_POINTS", "GRID_MAX_FEATURES", "GRID_COUNT_LDS_MAX"]
+    assert dict(zip(names, map(int, ask(*[("const", (n,)) for n in names])))) == \
+        {"TRACK_RESOLVE_LDS_FEATURES": 32768, "TRACK_CHUNK_POINTS": 1024, "GRID_MAX_FEATURES": 16384, "GRID_COUNT_LDS_MAX": 96 * 1024}
+    assert ask(("track_resolve_lds", (32768,)), ("track_resolve_lds", (32769,)), ("track_resolve_lds", (1,)), ("track_resolve_lds", ((1 << 20) - 2,))) == \
+        ["1", "0", "1", "0"]
+    N1 = forms.NCELL1
+    launch = lambda *a: ask(("track_launch", a))[0]
+    # fused only with one workgroup per frame and the claims behind the frame; the separate resolution by the capacity alone
+    assert launch(10000, 1024, 1000, 2401, 0, 0, 0, 0) == "frame/1/fused" and launch(10000, 1024, 1000, 2401, 0, 0, 1, 0) == "frame/1/lds"
+    assert launch(10000, 512, 1000, 2401, 0, 0, 0, 0) == "frame/2/lds" and launch(10000, 1024, 1000, 2401, 1, 0, 0, 0) == "batch/0/lds"
+    assert launch(100, 8, 32768, N1, 0, 0, 0, 64) == "batch/0/lds" and launch(100, 8, 32769, N1, 0, 0, 0, 64) == "batch/0/global"
+    assert launch(2049, 7, 2203, N1, 0, 0, 0, 64) == "frame/3/lds"   # seven frames: a workgroup per chunk unless SNK_TRACK_FRAME_WGS says otherwise
+    fused_end, frame_end = forms.track_plan_edges(driver, 2049, 7, N1, 1, 64)
+    assert (fused_end, frame_end) == (2203, 2347)
+    up = lambda v: (v + 15) & ~15
+    assert up(frame_lds(2203, N1)) + 4 * 2203 == 147452 and up(frame_lds(2204, N1)) + 4 * 2204 == 147504 > 144 * 1024
+    assert frame_lds(2347, N1) == 147412 and frame_lds(2348, N1) == 147460 > 144 * 1024
+    # the grid: 2 (ncell + 1) + 2 cap ints in 96 KB; SNK_GRID_NETWORK
+    lds = lambda n, c: int(ask(("grid_lds", (n, c)))[0])
+    assert lds(11247, 1040) == 96 * 1024 and lds(11248, 1040) == 96 * 1024 + 8 and lds(0, 0) == 8 and lds(16384, 65534) == (2 * 65535 + 2 * 16384) * 4
+    assert ask(("grid_form", (11247, 1040, 0)), ("grid_form", (11248, 1040, 0)), ("grid_form", (11247, 1040, 1)), ("grid_form", (1, 12286, 0)),
+               ("grid_form", (1, 12287, 0)), ("grid_form", (0, 12287, 0)), ("grid_form", (16384, 1, 0)), ("grid_form", (1, 65534, 0))) == \
+        ["count", "network", "network", "count", "network", "count", "network", "network"]
+    assert forms.grid_form_edge(driver, 1040) == 11247 and forms.grid_form_edge(driver, 12000) == 287
+    # no copy of a threshold is left in track.hip's code (its messages and comments may name the numbers)
+    track = re.sub(r'"[^"\n]*"|//[^\n]*', "", (forms.ROOT / "snake_slam_amd" / "csrc" / "track.hip").read_text())
+    assert not re.search(r"\b(32768|16384|96 \* 1024|98304)\b", track) and "grid_form(" in track and "track_resolve_in_lds(" in track
 
 
 def test_orb_and_track_switch_lists_agree():

@@ -551,3 +551,194 @@ def brute_relink(frame, cam, pose, qs, radius=0.8, outlier_threshold=2.1, featur
         if bi >= 0:
             action[n], best[n] = 2, bi
     return action, best
+
+
+# ---- the batched, device-resident chain coarse -> mark taken -> fine (read-only, then in place) ----
+def make_tracking_case_exact(orc, seed, target, m_pts, **kw):
+    """make_tracking_case with exactly `target` features.  The point features are drawn before the clutter, so a first run without
+    clutter counts them and a second one from the same seed adds the difference."""
+    probe = make_tracking_case(orc, np.random.default_rng(seed), n_clutter=0, m_pts=m_pts, **kw)
+    n_point_features = len(probe[0]["kps"])
+    assert n_point_features <= target, (n_point_features, target)
+    case = make_tracking_case(orc, np.random.default_rng(seed), n_clutter=target - n_point_features, m_pts=m_pts, **kw)
+    assert len(case[0]["kps"]) == target
+    return case
+
+
+def keep_features(orc, frame, keep):
+    """The frame with only the features `keep` (indices in grid order): a subset of a grid-ordered frame is grid-ordered, the cell
+    ranges come from the oracle's grid of the kept keypoints."""
+    keep = np.sort(np.asarray(keep, np.int64))
+    kps = frame["kps"][keep]
+    perm, cell_start, _, _ = orc.feature_grid(kps, frame["bounds"])
+    assert np.array_equal(perm, np.arange(len(keep)))
+    return dict(frame, kps=kps, desc=frame["desc"][keep], right_points=frame["right_points"][keep], taken=frame["taken"][keep], cell_start=cell_start)
+
+
+def thin_to(orc, rng, frame, target):
+    """`target` randomly chosen features of a frame that has at least that many."""
+    n = len(frame["kps"])
+    assert n >= target
+    out = keep_features(orc, frame, rng.permutation(n)[:target])
+    assert len(out["kps"]) == target
+    return out
+
+
+def mark(frame, widx):
+    """The frame after `mvpMapPoints[idx] = mp` for the matches widx."""
+    f2 = dict(frame)
+    f2["taken"] = frame["taken"].copy()
+    f2["taken"][widx[widx >= 0]] = 1
+    return f2
+
+
+CONFLICT_OFFSETS = (1, 64, 1024, 2048)  # same wavefront, another wavefront of the chunk, the next chunk (and workgroup), the one after
+
+
+def add_conflicts(orc, frame, cam, pose, ls, coarse, fine, per_offset=24, th_c=15.0, fe=75, th_f=5.0, ratio=0.8):
+    """Copies of points that the oracle matches, written over the records at fixed distances behind the original: both want the same
+    feature, the original (lower index) must get it and the copy -1.  coarse / fine: records of the same points, changed in place.
+    Returns [(original, copy, offset)]."""
+    m = len(coarse)
+    assert len(fine) == m
+    if m < 2:
+        return []
+    _, cidx = orc.match_coarse(frame, cam, pose, coarse, th_c, fe, 0, ls)
+    _, fidx, _, _ = orc.match_fine(mark(frame, cidx), cam, pose, fine, th_f, ratio, ls)
+    matched = [int(i) for i in np.nonzero((cidx >= 0) | (fidx >= 0))[0] if i >= m // 20]  # the first m // 20 points lie behind the camera
+    used, pairs = set(), []
+    for off in CONFLICT_OFFSETS[::-1]:  # the far offsets have the fewest candidates: they choose first
+        n = 0
+        for i in matched:
+            j = i + off
+            if n == per_offset or j >= m:
+                break
+            if i in used or j in used:
+                continue
+            coarse[j], fine[j] = coarse[i], fine[i]
+            used.update((i, j))
+            pairs.append((i, j, off))
+            n += 1
+    return pairs
+
+
+def lost_copies(pairs, cidx, fidx):
+    """The pairs of add_conflicts whose original the oracle matched and whose copy it left unmatched, in the coarse or in the fine call."""
+    return [(i, j, off) for i, j, off in pairs if (cidx[i] >= 0 and cidx[j] == -1) or (fidx[i] >= 0 and fidx[j] == -1)]
+
+
+def pack_frames_dev(frames, cap, n_override=None):
+    """Host frame dicts (grid order) -> padded device tensors of the batched, device-resident view."""
+    import torch
+
+    from snake_slam_amd.tracking import KP64_DTYPE
+
+    B = len(frames)
+    ncell = frames[0]["cols"] * frames[0]["rows"] + 1
+    kps = np.zeros((B, cap), KP64_DTYPE)
+    desc = np.zeros((B, cap, 4), np.uint64)
+    rp = np.full((B, cap), -1.0, np.float32)
+    taken = np.zeros((B, cap), np.uint8)
+    cs = np.zeros((B, ncell), np.int32)
+    n = np.zeros(B, np.int32)
+    for b, f in enumerate(frames):
+        k = len(f["kps"])
+        n[b] = k
+        kps[b, :k], desc[b, :k], rp[b, :k], taken[b, :k], cs[b] = f["kps"], f["desc"], f["right_points"], f["taken"], f["cell_start"]
+    if n_override is not None:
+        n = np.asarray(n_override, np.int32)
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[0], -1)).to(dev)
+    return dict(n=torch.from_numpy(n).to(dev), kps=t(kps).view(B, cap, 24), desc=torch.from_numpy(desc.view(np.int64)).to(dev),
+                right_points=torch.from_numpy(rp).to(dev), taken=torch.from_numpy(taken).to(dev), cell_start=torch.from_numpy(cs).to(dev))
+
+
+GUARD_I32, GUARD_U8 = -0x5A5A5A5B, 0xA5  # the pattern of the guard rows around the outputs
+
+
+def run_chain_dev(matcher, frames, cam, poses, ls, coarse, fine, cap, mc_cap, mf_cap, tile=1, n_feat=None, n_coarse=None, n_fine=None,
+                  guards=False, expect_cleared=True):
+    """coarse -> `mvpMapPoints[idx] = mp` on the device -> fine (read-only form, then in place) for the frames tiled `tile` times (row
+    t * B + b is frame b).  n_feat / n_coarse / n_fine replace the counts the device reads (the arrays stay as the inputs fill them).
+    guards: match_idx, visible and n_matches are views into larger tensors with a row (an element) of a known pattern before and
+    after; the result then holds `guards_intact`.  Returns host arrays."""
+    import torch
+
+    from snake_slam_amd.tracking import LM_COARSE_DTYPE, LM_FINE_DTYPE, frames_dev
+
+    B = len(frames)
+    pc = np.zeros((B, mc_cap), LM_COARSE_DTYPE)
+    pf = np.zeros((B, mf_cap), LM_FINE_DTYPE)
+    nc, nf = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for b in range(B):
+        nc[b], nf[b] = len(coarse[b]), len(fine[b])
+        pc[b, : nc[b]], pf[b, : nf[b]] = coarse[b], fine[b]
+    if n_coarse is not None:
+        nc = np.asarray(n_coarse, np.int32)
+    if n_fine is not None:
+        nf = np.asarray(n_fine, np.int32)
+    dev = torch.device("cuda", 0)
+    rep = lambda t: t.repeat((tile,) + (1,) * (t.dim() - 1)).contiguous() if tile > 1 else t
+    D = {k: rep(v) for k, v in pack_frames_dev(frames, cap, n_feat).items()}
+    BT = B * tile
+    poses = rep(torch.from_numpy(np.stack(poses)).to(dev))
+    d_pc = rep(torch.from_numpy(pc.view(np.uint8).reshape(B, mc_cap, 88)).to(dev))
+    d_pf = rep(torch.from_numpy(pf.view(np.uint8).reshape(B, mf_cap, 96)).to(dev))
+    d_nc, d_nf = rep(torch.from_numpy(nc).to(dev)), rep(torch.from_numpy(nf).to(dev))
+    g = 1 if guards else 0
+    whole = []
+
+    def out(shape1, dtype, fill, pattern):
+        t = torch.full((BT + 2 * g,) + shape1, pattern, dtype=dtype, device=dev)
+        whole.append((t, pattern))
+        v = t[g: g + BT]
+        v.fill_(fill)
+        return v
+
+    mi_c, mi_f, mi_r = (out((m,), torch.int32, -7, GUARD_I32) for m in (mc_cap, mf_cap, mf_cap))
+    vis, vis_r = (out((mf_cap,), torch.uint8, 9, GUARD_U8) for _ in range(2))
+    n_c, n_f, n_r = (out((), torch.int32, 0, GUARD_I32) for _ in range(3))
+    fd = frames_dev(BOUNDS, D["n"], D["kps"], D["desc"], D["right_points"], D["taken"], D["cell_start"])
+    torch.cuda.synchronize()
+    matcher.coarse_batch_dev(fd, cam, poses, d_pc, d_nc, 15.0, 75, 0, ls, mi_c, n_c)
+    matcher.mark_taken_batch_dev(mi_c, d_nc, D["taken"])
+    # the read-only form first (snk_match_project_fine_batch_ro_dev): same matches, the records untouched
+    pf_before = d_pf.clone()
+    matcher.fine_batch_dev(fd, cam, poses, d_pf, d_nf, 5.0, 0.8, ls, mi_r, vis_r, n_r, write_valid=False)
+    matcher.sync()
+    assert torch.equal(d_pf, pf_before)
+    matcher.fine_batch_dev(fd, cam, poses, d_pf, d_nf, 5.0, 0.8, ls, mi_f, vis, n_f)
+    matcher.sync()
+    assert torch.equal(mi_r, mi_f) and torch.equal(vis_r, vis) and torch.equal(n_r, n_f)
+    if expect_cleared:
+        assert not torch.equal(d_pf, pf_before)  # the in-place form did clear flags
+    res = dict(mi_c=mi_c, mi_f=mi_f, vis=vis, n_c=n_c, n_f=n_f, taken=D["taken"])
+    res = {k: v.cpu().numpy() for k, v in res.items()}
+    res["pf"] = d_pf.cpu().numpy().view(LM_FINE_DTYPE).reshape(BT, mf_cap)
+    if guards:
+        res["guards_intact"] = all(bool((t[0] == p).all()) and bool((t[-1] == p).all()) for t, p in whole)
+    return res
+
+
+def check_chain(orc, res, frames, cam, poses, ls, coarse, fine, tile=1):
+    """The results of run_chain_dev against the oracle, frame by frame (every tile of a frame against the one reference); the sum of the
+    distinct frames' match counts, and the oracle's (coarse, fine) indices per frame."""
+    B = len(frames)
+    mi_c, mi_f, vis, n_c, n_f, taken_after, pf_after = (res[k] for k in ("mi_c", "mi_f", "vis", "n_c", "n_f", "taken", "pf"))
+    total, want = 0, []
+    for b, (frame, pose) in enumerate(zip(frames, poses)):
+        nc, nf = len(coarse[b]), len(fine[b])
+        wn, widx = orc.match_coarse(frame, cam, pose, coarse[b], 15.0, 75, 0, ls) if nc else (0, np.zeros(0, np.int32))
+        f2 = mark(frame, widx)
+        wn2, widx2, wvis, wvalid = orc.match_fine(f2, cam, pose, fine[b], 5.0, 0.8, ls) if nf else (0, np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0, np.uint8))
+        assert np.array_equal(np.asarray(wvis) != 0, np.asarray(wvalid) != 0), b  # what the read-only form relies on: valid after = visible
+        for r in range(b, B * tile, B):
+            assert n_c[r] == wn and np.array_equal(mi_c[r, :nc], widx), r
+            assert (mi_c[r, nc:] == -1).all()
+            assert np.array_equal(taken_after[r, : len(frame["kps"])], f2["taken"]), r
+            assert n_f[r] == wn2 and np.array_equal(mi_f[r, :nf], widx2), r
+            assert (mi_f[r, nf:] == -1).all()
+            assert np.array_equal(vis[r, :nf], wvis) and np.array_equal(pf_after[r, :nf]["valid"], wvalid), r
+        total += int(wn) + int(wn2)
+        want.append((widx, widx2))
+    return total, want
