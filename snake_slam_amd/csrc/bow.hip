@@ -84,13 +84,6 @@ __device__ __forceinline__ u32 wave_min_u32(u32 v)
     return v;
 }
 
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // transform
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -359,7 +352,7 @@ __global__ __launch_bounds__(256) void bow_db_score_kernel(DbRows D, DbQuery Qy)
             }
         }
     }
-    common = wave_sum_i32(common);
+    common = wave_sum_xor(common);
     sum    = wave_sum64_dpp(sum);
     if (lane == 0)
     {
@@ -600,11 +593,6 @@ __global__ __launch_bounds__(256) void bow_match_kernel(MatchSide A, MatchSide B
 // ------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------------
-size_t align16(size_t v)
-{
-    return (v + 15) & ~(size_t)15;
-}
-
 int transform_launch(snk_bow_vocab* v, const u64* desc, const int* n_dev, int batch, int cap, int levelsup, BowOut O, int* word_of, int* node_of)
 {
     hipLaunchKernelGGL(bow_descent_kernel, dim3(ceil_div(cap, 16), batch), dim3(256), 0, v->stream, v->T, desc, n_dev, cap, levelsup, word_of,

@@ -231,6 +231,36 @@ __device__ __forceinline__ int wave_scan_incl_dpp(int x)
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
     return x;
 }
+// Sum of one int per lane over the wavefront, returned to every lane: the __shfl_xor butterfly (orb.hip has a DPP wave_sum of its own)
+__device__ __forceinline__ int wave_sum_xor(int v)
+{
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+// Exclusive prefix sum of one int per lane over a workgroup of THREADS lanes, and the total.  Called by all THREADS lanes together.
+// s_part: 2 * (THREADS / 64) words of LDS; pass: the caller's count of scans, 0 at first, the same in every lane.  Two banks of
+// partial sums and ONE barrier: a bank is written again two scans later, behind the barrier of the scan between.
+template <int THREADS>
+__device__ __forceinline__ int block_scan(int v, int& total, unsigned* s_part, int& pass)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int incl = wave_scan_incl_dpp(v);
+    unsigned* part = s_part + (pass & 1) * (THREADS / 64);
+    pass += 1;
+    if (lane == 63) part[wave] = (unsigned)incl;
+    __syncthreads();
+    int before = 0;
+    total      = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w)
+    {
+        const int p = (int)part[w];
+        before += w < wave ? p : 0;
+        total += p;
+    }
+    return before + incl - v;
+}
 // Sum over the 64 lanes of a double, returned to every lane, without the LDS: four DPP butterflies inside each row of 16 lanes
 // (two 32-bit moves per step), then the four row sums are read back with v_readlane and added in a fixed order.  The
 // __shfl_xor tree above is twelve dependent ds_bpermute round trips per sum.

@@ -58,13 +58,6 @@ struct CovisCall
 // words of s_misc
 enum { W_BAD = 0, W_QUEUED = 1, W_TOUCHED = 2, W_FOUND = 3, W_SLOT = 4, W_MAXKEY = 6, W_PART = 8 };
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
 template <bool GATE, bool SELF_EXCLUDED, bool BAD_FILTER, bool THRESHOLD>
 __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
 {
@@ -167,8 +160,8 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
             if (listable && n >= min_count) found += 1;
             else s_cnt[k] = 0;
         }
-        touched = wave_sum(touched);
-        found   = wave_sum(found);
+        touched = wave_sum_xor(touched);
+        found   = wave_sum_xor(found);
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1)
         {
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
                     const u32 w = s_cnt[k];
                     n += w > 0 && covis_key(w, (u32)k) >= T ? 1 : 0;
                 }
-                n = wave_sum(n);
+                n = wave_sum_xor(n);
                 // two banks of partial sums: a bank is written again two passes later, behind the barrier of the pass between
                 u32* part = s_misc + W_PART + (pass & 1) * (COVIS_THREADS / 64);
                 if (lane == 0) part[wave] = (u32)n;
@@ -265,11 +258,6 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
     if (tid == 0) c.out[set] = CovisResult{n_found, n_conn, (int)s_ids[n_conn - 1], COVIS_OK};
 }
 
-size_t align16(size_t x)
-{
-    return (x + 15) & ~(size_t)15;
-}
-
 int long_env()
 {
     // SNK_COVIS_LONG_MIN=<n> (tests, A/B): read once
@@ -300,8 +288,8 @@ int check_scalars(const snk_covis_map* map, const snk_covis_params* params)
 // the host's look at the map: everything the kernel would otherwise have to refuse
 int check_map(const snk_covis_map* map)
 {
-    SNK_REQUIRE(map->obs_start[0] == 0, "covisibility: obs_start[0] must be 0");
-    for (int p = 0; p < map->n_points; ++p) SNK_REQUIRE(map->obs_start[p + 1] >= map->obs_start[p], "covisibility: obs_start must be non-decreasing");
+    int rc;
+    if ((rc = check_starts(map->obs_start, map->n_points, "covisibility: obs_start[0] must be 0", "covisibility: obs_start must be non-decreasing")) != SNK_OK) return rc;
     SNK_REQUIRE(map->obs_start[map->n_points] == map->n_obs, "covisibility: obs_start[n_points] must be n_obs");
     for (int o = 0; o < map->n_obs; ++o) SNK_REQUIRE(map->obs[o][0] >= 0 && map->obs[o][0] < map->n_kf, "covisibility: an observation's keyframe outside [0, n_kf)");
     return SNK_OK;
@@ -309,8 +297,8 @@ int check_map(const snk_covis_map* map)
 
 int check_items(const int32_t* start, int n_starts, const int32_t* point, int n_points)
 {
-    SNK_REQUIRE(start[0] == 0, "covisibility: a start array must begin at 0");
-    for (int s = 0; s < n_starts; ++s) SNK_REQUIRE(start[s + 1] >= start[s], "covisibility: a start array must be non-decreasing");
+    int rc;
+    if ((rc = check_starts(start, n_starts, "covisibility: a start array must begin at 0", "covisibility: a start array must be non-decreasing")) != SNK_OK) return rc;
     SNK_REQUIRE(start[n_starts] == 0 || point != nullptr, "covisibility: NULL point array with entries");
     for (int i = 0; i < start[n_starts]; ++i) SNK_REQUIRE(point[i] >= -1 && point[i] < n_points, "covisibility: a point id outside [-1, n_points)");
     return SNK_OK;
@@ -355,45 +343,34 @@ int run_host(snk_matcher* m, const snk_covis_map* map, const snk_covis_params* p
 {
     const size_t n_kf = (size_t)map->n_kf, n_pts = (size_t)map->n_points, n_obs = (size_t)map->n_obs, n_items = (size_t)start[n_starts],
                  ns = (size_t)n_sets, cap = (size_t)params->cap;
-    // one upload: kf_bad | pt_flags | obs_start | obs | start | point | depth | q
-    const size_t o_flags = align16(n_kf), o_ostart = o_flags + align16(n_pts), o_obs = o_ostart + align16((n_pts + 1) * 4), o_start = o_obs + align16(n_obs * 8),
-                 o_point = o_start + align16(((size_t)n_starts + 1) * 4), o_depth = o_point + align16(n_items * 4),
-                 o_q = o_depth + align16(CONN ? n_items * 4 : 0), bytes = o_q + align16(CONN ? ns * 4 : 0);
-    const size_t o_res = align16(ns * cap * sizeof(CovisConn)), out_bytes = o_res + ns * sizeof(CovisResult);
+    // one upload (stage.hpp): kf_bad | pt_flags | obs_start | obs | start | point | depth | q, the last two empty in the vote
+    Block in, out_b;
+    const int i_bad = in.add(map->kf_bad, n_kf), i_flags = in.add(map->pt_flags, n_pts), i_ostart = in.add(map->obs_start, (n_pts + 1) * 4),
+              i_obs = in.add(map->obs, n_obs * 8), i_start = in.add(start, ((size_t)n_starts + 1) * 4), i_point = in.add(point, n_items * 4),
+              i_depth = in.add(depth, CONN ? n_items * 4 : 0), i_q = in.add(q, CONN ? ns * 4 : 0);
+    const int o_conn = out_b.add(nullptr, ns * cap * sizeof(CovisConn)), o_res = out_b.add(nullptr, ns * sizeof(CovisResult));
     int rc;
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_bytes)) != SNK_OK) return rc;
-    char *host = m->h_in.as<char>(), *dev = m->q.as<char>();
-    if (n_kf) memcpy(host, map->kf_bad, n_kf);
-    if (n_pts) memcpy(host + o_flags, map->pt_flags, n_pts);
-    memcpy(host + o_ostart, map->obs_start, (n_pts + 1) * 4);
-    if (n_obs) memcpy(host + o_obs, map->obs, n_obs * 8);
-    memcpy(host + o_start, start, ((size_t)n_starts + 1) * 4);
-    if (n_items) memcpy(host + o_point, point, n_items * 4);
-    if (CONN && n_items) memcpy(host + o_depth, depth, n_items * 4);
-    if (CONN) memcpy(host + o_q, q, ns * 4);
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_reserve(m, in.bytes, out_b.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char *dev = m->q.as<char>(), *dout = m->out.as<char>(), *res = m->h_res.as<char>();
     CovisCall C  = make_call(map, params, n_sets, (int)n_items);
-    C.kf_bad     = reinterpret_cast<const u8*>(dev);
-    C.pt_flags   = reinterpret_cast<const u8*>(dev + o_flags);
-    C.obs_start  = reinterpret_cast<const int*>(dev + o_ostart);
-    C.obs        = reinterpret_cast<const int2*>(dev + o_obs);
-    C.item_start = reinterpret_cast<const int*>(dev + o_start);
-    C.item_point = reinterpret_cast<const int*>(dev + o_point);
-    C.item_depth = CONN ? reinterpret_cast<const float*>(dev + o_depth) : nullptr;
-    C.q          = CONN ? reinterpret_cast<const int*>(dev + o_q) : nullptr;
-    C.conn       = m->out.as<CovisConn>();
-    C.out        = reinterpret_cast<CovisResult*>(m->out.as<char>() + o_res);
+    C.kf_bad     = in.at<const u8>(dev, i_bad);
+    C.pt_flags   = in.at<const u8>(dev, i_flags);
+    C.obs_start  = in.at<const int>(dev, i_ostart);
+    C.obs        = in.at<const int2>(dev, i_obs);
+    C.item_start = in.at<const int>(dev, i_start);
+    C.item_point = in.at<const int>(dev, i_point);
+    C.item_depth = CONN ? in.at<const float>(dev, i_depth) : nullptr;
+    C.q          = CONN ? in.at<const int>(dev, i_q) : nullptr;
+    C.conn       = out_b.at<CovisConn>(dout, o_conn);
+    C.out        = out_b.at<CovisResult>(dout, o_res);
     if ((rc = launch<CONN>(m, C)) != SNK_OK) return rc;
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, m->out.p, out_bytes, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const char* res = m->h_res.as<char>();
-    memcpy(out, res + o_res, ns * sizeof(CovisResult));
+    if ((rc = stage_download(m, 0, out_b.end())) != SNK_OK) return rc;
+    memcpy(out, out_b.at<char>(res, o_res), ns * sizeof(CovisResult));
+    const CovisConn* lists = out_b.at<const CovisConn>(res, o_conn);
     for (size_t s = 0; s < ns; ++s)
-        if (out[s].n_conn > 0) memcpy(conn + s * cap, res + s * cap * sizeof(CovisConn), (size_t)out[s].n_conn * sizeof(CovisConn));
+        if (out[s].n_conn > 0) memcpy(conn + s * cap, lists + s * cap, (size_t)out[s].n_conn * sizeof(CovisConn));
     return SNK_OK;
 }
 }  // namespace

@@ -26,8 +26,9 @@
 // Emit: chunk by chunk in order, a candidate finds its slot again and wins iff the slot holds its order; winners are ranked by the
 // scan and write their 96-byte record (twelve 8-byte words) and their id.  No result depends on the order in which atomics land: the
 // table's contents as a set (id -> minimum order, flag) do not, and nothing else is read from it.
+//
+// The host entries lay the arrays of a call out as one block, inputs and outputs alike: stage.hpp, and matcher_handle.hpp for the copies.
 #include <cstddef>
-#include <vector>
 
 #include "matcher_handle.hpp"
 
@@ -101,35 +102,6 @@ struct GatherCall
     LmapGatherResult* out;
 };
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
-// Exclusive prefix sum of one int per lane over the workgroup, and the total.  Called by all 256 lanes.  Two banks of partial sums: a
-// bank is written again two scans later, behind the barrier of the scan between.
-__device__ __forceinline__ int block_scan(int v, int& total, u32* s_part, int& pass)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_scan_incl_dpp(v);
-    u32* part      = s_part + (pass & 1) * (LMAP_THREADS / 64);
-    pass += 1;
-    if (lane == 63) part[wave] = (u32)incl;
-    __syncthreads();
-    int before = 0;
-    total      = 0;
-#pragma unroll
-    for (int w = 0; w < LMAP_THREADS / 64; ++w)
-    {
-        const int p = (int)part[w];
-        before += w < wave ? p : 0;
-        total += p;
-    }
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(LMAP_THREADS) void lmap_select_kernel(SelectCall c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -197,7 +169,7 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_select_kernel(SelectCall c)
         const bool in  = j < R;
         const bool acc = in && lmap_accept(lmap_draw(key, (u32)j), c.n_direct_prob, R);
         int total;
-        const int ex = block_scan(in ? (acc ? 1 : 0x10000) : 0, total, s_misc + W_PART, pass);
+        const int ex = block_scan<LMAP_THREADS>(in ? (acc ? 1 : 0x10000) : 0, total, s_misc + W_PART, pass);
         if (acc)
         {
             const int pos = nd + n_acc + (ex & 0xFFFF);
@@ -284,9 +256,9 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_select_kernel(SelectCall c)
         const int j    = base + tid;
         const bool rej = j < R && !lmap_accept(lmap_draw(key, (u32)j), c.n_direct_prob, R);
         int total, total2;
-        const int ji    = j_base + block_scan(rej ? 1 : 0, total, s_misc + W_PART, pass);
+        const int ji    = j_base + block_scan<LMAP_THREADS>(rej ? 1 : 0, total, s_misc + W_PART, pass);
         const bool acc2 = rej && lmap_accept(lmap_draw(key, (u32)(R + ji)), c.n_indirect_prob, n_ind);
-        const int pos   = n_loc + block_scan(acc2 ? 1 : 0, total2, s_misc + W_PART, pass);
+        const int pos   = n_loc + block_scan<LMAP_THREADS>(acc2 ? 1 : 0, total2, s_misc + W_PART, pass);
         if (acc2 && pos < c.kf_cap) s_local[pos] = list[L - 1 - nd - j].kf;
         j_base += total;
         n_loc += total2;
@@ -296,9 +268,9 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_select_kernel(SelectCall c)
         const int o   = base + tid;
         const int nb  = o < n_slots ? s_first[o] : -1;
         int total, total2;
-        const int ji    = j_base + block_scan(nb >= 0 ? 1 : 0, total, s_misc + W_PART, pass);
+        const int ji    = j_base + block_scan<LMAP_THREADS>(nb >= 0 ? 1 : 0, total, s_misc + W_PART, pass);
         const bool acc2 = nb >= 0 && lmap_accept(lmap_draw(key, (u32)(R + ji)), c.n_indirect_prob, n_ind);
-        const int pos   = n_loc + block_scan(acc2 ? 1 : 0, total2, s_misc + W_PART, pass);
+        const int pos   = n_loc + block_scan<LMAP_THREADS>(acc2 ? 1 : 0, total2, s_misc + W_PART, pass);
         if (acc2 && pos < c.kf_cap) s_local[pos] = nb;
         j_base += total;
         n_loc += total2;
@@ -363,8 +335,8 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
     }
     // 256 lengths of up to 2^30 do not fit an int: the halves are summed apart
     int tot_lo, tot_hi;
-    const int ex_lo     = block_scan(len & 0xFFFF, tot_lo, s_misc + W_PART, pass);
-    const int ex_hi     = block_scan(len >> 16, tot_hi, s_misc + W_PART, pass);
+    const int ex_lo     = block_scan<LMAP_THREADS>(len & 0xFFFF, tot_lo, s_misc + W_PART, pass);
+    const int ex_hi     = block_scan<LMAP_THREADS>(len >> 16, tot_hi, s_misc + W_PART, pass);
     const long long T64 = ((long long)tot_hi << 16) + tot_lo;
     const int own_a = c.set_start[set], own_b = c.set_start[set + 1];
     const bool own_ok = own_a >= 0 && own_b >= own_a && own_b <= c.n_set_points;
@@ -478,7 +450,7 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
             }
         }
         int total;
-        const int rank = n_out + block_scan(win ? 1 : 0, total, s_misc + W_PART, pass);
+        const int rank = n_out + block_scan<LMAP_THREADS>(win ? 1 : 0, total, s_misc + W_PART, pass);
         if (win && rank < c.pts_cap)
         {
             u64* r        = recs + (size_t)rank * 12;
@@ -496,8 +468,8 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
         }
         n_out += total;
     }
-    searchable = wave_sum(searchable);
-    own_new    = wave_sum(own_new);
+    searchable = wave_sum_xor(searchable);
+    own_new    = wave_sum_xor(own_new);
     if ((tid & 63) == 0)
     {
         atomicAdd(&s_misc[W_SEARCH], (u32)searchable);
@@ -508,52 +480,12 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
     if (tid == 0) c.n_pts[set] = n_out, c.out[set] = LmapGatherResult{n_out, (int)s_misc[W_SEARCH], (int)s_misc[W_OWN], LMAP_OK};
 }
 
-size_t align16(size_t x)
-{
-    return (x + 15) & ~(size_t)15;
-}
-
-// the arrays of a host call as one block: add() in order, then copy() into the pinned staging; at() is the device address
-struct Block
-{
-    struct Part
-    {
-        const void* src;
-        size_t bytes, offset;
-    };
-    std::vector<Part> parts;
-    size_t bytes = 0;
-    int add(const void* src, size_t n)
-    {
-        parts.push_back(Part{src, n, bytes});
-        bytes += align16(n);
-        return (int)parts.size() - 1;
-    }
-    void copy(char* host) const
-    {
-        for (const Part& p : parts)
-            if (p.bytes) memcpy(host + p.offset, p.src, p.bytes);
-    }
-    template <typename T>
-    T* at(char* dev, int part) const
-    {
-        return reinterpret_cast<T*>(dev + parts[(size_t)part].offset);
-    }
-};
-
 int check_params(const snk_lmap_params* p)
 {
     SNK_REQUIRE(p != nullptr, "local map: params is NULL");
     SNK_REQUIRE(p->n_direct >= 0 && p->n_direct_prob >= 0 && p->n_indirect_prob >= 0 && p->n_neighbours >= 0, "local map: a parameter below 0");
     SNK_REQUIRE(p->n_neighbours <= SNK_LMAP_MAX_NEIGHBOURS, "local map: n_neighbours above SNK_LMAP_MAX_NEIGHBOURS (16)");
     SNK_REQUIRE(p->kf_cap >= 1 && p->kf_cap <= SNK_LMAP_MAX_LOCAL_KF, "local map: kf_cap outside [1, SNK_LMAP_MAX_LOCAL_KF]");
-    return SNK_OK;
-}
-
-int check_starts(const int32_t* start, int n, const char* begin_msg, const char* order_msg)
-{
-    SNK_REQUIRE(start[0] == 0, begin_msg);
-    for (int i = 0; i < n; ++i) SNK_REQUIRE(start[i + 1] >= start[i], order_msg);
     return SNK_OK;
 }
 
@@ -655,19 +587,15 @@ int snk_lmap_select(snk_matcher* m, int n_sets, const snk_covis_conn* conn, int 
         }
     }
     const size_t ns = (size_t)n_sets, cap = (size_t)params->kf_cap;
-    Block in;
+    Block in, out_b;
     const int i_conn = in.add(conn, ns * (size_t)vote_cap * sizeof(snk_covis_conn)), i_vote = in.add(vote, ns * sizeof(snk_covis_result)),
               i_bad = in.add(kf_bad, (size_t)n_kf), i_start = in.add(conn_start, ((size_t)n_kf + 1) * 4),
               i_list = in.add(conn_list, (size_t)n_list * sizeof(snk_covis_conn)), i_fid = in.add(frame_id, ns * 4);
-    const size_t o_res = align16(ns * cap * 4), out_bytes = o_res + ns * sizeof(LmapSelectResult);
+    const int o_kf = out_b.add(nullptr, ns * cap * 4), o_res = out_b.add(nullptr, ns * sizeof(LmapSelectResult));
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_bytes)) != SNK_OK) return rc;
-    char* dev = m->q.as<char>();
-    in.copy(m->h_in.as<char>());
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, m->h_in.p, in.bytes, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_reserve(m, in.bytes, out_b.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char *dev = m->q.as<char>(), *dout = m->out.as<char>(), *res = m->h_res.as<char>();
     SelectCall C = select_call(n_sets, vote_cap, n_kf, n_list, params);
     C.conn       = in.at<const snk_covis_conn>(dev, i_conn);
     C.vote       = in.at<const snk_covis_result>(dev, i_vote);
@@ -675,13 +603,12 @@ int snk_lmap_select(snk_matcher* m, int n_sets, const snk_covis_conn* conn, int 
     C.conn_start = in.at<const int>(dev, i_start);
     C.conn_list  = in.at<const int2>(dev, i_list);
     C.frame_id   = in.at<const int>(dev, i_fid);
-    C.local_kf   = m->out.as<int>();
-    C.out        = reinterpret_cast<LmapSelectResult*>(m->out.as<char>() + o_res);
+    C.local_kf   = out_b.at<int>(dout, o_kf);
+    C.out        = out_b.at<LmapSelectResult>(dout, o_res);
     if ((rc = launch_select(m, C)) != SNK_OK) return rc;
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, m->out.p, out_bytes, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(local_kf, m->h_res.p, ns * cap * 4);
-    memcpy(out, m->h_res.as<char>() + o_res, ns * sizeof(LmapSelectResult));
+    if ((rc = stage_download(m, 0, out_b.end())) != SNK_OK) return rc;
+    memcpy(local_kf, out_b.at<char>(res, o_kf), ns * cap * 4);
+    memcpy(out, out_b.at<char>(res, o_res), ns * sizeof(LmapSelectResult));
     return SNK_OK;
 }
 
@@ -746,22 +673,19 @@ int snk_lmap_gather(snk_matcher* m, int n_sets, const snk_lmap_map* map, const s
         SNK_REQUIRE(candidates <= LMAP_MAX_ORDER, "local map: more than 2^30 candidates in a set");
     }
     const size_t ns = (size_t)n_sets, np = (size_t)map->n_points, cap = (size_t)pts_cap;
-    Block in;
+    Block in, out_b;
     const int i_fs = in.add(map->feat_start, ((size_t)map->n_kf + 1) * 4), i_fp = in.add(map->feat_point, (size_t)map->n_feat * 4),
               i_fl = in.add(map->pt_flags, np), i_ls = in.add(map->pt_last_seen, np * 4), i_fid = in.add(frame_id, ns * 4),
               i_lk = in.add(local_kf, ns * (size_t)kf_cap * 4), i_sel = in.add(sel, ns * sizeof(LmapSelectResult)), i_ss = in.add(set_start, (ns + 1) * 4),
               i_sp = in.add(set_point, (size_t)n_set_points * 4), i_pos = in.add(points->pos, np * 24), i_nrm = in.add(points->normal, np * 24),
               i_dsc = in.add(points->desc, np * 32), i_dep = in.add(points->ref_depth, np * 4), i_lvl = in.add(points->ref_level, np * 4);
-    const size_t o_ids = align16(ns * cap * sizeof(snk_lm_fine)), o_n = o_ids + align16(ns * cap * 4), o_res = o_n + align16(ns * 4),
-                 out_bytes = o_res + ns * sizeof(LmapGatherResult);
+    const size_t rec = sizeof(snk_lm_fine);
+    const int o_pts = out_b.add(nullptr, ns * cap * rec), o_ids = out_b.add(nullptr, ns * cap * 4), o_n = out_b.add(nullptr, ns * 4),
+              o_res = out_b.add(nullptr, ns * sizeof(LmapGatherResult));
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_bytes)) != SNK_OK) return rc;
-    char *dev = m->q.as<char>(), *dout = m->out.as<char>();
-    in.copy(m->h_in.as<char>());
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, m->h_in.p, in.bytes, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_reserve(m, in.bytes, out_b.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char *dev = m->q.as<char>(), *dout = m->out.as<char>(), *res = m->h_res.as<char>();
     snk_lmap_map dmap = *map;
     dmap.feat_start = in.at<const int32_t>(dev, i_fs), dmap.feat_point = in.at<const int32_t>(dev, i_fp), dmap.pt_flags = in.at<const uint8_t>(dev, i_fl);
     dmap.pt_last_seen = in.at<const int32_t>(dev, i_ls);
@@ -773,26 +697,24 @@ int snk_lmap_gather(snk_matcher* m, int n_sets, const snk_lmap_map* map, const s
     C.sel        = in.at<const LmapSelectResult>(dev, i_sel);
     C.set_start  = in.at<const int>(dev, i_ss);
     C.set_point  = in.at<const int>(dev, i_sp);
-    C.lm_pts     = reinterpret_cast<u64*>(dout);
-    C.lm_point   = reinterpret_cast<int*>(dout + o_ids);
-    C.n_pts      = reinterpret_cast<int*>(dout + o_n);
-    C.out        = reinterpret_cast<LmapGatherResult*>(dout + o_res);
+    C.lm_pts     = out_b.at<u64>(dout, o_pts);
+    C.lm_point   = out_b.at<int>(dout, o_ids);
+    C.n_pts      = out_b.at<int>(dout, o_n);
+    C.out        = out_b.at<LmapGatherResult>(dout, o_res);
     if ((rc = launch_gather(m, C)) != SNK_OK) return rc;
-    // the records come back per set, n_pts of them: the words behind them were never written
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.as<char>() + o_ids, dout + o_ids, out_bytes - o_ids, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const char* res = m->h_res.as<char>();
-    const int* got  = reinterpret_cast<const int*>(res + o_n);
+    // two steps: everything behind the records, then the records per set, n_pts of them: the words behind them were never written
+    const size_t ids_at = out_b.parts[(size_t)o_ids].offset;
+    if ((rc = stage_download(m, ids_at, out_b.end() - ids_at)) != SNK_OK) return rc;
+    const int* got = out_b.at<const int>(res, o_n);
     for (size_t s = 0; s < ns; ++s)
         if (got[s] > 0)
-            SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.as<char>() + s * cap * sizeof(snk_lm_fine), dout + s * cap * sizeof(snk_lm_fine),
-                                         (size_t)got[s] * sizeof(snk_lm_fine), hipMemcpyDeviceToHost, m->stream));
+            SNK_HIP_CHECK(hipMemcpyAsync(res + s * cap * rec, dout + s * cap * rec, (size_t)got[s] * rec, hipMemcpyDeviceToHost, m->stream));
     SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
     for (size_t s = 0; s < ns; ++s)
-        if (got[s] > 0) memcpy(lm_pts + s * cap, res + s * cap * sizeof(snk_lm_fine), (size_t)got[s] * sizeof(snk_lm_fine));
-    memcpy(lm_point, res + o_ids, ns * cap * 4);
+        if (got[s] > 0) memcpy(lm_pts + s * cap, res + s * cap * rec, (size_t)got[s] * rec);
+    memcpy(lm_point, out_b.at<char>(res, o_ids), ns * cap * 4);
     memcpy(n_pts, got, ns * 4);
-    memcpy(out, res + o_res, ns * sizeof(LmapGatherResult));
+    memcpy(out, out_b.at<char>(res, o_res), ns * sizeof(LmapGatherResult));
     return SNK_OK;
 }
 

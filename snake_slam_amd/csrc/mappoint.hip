@@ -485,11 +485,6 @@ __global__ __launch_bounds__(MP_WIDE_THREADS) void mp_wide_kernel(MpCall c)
     }
 }
 
-size_t align16(size_t x)
-{
-    return (x + 15) & ~(size_t)15;
-}
-
 int form_env()
 {
     // SNK_MP_FORM=packed|wide (tests, A/B): read once
@@ -565,26 +560,15 @@ int snk_mappoint_refresh(snk_matcher* m, const snk_mp_params* params, int n_poin
     }
     const size_t n_obs = (size_t)obs_start[n_points], np = (size_t)n_points;
     SNK_REQUIRE(n_obs == 0 || (desc != nullptr && cam_pose != nullptr && octave != nullptr && valid != nullptr), "map-point refresh: NULL observation array with observations");
-    // one upload: obs_start | ref_obs | position | valid | octave | cam_pose | desc
-    const size_t o_ref = align16((np + 1) * 4), o_pos = o_ref + align16(np * 4), o_valid = o_pos + align16(np * 24), o_oct = o_valid + align16(n_obs),
-                 o_pose = o_oct + align16(n_obs * 4), o_desc = o_pose + align16(n_obs * 56), bytes = o_desc + align16(n_obs * 32);
+    // one upload (stage.hpp): obs_start | ref_obs | position | valid | octave | cam_pose | desc
+    Block in, out_b;
+    const int i_start = in.add(obs_start, (np + 1) * 4), i_ref = in.add(ref_obs, np * 4), i_pos = in.add(position, np * 24), i_valid = in.add(valid, n_obs),
+              i_oct = in.add(octave, n_obs * 4), i_pose = in.add(cam_pose, n_obs * 56), i_desc = in.add(desc, n_obs * 32);
+    const int o_res = out_b.add(nullptr, np * sizeof(snk_mp_result));
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(np * sizeof(snk_mp_result))) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(np * sizeof(snk_mp_result))) != SNK_OK) return rc;
-    char *host = m->h_in.as<char>(), *dev = m->q.as<char>();
-    memcpy(host, obs_start, (np + 1) * 4);
-    memcpy(host + o_ref, ref_obs, np * 4);
-    memcpy(host + o_pos, position, np * 24);
-    if (n_obs)
-    {
-        memcpy(host + o_valid, valid, n_obs);
-        memcpy(host + o_oct, octave, n_obs * 4);
-        memcpy(host + o_pose, cam_pose, n_obs * 56);
-        memcpy(host + o_desc, desc, n_obs * 32);
-    }
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_reserve(m, in.bytes, out_b.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char* dev = m->q.as<char>();
     MpCall C{};
     C.n_points  = n_points;
     C.n_obs     = (int)n_obs;
@@ -592,18 +576,17 @@ int snk_mappoint_refresh(snk_matcher* m, const snk_mp_params* params, int n_poin
     C.what      = params->what;
     C.rows_cap  = rows_cap;
     C.k_cap     = k_cap;
-    C.obs_start = reinterpret_cast<const int*>(dev);
-    C.ref_obs   = reinterpret_cast<const int*>(dev + o_ref);
-    C.position  = reinterpret_cast<const double*>(dev + o_pos);
-    C.valid     = reinterpret_cast<const u8*>(dev + o_valid);
-    C.octave    = reinterpret_cast<const int*>(dev + o_oct);
-    C.pose      = reinterpret_cast<const double*>(dev + o_pose);
-    C.desc      = reinterpret_cast<const u64*>(dev + o_desc);
-    C.out       = m->out.as<snk_mp_result>();
+    C.obs_start = in.at<const int>(dev, i_start);
+    C.ref_obs   = in.at<const int>(dev, i_ref);
+    C.position  = in.at<const double>(dev, i_pos);
+    C.valid     = in.at<const u8>(dev, i_valid);
+    C.octave    = in.at<const int>(dev, i_oct);
+    C.pose      = in.at<const double>(dev, i_pose);
+    C.desc      = in.at<const u64>(dev, i_desc);
+    C.out       = out_b.at<snk_mp_result>(m->out.as<char>(), o_res);
     if ((rc = launch<false>(m, C, n_wide)) != SNK_OK) return rc;
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, C.out, np * sizeof(snk_mp_result), hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(out, m->h_res.p, np * sizeof(snk_mp_result));
+    if ((rc = stage_download(m, 0, out_b.end())) != SNK_OK) return rc;
+    memcpy(out, out_b.at<char>(m->h_res.as<char>(), o_res), np * sizeof(snk_mp_result));
     return SNK_OK;
 }
 

@@ -1,6 +1,7 @@
 // The matcher / preprocess handle (shared by matcher.hip and preprocess.hip).
 #pragma once
 #include "common.hpp"
+#include "stage.hpp"
 
 struct snk_matcher : snk::HandleBase
 {
@@ -25,6 +26,42 @@ struct snk_matcher : snk::HandleBase
 
 namespace snk
 {
+// The map-side host entries (covis, localmap, mappoint, scene, triangulate) stage a call the same way: the input arrays as one Block
+// (stage.hpp) through `h_in` into `q` with one DMA, the results from `out` through `h_res` with one DMA back.
+
+// start[0 .. n]: begins at 0, never decreases
+inline int check_starts(const int32_t* start, int n, const char* begin_msg, const char* order_msg)
+{
+    SNK_REQUIRE(start[0] == 0, begin_msg);
+    for (int i = 0; i < n; ++i) SNK_REQUIRE(start[i + 1] >= start[i], order_msg);
+    return SNK_OK;
+}
+
+inline int stage_reserve(snk_matcher* m, size_t in_bytes, size_t out_bytes)
+{
+    int rc;
+    if ((rc = m->q.reserve(in_bytes)) != SNK_OK) return rc;
+    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
+    if ((rc = m->h_in.reserve(in_bytes)) != SNK_OK) return rc;
+    return m->h_res.reserve(out_bytes);
+}
+
+// after stage_reserve(m, in.bytes, ...): the parts into `h_in`, then the whole block to `q` on the handle's stream
+inline int stage_upload(snk_matcher* m, const Block& in)
+{
+    in.copy(m->h_in.as<char>());
+    SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, in.bytes, hipMemcpyHostToDevice, m->stream));
+    return SNK_OK;
+}
+
+// out[offset .. offset + bytes) to the same place of `h_res`; returns when it is there
+inline int stage_download(snk_matcher* m, size_t offset, size_t bytes)
+{
+    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.as<char>() + offset, m->out.as<char>() + offset, bytes, hipMemcpyDeviceToHost, m->stream));
+    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return SNK_OK;
+}
+
 // snk_stereo_match_batch_dev with the option of doing Frame::allocateTmp's -1000 prefill of right_points / depth itself (the one-call front-end)
 int stereo_match_batch_dev_impl(snk_matcher* m, const snk_kp64* left_dev, const uint64_t* desc_left_dev, const int32_t* nl_dev, int nl_cap,
                                 const snk_kp64* right_dev, const uint64_t* desc_right_dev, const int32_t* nr_dev, int nr_cap, int batch, double bf,

@@ -23,8 +23,9 @@
 //   lane reads the same word), writes at base + rank, and then adds itself to the base for the next sub-chunk.  No result depends on
 //   the order in which atomics land: the tables' contents as sets do not, and ranks never come from an atomic's return value.
 // Every probe loop ends after `slots` steps, every search after log2 steps, the chain after n_last; no lane waits for another.
+//
+// The host entries lay the arrays of a call out as one block, inputs and outputs alike: stage.hpp, and matcher_handle.hpp for the copies.
 #include <cstddef>
-#include <vector>
 
 #include "matcher_handle.hpp"
 
@@ -77,26 +78,6 @@ struct GatherCall
     const SceneWindowResult* win;
     snk_scene_out out;
 };
-
-__device__ __forceinline__ int block_scan(int v, int& total, u32* s_part, int& pass)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_scan_incl_dpp(v);
-    u32* part      = s_part + (pass & 1) * (SCENE_THREADS / 64);
-    pass += 1;
-    if (lane == 63) part[wave] = (u32)incl;
-    __syncthreads();
-    int before = 0;
-    total      = 0;
-#pragma unroll
-    for (int w = 0; w < SCENE_THREADS / 64; ++w)
-    {
-        const int p = (int)part[w];
-        before += w < wave ? p : 0;
-        total += p;
-    }
-    return before + incl - v;
-}
 
 __global__ __launch_bounds__(SCENE_WIN_THREADS) void scene_window_kernel(WindowCall c)
 {
@@ -255,8 +236,8 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
         }
     }
     int tot_lo, tot_hi;
-    const int ex_lo     = block_scan(len & 0xFFFF, tot_lo, s_misc + W_PART, pass);
-    const int ex_hi     = block_scan(len >> 16, tot_hi, s_misc + W_PART, pass);
+    const int ex_lo     = block_scan<SCENE_THREADS>(len & 0xFFFF, tot_lo, s_misc + W_PART, pass);
+    const int ex_hi     = block_scan<SCENE_THREADS>(len >> 16, tot_hi, s_misc + W_PART, pass);
     const long long T64 = ((long long)tot_hi << 16) + tot_lo;
     if (T64 > LMAP_MAX_ORDER || s_misc[W_BAD])  // uniform: the scans' barriers are behind the writes of W_BAD
     {
@@ -349,7 +330,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
             }
         }
         int total;
-        const int rank = n_pt + block_scan(win ? 1 : 0, total, s_misc + W_PART, pass);
+        const int rank = n_pt + block_scan<SCENE_THREADS>(win ? 1 : 0, total, s_misc + W_PART, pass);
         if (win && rank < O.pt_cap) ids[rank] = p;
         n_pt += total;
     }
@@ -403,8 +384,8 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
             s_pinfo[tid] = p;
             if (bad) s_misc[W_BAD] = 1;
             int lo_t, hi_t;
-            const int lo_e    = block_scan(plen & 0xFFFF, lo_t, s_misc + W_PART, pass);
-            const int hi_e    = block_scan(plen >> 16, hi_t, s_misc + W_PART, pass);
+            const int lo_e    = block_scan<SCENE_THREADS>(plen & 0xFFFF, lo_t, s_misc + W_PART, pass);
+            const int hi_e    = block_scan<SCENE_THREADS>(plen >> 16, hi_t, s_misc + W_PART, pass);
             const long long L = ((long long)hi_t << 16) + lo_t;
             if (s_misc[W_BAD] || walk_base + L > SCENE_MAX_WALK) return false;  // uniform
             s_pstart[tid] = (int)(((long long)hi_e << 16) + lo_e);
@@ -542,7 +523,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
         const int i = base + tid;
         const int v = i < n_img ? (int)s_base[i] : 0;  // <= 2^30 in all
         int total;
-        const int ex = block_scan(v, total, s_misc + W_PART, pass);
+        const int ex = block_scan<SCENE_THREADS>(v, total, s_misc + W_PART, pass);
         if (i < n_img) s_base[i] = (u32)(n_obs + ex);
         n_obs += total;
     }
@@ -654,46 +635,6 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
     if (tid == 0) reinterpret_cast<SceneResult*>(O.result)[set] = SceneResult{nw, n_img, n_pt, n_obs, (int)s_misc[W_NRPC], SCENE_OK};
 }
 
-size_t align16(size_t x)
-{
-    return (x + 15) & ~(size_t)15;
-}
-
-// the arrays of a host call as one block: add() in order, then copy() into the pinned staging; at() is the device address
-struct Block
-{
-    struct Part
-    {
-        const void* src;
-        size_t bytes, offset;
-    };
-    std::vector<Part> parts;
-    size_t bytes = 0;
-    int add(const void* src, size_t n)
-    {
-        parts.push_back(Part{src, n, bytes});
-        bytes += align16(n);
-        return (int)parts.size() - 1;
-    }
-    void copy(char* host) const
-    {
-        for (const Part& p : parts)
-            if (p.bytes && p.src) memcpy(host + p.offset, p.src, p.bytes);
-    }
-    template <typename T>
-    T* at(char* dev, int part) const
-    {
-        return reinterpret_cast<T*>(dev + parts[(size_t)part].offset);
-    }
-};
-
-int check_starts(const int32_t* start, int n, const char* begin_msg, const char* order_msg)
-{
-    SNK_REQUIRE(start[0] == 0, begin_msg);
-    for (int i = 0; i < n; ++i) SNK_REQUIRE(start[i + 1] >= start[i], order_msg);
-    return SNK_OK;
-}
-
 int check_window_scalars(int n_q, int n_kf, const snk_scene_params* p, int win_cap)
 {
     SNK_REQUIRE(p != nullptr, "scene: params is NULL");
@@ -704,6 +645,15 @@ int check_window_scalars(int n_q, int n_kf, const snk_scene_params* p, int win_c
     SNK_REQUIRE(win_cap >= 1 && win_cap <= SNK_SCENE_MAX_WINDOW, "scene: win_cap outside [1, SNK_SCENE_MAX_WINDOW]");
     return SNK_OK;
 }
+
+// a row output of snk_scene_gather: where the caller wants it, the rows' capacity in items, an item's bytes, and the count of the
+// query's result that a row comes back up to (nullptr: the whole row)
+struct SceneRow
+{
+    void* dst;
+    size_t cap, item;
+    int32_t SceneResult::*count;
+};
 
 bool has_imu(const snk_scene_map* map)
 {
@@ -792,31 +742,26 @@ int snk_scene_window(snk_matcher* m, int n_q, const int32_t* q, int n_kf, const 
     SNK_REQUIRE(q != nullptr && window_kf != nullptr && out != nullptr, "scene: NULL array with n_q > 0");
     for (int s = 0; s < n_q; ++s) SNK_REQUIRE(q[s] >= 0 && q[s] < n_kf, "scene: a query outside [0, n_kf)");
     const size_t ns = (size_t)n_q, cap = (size_t)win_cap;
-    Block in;
+    Block in, out_b;
     const int i_q = in.add(q, ns * 4), i_bad = in.add(kf_bad, (size_t)n_kf), i_prev = in.add(kf_prev, (size_t)n_kf * 4),
               i_start = in.add(conn_start, ((size_t)n_kf + 1) * 4), i_list = in.add(conn_list, (size_t)n_list * sizeof(snk_covis_conn));
-    const size_t o_res = align16(ns * cap * 4), out_bytes = o_res + ns * sizeof(SceneWindowResult);
+    const int o_win = out_b.add(nullptr, ns * cap * 4), o_res = out_b.add(nullptr, ns * sizeof(SceneWindowResult));
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_bytes)) != SNK_OK) return rc;
-    char* dev = m->q.as<char>();
-    in.copy(m->h_in.as<char>());
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, m->h_in.p, in.bytes, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_reserve(m, in.bytes, out_b.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char *dev = m->q.as<char>(), *dout = m->out.as<char>(), *res = m->h_res.as<char>();
     WindowCall C = window_call(n_q, n_kf, n_list, params, win_cap);
     C.q          = in.at<const int>(dev, i_q);
     C.kf_bad     = in.at<const u8>(dev, i_bad);
     C.kf_prev    = in.at<const int>(dev, i_prev);
     C.conn_start = in.at<const int>(dev, i_start);
     C.conn_list  = in.at<const int2>(dev, i_list);
-    C.window_kf  = m->out.as<int>();
-    C.out        = reinterpret_cast<SceneWindowResult*>(m->out.as<char>() + o_res);
+    C.window_kf  = out_b.at<int>(dout, o_win);
+    C.out        = out_b.at<SceneWindowResult>(dout, o_res);
     if ((rc = launch_window(m, C)) != SNK_OK) return rc;
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, m->out.p, out_bytes, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(window_kf, m->h_res.p, ns * cap * 4);
-    memcpy(out, m->h_res.as<char>() + o_res, ns * sizeof(SceneWindowResult));
+    if ((rc = stage_download(m, 0, out_b.end())) != SNK_OK) return rc;
+    memcpy(window_kf, out_b.at<char>(res, o_win), ns * cap * 4);
+    memcpy(out, out_b.at<char>(res, o_res), ns * sizeof(SceneWindowResult));
     return SNK_OK;
 }
 
@@ -888,7 +833,7 @@ int snk_scene_gather(snk_matcher* m, int n_q, const snk_scene_map* map, const in
     SNK_REQUIRE(map->n_obs <= SCENE_MAX_WALK, "scene: more than 2^30 observations");
     const size_t nk = (size_t)map->n_kf, np = (size_t)map->n_points, nf = (size_t)map->n_feat, no = (size_t)map->n_obs;
     const bool imu = has_imu(map);
-    Block in;
+    Block in, out_b;
     const int i_bad = in.add(map->kf_bad, nk), i_pose = in.add(map->kf_pose, nk * 56), i_fs = in.add(map->feat_start, (nk + 1) * 4),
               i_fp = in.add(map->feat_point, nf * 4), i_fd = in.add(map->feat_depth, nf * 4), i_uv = in.add(map->feat_uv, nf * 8),
               i_oct = in.add(map->feat_octave, nf * 4), i_os = in.add(map->obs_start, (np + 1) * 4), i_obs = in.add(map->obs, no * 8),
@@ -896,21 +841,20 @@ int snk_scene_gather(snk_matcher* m, int n_q, const snk_scene_map* map, const in
               i_t = in.add(map->kf_time, imu ? nk * 8 : 0), i_tb = in.add(map->kf_imu_begin, imu ? nk * 8 : 0), i_te = in.add(map->kf_imu_end, imu ? nk * 8 : 0),
               i_pv = in.add(map->kf_preint_valid, imu ? nk : 0), i_rpc = in.add(map->kf_rpc, imu ? nk * sizeof(snk_ba_rpc) : 0),
               i_win = in.add(window_kf, ns * wc * 4), i_wr = in.add(win, ns * sizeof(SceneWindowResult));
-    // the outputs as one block, in the order of snk_scene_out
-    const size_t sizes[15] = {ns * ic * 4, ns * ic * 56, ns * ic, ns * pc * 4, ns * pc * 24, ns * pc, ns * pc, ns * oc * 4, ns * oc * 4, ns * oc * 16,
-                              ns * oc * 8, ns * oc * 8, ns * oc * 8, ns * wc * sizeof(snk_ba_rpc), ns * sizeof(SceneResult)};
-    size_t off[16];
-    off[0] = 0;
-    for (int i = 0; i < 15; ++i) off[i + 1] = off[i] + align16(sizes[i]);
-    const size_t out_bytes = off[15];
+    // the outputs as one block, in the order of snk_scene_out: parts 0 .. 13 are the row outputs of `rows`, part 14 the results
+    const SceneRow rows[14] = {{out->img_kf, ic, 4, &SceneResult::n_img},     {out->pose, ic, 56, &SceneResult::n_img},
+                               {out->img_const, ic, 1, &SceneResult::n_img},  {out->pt_id, pc, 4, nullptr},
+                               {out->pt, pc, 24, &SceneResult::n_pt},         {out->pt_const, pc, 1, &SceneResult::n_pt},
+                               {out->pt_valid, pc, 1, &SceneResult::n_pt},    {out->obs_img, oc, 4, &SceneResult::n_obs},
+                               {out->obs_pt, oc, 4, &SceneResult::n_obs},     {out->obs_uv, oc, 16, &SceneResult::n_obs},
+                               {out->obs_depth, oc, 8, &SceneResult::n_obs},  {out->obs_weight, oc, 8, &SceneResult::n_obs},
+                               {out->obs_src, oc, 8, &SceneResult::n_obs},    {out->rpc, wc, sizeof(snk_ba_rpc), &SceneResult::n_rpc}};
+    for (const SceneRow& row : rows) out_b.add(nullptr, ns * row.cap * row.item);
+    const int o_result = out_b.add(nullptr, ns * sizeof(SceneResult));
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in.bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_bytes)) != SNK_OK) return rc;
-    char *dev = m->q.as<char>(), *dout = m->out.as<char>();
-    in.copy(m->h_in.as<char>());
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, m->h_in.p, in.bytes, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_reserve(m, in.bytes, out_b.bytes)) != SNK_OK) return rc;  // this block has always been asked for with its last part padded
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char *dev = m->q.as<char>(), *dout = m->out.as<char>(), *res = m->h_res.as<char>();
     snk_scene_map dmap = *map;
     dmap.kf_bad = in.at<const uint8_t>(dev, i_bad), dmap.kf_prev = nullptr, dmap.kf_pose = in.at<const double>(dev, i_pose);
     dmap.feat_start = in.at<const int32_t>(dev, i_fs), dmap.feat_point = in.at<const int32_t>(dev, i_fp), dmap.feat_depth = in.at<const float>(dev, i_fd);
@@ -923,31 +867,26 @@ int snk_scene_gather(snk_matcher* m, int n_q, const snk_scene_map* map, const in
         dmap.kf_preint_valid = in.at<const uint8_t>(dev, i_pv), dmap.kf_rpc = in.at<const snk_ba_rpc>(dev, i_rpc);
     }
     snk_scene_out dso = *out;
-    dso.img_kf = reinterpret_cast<int32_t*>(dout + off[0]), dso.pose = reinterpret_cast<double*>(dout + off[1]), dso.img_const = reinterpret_cast<uint8_t*>(dout + off[2]);
-    dso.pt_id = reinterpret_cast<int32_t*>(dout + off[3]), dso.pt = reinterpret_cast<double*>(dout + off[4]), dso.pt_const = reinterpret_cast<uint8_t*>(dout + off[5]);
-    dso.pt_valid = reinterpret_cast<uint8_t*>(dout + off[6]), dso.obs_img = reinterpret_cast<int32_t*>(dout + off[7]), dso.obs_pt = reinterpret_cast<int32_t*>(dout + off[8]);
-    dso.obs_uv = reinterpret_cast<double*>(dout + off[9]), dso.obs_depth = reinterpret_cast<double*>(dout + off[10]), dso.obs_weight = reinterpret_cast<double*>(dout + off[11]);
-    dso.obs_src = reinterpret_cast<int32_t*>(dout + off[12]), dso.rpc = reinterpret_cast<snk_ba_rpc*>(dout + off[13]), dso.result = reinterpret_cast<snk_scene_result*>(dout + off[14]);
+    dso.img_kf = out_b.at<int32_t>(dout, 0), dso.pose = out_b.at<double>(dout, 1), dso.img_const = out_b.at<uint8_t>(dout, 2);
+    dso.pt_id = out_b.at<int32_t>(dout, 3), dso.pt = out_b.at<double>(dout, 4), dso.pt_const = out_b.at<uint8_t>(dout, 5);
+    dso.pt_valid = out_b.at<uint8_t>(dout, 6), dso.obs_img = out_b.at<int32_t>(dout, 7), dso.obs_pt = out_b.at<int32_t>(dout, 8);
+    dso.obs_uv = out_b.at<double>(dout, 9), dso.obs_depth = out_b.at<double>(dout, 10), dso.obs_weight = out_b.at<double>(dout, 11);
+    dso.obs_src = out_b.at<int32_t>(dout, 12), dso.rpc = out_b.at<snk_ba_rpc>(dout, 13), dso.result = out_b.at<snk_scene_result>(dout, o_result);
     GatherCall C = gather_call(n_q, &dmap, params, &dso);
     C.window_kf  = in.at<const int>(dev, i_win);
     C.win        = in.at<const SceneWindowResult>(dev, i_wr);
     if ((rc = launch_gather(m, C)) != SNK_OK) return rc;
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, m->out.p, out_bytes, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if ((rc = stage_download(m, 0, out_b.bytes)) != SNK_OK) return rc;
     // a row comes back up to its count: the words behind it were never written
-    const char* res      = m->h_res.as<char>();
-    const SceneResult* r = reinterpret_cast<const SceneResult*>(res + off[14]);
-    auto rows = [&](void* dst, int part, size_t cap, size_t item, size_t s, int count) {
-        if (dst != nullptr && count > 0) memcpy(static_cast<char*>(dst) + s * cap * item, res + off[part] + s * cap * item, (size_t)count * item);
-    };
+    const SceneResult* r = out_b.at<const SceneResult>(res, o_result);
     for (size_t s = 0; s < ns; ++s)
-    {
-        rows(out->img_kf, 0, ic, 4, s, r[s].n_img), rows(out->pose, 1, ic, 56, s, r[s].n_img), rows(out->img_const, 2, ic, 1, s, r[s].n_img);
-        rows(out->pt_id, 3, pc, 4, s, out->pt_cap), rows(out->pt, 4, pc, 24, s, r[s].n_pt), rows(out->pt_const, 5, pc, 1, s, r[s].n_pt);
-        rows(out->pt_valid, 6, pc, 1, s, r[s].n_pt), rows(out->obs_img, 7, oc, 4, s, r[s].n_obs), rows(out->obs_pt, 8, oc, 4, s, r[s].n_obs);
-        rows(out->obs_uv, 9, oc, 16, s, r[s].n_obs), rows(out->obs_depth, 10, oc, 8, s, r[s].n_obs), rows(out->obs_weight, 11, oc, 8, s, r[s].n_obs);
-        rows(out->obs_src, 12, oc, 8, s, r[s].n_obs), rows(out->rpc, 13, wc, sizeof(snk_ba_rpc), s, r[s].n_rpc);
-    }
+        for (int part = 0; part < 14; ++part)
+        {
+            const SceneRow& row = rows[part];
+            const size_t at = s * row.cap * row.item;
+            const int count = row.count ? r[s].*row.count : out->pt_cap;
+            if (row.dst != nullptr && count > 0) memcpy(static_cast<char*>(row.dst) + at, out_b.at<char>(res, part) + at, (size_t)count * row.item);
+        }
     memcpy(out->result, r, ns * sizeof(SceneResult));
     return SNK_OK;
 }

@@ -203,37 +203,26 @@ int check_view(const snk_tri_view* v)
     return SNK_OK;
 }
 
-size_t align16(size_t x)
+// a view's arrays as four parts of the upload block (stage.hpp): kps | right_points | depth | has_mp
+struct ViewParts
 {
-    return (x + 15) & ~(size_t)15;
-}
-
-// bytes of one view's arrays in the upload block: kps | right_points | depth | has_mp, each 16-aligned
-size_t view_bytes(int n)
-{
-    const size_t nn = (size_t)n;
-    return align16(nn * sizeof(snk_kp64)) + 2 * align16(nn * 4) + align16(nn);
-}
-
-// copies the view's arrays to host[off ...] and points V at their device addresses
-size_t stage_view(const snk_tri_view* v, char* host, char* dev, size_t off, TriViewDev* V)
+    int kps, right_points, depth, has_mp;
+};
+ViewParts add_view(Block& in, const snk_tri_view* v)
 {
     const size_t nn = (size_t)v->n;
-    V->n            = v->n;
+    return ViewParts{in.add(v->kps, nn * sizeof(snk_kp64)), in.add(v->right_points, nn * 4), in.add(v->depth, nn * 4), in.add(v->has_mp, nn)};
+}
+
+// the view as the kernels take it: its pose, its arrays at their device addresses
+void view_on_device(const snk_tri_view* v, const Block& in, char* dev, const ViewParts& p, TriViewDev* V)
+{
+    V->n = v->n;
     make_pose(v->pose, &V->P);
-    V->kps = reinterpret_cast<const snk_kp64*>(dev + off);
-    if (nn) memcpy(host + off, v->kps, nn * sizeof(snk_kp64));
-    off += align16(nn * sizeof(snk_kp64));
-    V->right_points = reinterpret_cast<const float*>(dev + off);
-    if (nn) memcpy(host + off, v->right_points, nn * 4);
-    off += align16(nn * 4);
-    V->depth = reinterpret_cast<const float*>(dev + off);
-    if (nn) memcpy(host + off, v->depth, nn * 4);
-    off += align16(nn * 4);
-    V->has_mp = reinterpret_cast<const u8*>(dev + off);
-    if (nn) memcpy(host + off, v->has_mp, nn);
-    off += align16(nn);
-    return off;
+    V->kps          = in.at<const snk_kp64>(dev, p.kps);
+    V->right_points = in.at<const float>(dev, p.right_points);
+    V->depth        = in.at<const float>(dev, p.depth);
+    V->has_mp       = in.at<const u8>(dev, p.has_mp);
 }
 
 int triangulate_impl(snk_matcher* m, const snk_camera* cam, const snk_tri_params* params, const snk_tri_view* kf1, const snk_tri_view* kf2s,
@@ -254,12 +243,16 @@ int triangulate_impl(snk_matcher* m, const snk_camera* cam, const snk_tri_params
     int rc;
     if ((rc = check_view(kf1)) != SNK_OK) return rc;
     SNK_REQUIRE(pair_start[0] == 0, "pair_start[0] must be 0");
-    size_t bytes = align16((size_t)n_nb * sizeof(TriViewDev)) + view_bytes(kf1->n);
+    // one upload: the TriViewDev table (filled in the staging buffer below) | kf1's arrays | every neighbour's | pairs
+    Block in, out_b;
+    const int i_views  = in.add(nullptr, (size_t)n_nb * sizeof(TriViewDev));
+    const ViewParts p1 = add_view(in, kf1);
+    std::vector<ViewParts> p2((size_t)n_nb);
     for (int k = 0; k < n_nb; ++k)
     {
         if ((rc = check_view(&kf2s[k])) != SNK_OK) return rc;
         SNK_REQUIRE(pair_start[k + 1] >= pair_start[k], "pair_start must be non-decreasing");
-        bytes += view_bytes(kf2s[k].n);
+        p2[(size_t)k] = add_view(in, &kf2s[k]);
     }
     const int n_pairs = pair_start[n_nb];
     if (n_pairs == 0) return SNK_OK;
@@ -273,16 +266,14 @@ int triangulate_impl(snk_matcher* m, const snk_camera* cam, const snk_tri_params
             SNK_REQUIRE(kf1->kps[a].octave >= 0 && kf1->kps[a].octave < n_levels, "pair: keyframe-1 octave outside [0, n_levels)");
             SNK_REQUIRE(kf2s[k].kps[b].octave >= 0 && kf2s[k].kps[b].octave < n_levels, "pair: keyframe-2 octave outside [0, n_levels)");
         }
-    const size_t o_pairs = bytes;
-    bytes += align16((size_t)n_pairs * 8);
-    // results: out_start[n_nb + 1] | points[n_pairs]; scratch behind them: count[n_nb] | candidates[n_pairs]
-    const size_t r_pts = align16((size_t)(n_nb + 1) * 4), r_bytes = r_pts + (size_t)n_pairs * sizeof(snk_new_point);
-    const size_t s_cand = align16(r_bytes) + align16((size_t)n_nb * 4), s_bytes = s_cand + (size_t)n_pairs * sizeof(snk_new_point);
+    const int i_pairs = in.add(pairs, (size_t)n_pairs * 8);
+    // results: out_start[n_nb + 1] | points[n_pairs]; scratch behind them, on the device only: count[n_nb] | candidates[n_pairs]
+    const int o_start = out_b.add(nullptr, (size_t)(n_nb + 1) * 4), o_pts = out_b.add(nullptr, (size_t)n_pairs * sizeof(snk_new_point));
+    const size_t r_bytes = out_b.end();
+    const int o_count = out_b.add(nullptr, (size_t)n_nb * 4), o_cand = out_b.add(nullptr, (size_t)n_pairs * sizeof(snk_new_point));
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    if ((rc = m->q.reserve(bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(s_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(r_bytes)) != SNK_OK) return rc;
+    if ((rc = m->out.reserve(out_b.end())) != SNK_OK) return rc;  // with the scratch; the pinned block holds the results only
+    if ((rc = stage_reserve(m, in.bytes, r_bytes)) != SNK_OK) return rc;
     char *host = m->h_in.as<char>(), *dev = m->q.as<char>();
     TriCallDev C;
     C.K.fx = cam->fx; C.K.fy = cam->fy; C.K.cx = cam->cx; C.K.cy = cam->cy; C.K.bf = cam->bf;
@@ -291,13 +282,12 @@ int triangulate_impl(snk_matcher* m, const snk_camera* cam, const snk_tri_params
     C.K.chi2_stereo  = params->error_stereo * params->error_stereo;  // :128
     C.K.ratio_factor = 1.5f * params->scale_factor;                  // :132
     for (int i = 0; i < TRI_MAX_LEVELS; ++i) C.level_scale[i] = level_scale[i < n_levels ? i : n_levels - 1];
-    size_t off = align16((size_t)n_nb * sizeof(TriViewDev));
-    off        = stage_view(kf1, host, dev, off, &C.kf1);
+    view_on_device(kf1, in, dev, p1, &C.kf1);
     C.kf1.pair_begin = 0; C.kf1.pair_end = n_pairs; C.kf1.skip = 0;
-    TriViewDev* hv = reinterpret_cast<TriViewDev*>(host);
+    TriViewDev* hv = in.at<TriViewDev>(host, i_views);
     for (int k = 0; k < n_nb; ++k)
     {
-        off              = stage_view(&kf2s[k], host, dev, off, &hv[k]);
+        view_on_device(&kf2s[k], in, dev, p2[(size_t)k], &hv[k]);
         hv[k].pair_begin = pair_start[k];
         hv[k].pair_end   = pair_start[k + 1];
         // the per-neighbour baseline gate, :140-157
@@ -313,22 +303,19 @@ int triangulate_impl(snk_matcher* m, const snk_camera* cam, const snk_tri_params
         else
             hv[k].skip = baseline < cam->bf / cam->fx ? 1 : 0;  // stereo_cam.baseLine() [DEFINED] = bf / fx
     }
-    memcpy(host + o_pairs, pairs, (size_t)n_pairs * 8);
-    SNK_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, m->stream));
-    char* res           = m->out.as<char>();
-    int* d_out_start    = reinterpret_cast<int*>(res);
-    snk_new_point* d_pt = reinterpret_cast<snk_new_point*>(res + r_pts);
-    int* d_count        = reinterpret_cast<int*>(res + align16(r_bytes));
-    snk_new_point* d_cd = reinterpret_cast<snk_new_point*>(res + s_cand);
-    const TriViewDev* d_views = reinterpret_cast<const TriViewDev*>(dev);
-    hipLaunchKernelGGL(tri_pairs_kernel, dim3(n_nb), dim3(256), 0, m->stream, C, d_views, reinterpret_cast<const int2*>(dev + o_pairs), d_cd,
-                       d_count);
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;  // the table is in place: it has no source
+    char* dout          = m->out.as<char>();
+    int* d_out_start    = out_b.at<int>(dout, o_start);
+    snk_new_point* d_pt = out_b.at<snk_new_point>(dout, o_pts);
+    int* d_count        = out_b.at<int>(dout, o_count);
+    snk_new_point* d_cd = out_b.at<snk_new_point>(dout, o_cand);
+    const TriViewDev* d_views = in.at<const TriViewDev>(dev, i_views);
+    hipLaunchKernelGGL(tri_pairs_kernel, dim3(n_nb), dim3(256), 0, m->stream, C, d_views, in.at<const int2>(dev, i_pairs), d_cd, d_count);
     SNK_LAUNCH_CHECK();
     hipLaunchKernelGGL(tri_commit_kernel, dim3(1), dim3(64), 0, m->stream, C.kf1, d_views, n_nb, d_cd, d_count, d_out_start, d_pt);
     SNK_LAUNCH_CHECK();
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, res, r_bytes, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const int* h_start = m->h_res.as<int>();
+    if ((rc = stage_download(m, 0, r_bytes)) != SNK_OK) return rc;
+    const int* h_start = out_b.at<const int>(m->h_res.as<char>(), o_start);
     const int total    = h_start[n_nb];
     if (total < 0 || total > n_pairs)
     {
@@ -336,7 +323,7 @@ int triangulate_impl(snk_matcher* m, const snk_camera* cam, const snk_tri_params
         return SNK_ERR_HIP;
     }
     memcpy(out_start, h_start, (size_t)(n_nb + 1) * 4);
-    memcpy(out, m->h_res.as<char>() + r_pts, (size_t)total * sizeof(snk_new_point));
+    memcpy(out, out_b.at<char>(m->h_res.as<char>(), o_pts), (size_t)total * sizeof(snk_new_point));
     *n_out = total;
     return SNK_OK;
 }

@@ -16,9 +16,11 @@ import numpy as np
 
 import bow_numpy as BW
 import covis_numpy as CV
+import localmap_numpy as LM
 import mappoint_numpy as MP
 import p3p_numpy as P3
 import pgo_numpy as PG
+import scene_numpy as SN
 import sim3_numpy as S3
 import tri_numpy as TR
 from helpers import SEED, make_stereo_case, rand_desc
@@ -107,6 +109,46 @@ def covis_case(k):
     set_start, set_point = CV.frames_of(m, 41 + k, 12)
     q = np.random.default_rng(51 + k).permutation(300)[:40].astype(np.int32)
     return dict(m=m, q=q, set_start=np.asarray(set_start, np.int32), set_point=np.asarray(set_point, np.int32))
+
+
+# the local map at kf_cap 4 / pts_cap 64: three votes of localmap_numpy.select_case and three sets of gather_case(64) with at most four
+# local keyframes per case (the two halves of edge_case have maps of their own: gather does not read what select wrote)
+LMAP_PARAMS = dict(n_direct=2, n_direct_prob=1, n_indirect_prob=1, n_neighbours=2, kf_cap=4, seed=0)
+LMAP_PTS_CAP = 64
+LMAP_SELECT_SETS = ((1, 4, 8), (2, 5, 9), (3, 7, 11))  # case 0 ends on a KF_OVERFLOW, case 2 on the truncated vote
+LMAP_GATHER_SETS = (("mixed_seen", "cap", "collisions"), ("mixed", "cap+1", "chunk257"), ("shared_reversed", "cap_by_own", "empty_status"))
+
+
+def _lmap_gather_sets(g, sets):
+    """the sets `sets` of a localmap_numpy.gather_case as a case of their own, local_kf cut to kf_cap columns"""
+    cap = LMAP_PARAMS["kf_cap"]
+    assert np.all(g["local_kf"][sets][:, cap:] == -1)
+    own = [g["set_point"][g["set_start"][s]:g["set_start"][s + 1]] for s in sets]
+    return dict(m=g["m"], frame_id=g["frame_id"][sets], local_kf=np.ascontiguousarray(g["local_kf"][sets][:, :cap]), sel=g["sel"][sets],
+                set_start=LM.csr(own), set_point=np.concatenate(own).astype(np.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def lmap_case(k):
+    e = LM.edge_case(LMAP_PTS_CAP)
+    s, g = e["select"], e["gather"]
+    rows = list(LMAP_SELECT_SETS[k])
+    select = dict(s, conn=s["conn"][rows], vote=s["vote"][rows], frame_id=s["frame_id"][rows])
+    return dict(select=select, gather=_lmap_gather_sets(g, [g["what"][n] for n in LMAP_GATHER_SETS[k]]))
+
+
+# local BA windows at win_cap 4 / pt_cap 64 / obs_cap 256: scene_numpy.build_map with 16 features a keyframe, three of its QUERIES per case
+SCENE_PARAMS = dict(n_neighbours=2, n_last=1, win_cap=4, gyro_weight=2.0, acc_weight=0.5)
+SCENE_CAPS = dict(win_cap=4, pt_cap=64, img_cap=16, obs_cap=256)
+
+
+@functools.lru_cache(maxsize=None)
+def scene_map():
+    return SN.build_map(feats=16)
+
+
+def scene_queries(k):
+    return SN.QUERIES[k::3]  # (100, 5, 7), (45, 50, 110), (41, 60, 20): 50 is a bad query
 
 
 BOW_FRAME_COUNTS = (257, 65, 1000)
@@ -434,6 +476,44 @@ def run_covis(H, k):
     return out
 
 
+def make_lmap(device=0, stream=None):
+    from snake_slam_amd.localmap import LocalMapBuilder
+
+    st = _stream(device, stream)
+    return _base(device, st, [LocalMapBuilder(LMAP_PARAMS, device, st.cuda_stream)])
+
+
+def lmap_gather_bytes(b, g, pts_cap=LMAP_PTS_CAP):
+    m = g["m"]
+    return cat(*b.gather(*(m[a] for a in LM.GATHER_KEYS), m, g["frame_id"], g["local_kf"], g["sel"], g["set_start"], g["set_point"], pts_cap))
+
+
+def run_lmap(H, k):
+    """select, then gather"""
+    b, c = H["objs"][0], lmap_case(k % 3)
+    return cat(*b.select(*(c["select"][a] for a in LM.SELECT_KEYS))) + lmap_gather_bytes(b, c["gather"])
+
+
+def make_scene(device=0, stream=None):
+    from snake_slam_amd.scene import LocalSceneBuilder
+
+    st = _stream(device, stream)
+    return _base(device, st, [LocalSceneBuilder(SCENE_PARAMS, device, st.cuda_stream)])
+
+
+def scene_bytes(b, t, queries):
+    """window, then gather into zeroed rows (pt_id: -1)"""
+    from snake_slam_amd import scene as S
+
+    win, res = b.window(queries, t["kf_bad"], t["kf_prev"], t["conn_start"], t["conn_list"])
+    o = b.gather(t, win, res, SCENE_CAPS["pt_cap"], SCENE_CAPS["img_cap"], SCENE_CAPS["obs_cap"], out=S.host_outputs(len(queries), **SCENE_CAPS))
+    return cat(win, res, *(o[row[0]] for row in S.OUT_ROWS), o["result"])
+
+
+def run_scene(H, k):
+    return scene_bytes(H["objs"][0], scene_map(), scene_queries(k % 3))
+
+
 BOW_CAP = 1024  # the device batch's feature capacity: above every count of BOW_FRAME_COUNTS
 BOW_QCAP, BOW_Q = 64, 4
 
@@ -686,11 +766,13 @@ def run_pose(H, k):
 
 SEAMS = {"p3p": (make_p3p, run_p3p), "sim3": (make_sim3, run_sim3), "tri": (make_tri, run_tri), "mappoint": (make_mappoint, run_mappoint),
          "covis": (make_covis, run_covis), "bow": (make_bow, run_bow), "pgo": (make_pgo, run_pgo), "knn2": (make_knn2, run_knn2),
-         "stereo": (make_stereo, run_stereo), "track": (make_track, run_track), "pose": (make_pose, run_pose)}
+         "stereo": (make_stereo, run_stereo), "track": (make_track, run_track), "pose": (make_pose, run_pose), "lmap": (make_lmap, run_lmap),
+         "scene": (make_scene, run_scene)}
 # what runs on a snk_matcher (bow: its MatchBoW part, the vocabulary and the database have handles of their own)
-MATCHER_SEAMS = ("knn2", "stereo", "track", "pose", "p3p", "sim3", "tri", "mappoint", "covis", "bow")
-# the poison children: three groups, torch's import paid three times
-GROUPS = {"front": ("knn2", "stereo", "track", "pose", "tri"), "ransac": ("p3p", "sim3", "mappoint", "covis"), "loop": ("bow", "pgo")}
+MATCHER_SEAMS = ("knn2", "stereo", "track", "pose", "p3p", "sim3", "tri", "mappoint", "covis", "bow", "lmap", "scene")
+# the poison children: four groups, torch's import paid four times
+GROUPS = {"front": ("knn2", "stereo", "track", "pose", "tri"), "ransac": ("p3p", "sim3", "mappoint", "covis"), "loop": ("bow", "pgo"),
+          "map": ("lmap", "scene")}
 
 
 def run_on_matcher(name):
@@ -757,6 +839,11 @@ GROWTH_ITERATIONS = 8  # keeps the large calls far below a second of device time
 GROWTH_COVIS_CAP = 256
 GROWTH_SET_CAP = 512   # entries per padded vote set of the large covis call
 GROWTH_KNN2_TRAIN = 4096
+LMAP_POINT_BYTES = 1 + 4 + 24 + 24 + 32 + 4 + 4                        # a map point in snk_lmap_gather's input block: flags, last_seen and the five tables of snk_lmap_points
+LMAP_SET_RESULT_BYTES = LMAP_PTS_CAP * (96 + 4) + 4 + 16               # a set in its result block: the records, the ids, n_pts, the result
+SCENE_POINT_BYTES = 4 + 1 + 24                                         # a map point in snk_scene_gather's input block: obs_start, flags, position
+SCENE_ROW_BYTES = dict(img_cap=(4, 56, 1), pt_cap=(4, 24, 1, 1), obs_cap=(4, 4, 16, 8, 8, 8), win_cap=(80,))  # an item of every row output of snk_scene_out, by its cap
+SCENE_QUERY_RESULT_BYTES = sum(SCENE_CAPS[cap] * sum(items) for cap, items in SCENE_ROW_BYTES.items()) + 24  # a query in its result block
 POSE_MATCHES, POSE_MATCH_BYTES, POSE_RESULT_BYTES = 300, 24 + 32, 56 + 4  # pose_case: matches per problem; a match in the input block; a
 #                                                                           problem in the result block behind the outlier bytes
 
@@ -769,7 +856,10 @@ def growth_sizes():
     covis -- padded vote sets: the set array alone past `q` / `h_in` and the lists past `out` / `h_res`;
     knn2 -- queries: the result block past `out` / `h_res` (query + train is then past `q` / `h_in`);
     pose -- problems of pose_case(0): the result block (an outlier byte per match, a pose and a count per problem) past `h_res` (the
-    input is then past `q` / `h_in`)."""
+    input is then past `q` / `h_in`);
+    lmap -- sets of gather: the result block past `out` / `h_res`, and map points (behind the case's own, seen by nobody): the point tables
+    past `q` / `h_in`;
+    scene -- queries of gather and map points in the same way."""
     c = matcher_constants()
     dev, h_res = c["dev_capacity"], c["h_res_capacity"]
     return dict(p3p_problems=dev // (P3P_PAIR_BYTES * P3.MAX_PAIRS) + 1,
@@ -777,12 +867,14 @@ def growth_sizes():
                 mappoint_points=dev // MP_RESULT_BYTES + 1,
                 covis_sets=max(dev // (GROWTH_SET_CAP * 4), dev // (GROWTH_COVIS_CAP * COVIS_CONN_BYTES + COVIS_RESULT_BYTES)) + 1,
                 knn2_queries=dev // KNN2_BYTES + 1,
-                pose_problems=h_res // (POSE_MATCHES + POSE_RESULT_BYTES) + 1)
+                pose_problems=h_res // (POSE_MATCHES + POSE_RESULT_BYTES) + 1,
+                lmap_sets=dev // LMAP_SET_RESULT_BYTES + 1, lmap_points=dev // LMAP_POINT_BYTES + 1,
+                scene_queries=dev // SCENE_QUERY_RESULT_BYTES + 1, scene_points=dev // SCENE_POINT_BYTES + 1)
 
 
 def growth_requests(name):
     """{buffer: bytes the large call asks of it}, by the layout of the host entry (p3p.hip / sim3.hip ransac_host, snk_mappoint_refresh,
-    covis.hip run_host, snk_bf_knn2) -- at least: the per-problem records of the RANSACs come on top.  Every buffer named here must
+    covis.hip run_host, snk_bf_knn2, snk_lmap_gather, snk_scene_gather: stage.hpp pads every part to 16 bytes) -- at least: the per-problem records of the RANSACs come on top.  Every buffer named here must
     be reallocated by the call."""
     g = growth_sizes()
     if name == "p3p":
@@ -806,6 +898,16 @@ def growth_requests(name):
     if name == "pose":
         n = g["pose_problems"]
         return dict(q=n * POSE_MATCHES * POSE_MATCH_BYTES, h_in=n * POSE_MATCHES * POSE_MATCH_BYTES, h_res=n * (POSE_MATCHES + POSE_RESULT_BYTES))
+    if name == "lmap":
+        n, pts = g["lmap_sets"], g["lmap_points"]  # the point parts: pt_flags | pt_last_seen | pos | normal | desc | ref_depth | ref_level
+        bytes_in = sum(align16(pts * b) for b in (1, 4, 24, 24, 32, 4, 4))
+        out = align16(n * LMAP_PTS_CAP * 96) + align16(n * LMAP_PTS_CAP * 4) + align16(n * 4) + n * 16  # lm_pts | lm_point | n_pts | result
+        return dict(q=bytes_in, h_in=bytes_in, out=out, h_res=out)
+    if name == "scene":
+        n, pts = g["scene_queries"], g["scene_points"]  # the point parts: obs_start | pt_flags | pt_pos
+        bytes_in = align16((pts + 1) * 4) + align16(pts) + align16(pts * 24)
+        out = sum(align16(n * SCENE_CAPS[cap] * b) for cap, items in SCENE_ROW_BYTES.items() for b in items) + align16(n * 24)  # the rows | result
+        return dict(q=bytes_in, h_in=bytes_in, out=out, h_res=out)
     raise KeyError(name)
 
 
@@ -839,6 +941,24 @@ def growth_case(name):
     if name == "pose":
         pr = pose_case(0)
         return [dict(pose=pr["pose0"], wps=pr["wps"], obs=pr["obs"])] * g["pose_problems"]
+    if name == "lmap":
+        # the three sets of case 0 in turn; the point tables go on behind the case's own points with zeros
+        gc = LM.edge_case(LMAP_PTS_CAP)["gather"]
+        sets = [gc["what"][n] for n in LMAP_GATHER_SETS[0]]
+        c = _lmap_gather_sets(gc, [sets[i % 3] for i in range(g["lmap_sets"])])
+        m = dict(c["m"])
+        for key in ("pt_flags", "pt_last_seen") + LM.POINT_KEYS:
+            m[key] = np.concatenate([m[key], np.zeros((g["lmap_points"] - len(m[key]),) + m[key].shape[1:], m[key].dtype)])
+        return dict(c, m=m)
+    if name == "scene":
+        # the queries of case 0 in turn; points without observations behind the map's own
+        t = dict(scene_map())
+        more = g["scene_points"] - len(t["pt_flags"])
+        t["obs_start"] = np.concatenate([t["obs_start"], np.full(more, t["obs_start"][-1], np.int32)])
+        t["pt_flags"] = np.concatenate([t["pt_flags"], np.zeros(more, np.uint8)])
+        t["pt_pos"] = np.concatenate([t["pt_pos"], np.zeros((more, 3))])
+        q = scene_queries(0)
+        return t, [q[i % 3] for i in range(g["scene_queries"])]
     raise KeyError(name)
 
 
@@ -874,13 +994,17 @@ def growth_call(name, H):
         import pose_helpers as PH
 
         return b"".join(cat(pose, outl) + i32(inl) for pose, outl, inl in o.refine_batch(PH.CAM, c))
+    if name == "lmap":
+        return lmap_gather_bytes(o, c)
+    if name == "scene":
+        return scene_bytes(o, *c)
     raise KeyError(name)
 
 
 # No growth case: bow (MatchBoW takes at most 2048 features a keyframe, 66 KB a side: it cannot outgrow a buffer); tri and stereo (their
 # inputs are whole keyframes / images, and one past 5 MiB of scratch has some 90 000 keypoints, beyond what the stereo row index holds);
 # track (82 000 local-map points would do it; not built: the seam rebinds its frame in every run, which the bound-frame check needs kept)
-GROWTH_SEAMS = ("p3p", "sim3", "mappoint", "covis", "knn2", "pose")
+GROWTH_SEAMS = ("p3p", "sim3", "mappoint", "covis", "knn2", "pose", "lmap", "scene")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

@@ -8,17 +8,19 @@ import numpy as np
 import backend_cases as BC
 import bow_numpy as BW
 import covis_numpy as CV
+import localmap_numpy as LM
 import mappoint_numpy as MP
 import p3p_numpy as P3
+import scene_numpy as SN
 import sim3_numpy as S3
 import tri_numpy as TR
 
 
 def test_the_table_names_every_seam_once():
-    assert set(BC.SEAMS) == {"p3p", "sim3", "tri", "mappoint", "covis", "bow", "pgo", "knn2", "stereo", "track", "pose"}
+    assert set(BC.SEAMS) == {"p3p", "sim3", "tri", "mappoint", "covis", "bow", "pgo", "knn2", "stereo", "track", "pose", "lmap", "scene"}
     assert set(BC.MATCHER_SEAMS) == set(BC.SEAMS) - {"pgo"}
     grouped = [s for g in BC.GROUPS.values() for s in g]
-    assert sorted(grouped) == sorted(BC.SEAMS) and len(BC.GROUPS) <= 3
+    assert sorted(grouped) == sorted(BC.SEAMS) and len(BC.GROUPS) <= 4 and BC.GROUPS["map"] == ("lmap", "scene")
 
 
 def test_mappoint_case_takes_both_forms_under_both_rules():
@@ -45,6 +47,37 @@ def test_covis_case_cuts_a_list_at_the_cap():
         assert np.any(res["n_conn"] == BC.COVIS_CAP) and np.all(res["status"] != CV.BAD_INDEX)
         assert np.any(conn["kf"] >= 0)
     assert np.any(res_u["n_found"] < BC.COVIS_CAP), "and one is not"
+
+
+def test_lmap_cases_select_and_gather_at_their_small_caps():
+    """kf_cap 4 and pts_cap 64: lists are built, one overflows its four keyframes, a vote is passed through as truncated; points are kept at
+    the cap, refused above it, found on one table slot."""
+    statuses, points = [], []
+    for k in range(3):
+        c = BC.lmap_case(k)
+        s, g = c["select"], c["gather"]
+        assert len(s["vote"]) == len(g["sel"]) == 3 and g["local_kf"].shape == (3, BC.LMAP_PARAMS["kf_cap"])
+        local, res = LM.select(*(s[a] for a in LM.SELECT_KEYS), BC.LMAP_PARAMS)
+        assert local.shape == (3, 4) and np.all((local >= 0).sum(1) == res["n_local"])
+        statuses += res["status"].tolist()
+        _, ids, n_pts, gres = LM.gather(g["m"], g["frame_id"], g["local_kf"], g["sel"], g["set_start"], g["set_point"], BC.LMAP_PTS_CAP)
+        assert np.all((ids >= 0).sum(1) == n_pts)
+        statuses += gres["status"].tolist()
+        points += n_pts.tolist()
+    assert {LM.OK, LM.KF_OVERFLOW, LM.TRUNCATED, LM.PTS_OVERFLOW} <= set(statuses) and statuses.count(LM.OK) >= 12
+    assert BC.LMAP_PTS_CAP in points and max(points) == BC.LMAP_PTS_CAP and 0 < min(p for p in points if p) < 10
+
+
+def test_scene_cases_fit_their_small_caps():
+    """win_cap 4, pt_cap 64, obs_cap 256: every query but the bad one gives a scene with fixed cameras, records and, somewhere, constraints"""
+    t, p, caps = BC.scene_map(), BC.SCENE_PARAMS, BC.SCENE_CAPS
+    got = [SN.local_scene(t, q, p["n_neighbours"], p["n_last"], caps["win_cap"], caps["pt_cap"], caps["img_cap"], caps["obs_cap"], p["gyro_weight"],
+                          p["acc_weight"])[1] for k in range(3) for q in BC.scene_queries(k)]
+    assert sorted(q for k in range(3) for q in BC.scene_queries(k)) == sorted(SN.QUERIES) and len(got) == 9
+    assert [s["status"] for s in got].count(SN.OK) == 8 and [s["status"] for s in got].count(SN.SKIPPED) == 1
+    ok = [s for s in got if s["status"] == SN.OK]
+    assert all(s["n_img"] > s["n_window"] >= 2 and s["n_pt"] > 16 and s["n_obs"] > s["n_pt"] for s in ok)
+    assert max(s["n_window"] for s in ok) == caps["win_cap"] and any(s["n_rpc"] for s in ok) and any(not s["n_rpc"] for s in ok)
 
 
 def test_tri_case_commits_a_pair_and_rejects_another():
@@ -118,3 +151,12 @@ def test_growth_cases_are_the_smallest_that_outgrow_what_a_handle_holds():
     assert len(start) - 1 == g["covis_sets"] and sets.shape == (g["covis_sets"], BC.GROWTH_SET_CAP) and np.any(sets >= 0)
     q, t = BC.growth_case("knn2")
     assert len(q) == g["knn2_queries"] and len(t) == BC.GROWTH_KNN2_TRAIN
+    # the map seams: one set / query fewer leaves `out`, one map point fewer leaves `q` as it is (48 / 240 bytes: the padding of the parts)
+    assert (g["lmap_sets"] - 1) * BC.LMAP_SET_RESULT_BYTES + 48 <= dev and (g["lmap_points"] - 1) * BC.LMAP_POINT_BYTES <= dev
+    assert (g["scene_queries"] - 1) * BC.SCENE_QUERY_RESULT_BYTES + 240 <= dev and (g["scene_points"] - 1) * BC.SCENE_POINT_BYTES <= dev
+    lm = BC.growth_case("lmap")
+    assert len(lm["sel"]) == len(lm["frame_id"]) == len(lm["set_start"]) - 1 == g["lmap_sets"] and lm["local_kf"].shape == (g["lmap_sets"], 4)
+    assert all(len(lm["m"][key]) == g["lmap_points"] for key in ("pt_flags", "pt_last_seen") + LM.POINT_KEYS)
+    t, queries = BC.growth_case("scene")
+    assert len(queries) == g["scene_queries"] and len(t["pt_flags"]) == len(t["pt_pos"]) == len(t["obs_start"]) - 1 == g["scene_points"]
+    assert t["obs_start"][-1] == len(t["obs"]) and np.all(np.diff(t["obs_start"]) >= 0)

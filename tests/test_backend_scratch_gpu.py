@@ -1,6 +1,6 @@
 """GPU: the back-end entry points outside a fresh handle that one module has to itself (tests/backend_cases.py has the seams).
 
-* poison: every seam with SNK_DEBUG_POISON=1 -- fresh device scratch and fresh pinned staging memory filled with 0xCD -- in three child
+* poison: every seam with SNK_DEBUG_POISON=1 -- fresh device scratch and fresh pinned staging memory filled with 0xCD -- in four child
   processes (the switch is read once);
 * one handle: the seams that run on a snk_matcher, all on ONE handle, interleaved in the reference's frame order and in a seeded
   shuffle, and the three pieces of state a handle keeps between calls ("One handle, many entry points");
@@ -18,8 +18,8 @@ from helpers import SEED
 pytestmark = pytest.mark.gpu
 
 # Tracking's order inside a frame, then relocalisation, local mapping and loop closing (reference System: Preprocess -> TrackingCoarse /
-# TrackingFine -> TrackBruteForce -> LocalMapping -> LoopClosing)
-FRAME_ORDER = ("stereo", "track", "pose", "knn2", "p3p", "tri", "mappoint", "covis", "bow", "sim3")
+# TrackingFine, whose local map is lmap -> TrackBruteForce -> LocalMapping, whose local BA window is scene -> LoopClosing)
+FRAME_ORDER = ("stereo", "track", "pose", "lmap", "knn2", "p3p", "tri", "mappoint", "covis", "scene", "bow", "sim3")
 
 
 def where(got, want):

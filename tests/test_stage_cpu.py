@@ -1,0 +1,65 @@
+"""CPU: snake_slam_amd/csrc/stage.hpp -- the layout every map-side host entry stages its arrays in -- compiled with plain g++ (no HIP)
+into tests/cpp/stage_driver.cpp.  Offsets, `bytes` and `end()` must equal the restatement below; `copy` must write exactly the parts
+that have a source and a size, and leave every other byte of the buffer (the padding, the parts without a source, 16 bytes behind the
+block) as it found it."""
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+SIZES = [0, 1, 15, 16, 17, 0, 4096]
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("stage") / "stage_driver"
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Werror", f"-I{ROOT / 'snake_slam_amd' / 'csrc'}", str(ROOT / "tests" / "cpp" / "stage_driver.cpp"),
+           "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+def layout(sizes):
+    """(offsets, bytes, end): a part begins where the padded parts before it end"""
+    offsets = [sum((s + 15) & ~15 for s in sizes[:i]) for i in range(len(sizes))]
+    total = sum((s + 15) & ~15 for s in sizes)
+    return offsets, total, (offsets[-1] + sizes[-1] if sizes else 0)
+
+
+def ask(driver, mask, sizes):
+    p = subprocess.run([str(driver), mask, *map(str, sizes)], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, (p.returncode, p.stderr)
+    out = dict(line.split(" ", 1) if " " in line else (line, "") for line in p.stdout.splitlines())
+    b, e = out["bytes"].split(" end ")
+    return ([int(x) for x in out["offsets"].split()], int(b), int(e), [int(x) for x in out["at"].split()], bytes.fromhex(out["buffer"].strip()))
+
+
+@pytest.mark.parametrize("mask", ["1111111", "1101011", "0000000", "0111110"])
+def test_layout_and_copy(driver, mask):
+    offsets, total, end, at, buf = ask(driver, mask, SIZES)
+    assert (offsets, total, end) == layout(SIZES) == ([0, 0, 16, 32, 48, 80, 80], 4176, 4176)
+    assert at == offsets and all(o % 16 == 0 for o in offsets)
+    want = bytearray(b"\xcd" * (total + 16))
+    for i, (o, s, m) in enumerate(zip(offsets, SIZES, mask)):
+        if m == "1":
+            want[o:o + s] = bytes((7 * j + i) & 0x7F for j in range(s))
+    assert buf == bytes(want)
+    # what the comparison above contains: padding behind the parts of 1, 15 and 17 bytes, and a part without a source, all untouched
+    assert buf[1:16] == b"\xcd" * 15 and buf[31:32] == b"\xcd" and buf[65:80] == b"\xcd" * 15 and buf[total:] == b"\xcd" * 16
+    if mask[6] == "0":
+        assert buf[80:total] == b"\xcd" * 4096
+
+
+def test_end_is_the_last_part_unpadded(driver):
+    for sizes in ([16, 1], [1, 16], [5], [0], [40, 0], [3, 24 * 7]):
+        offsets, total, end, _, _ = ask(driver, "1" * len(sizes), sizes)
+        assert (offsets, total, end) == layout(sizes)
+        assert end == offsets[-1] + sizes[-1] and end <= total < end + 16
+
+
+def test_empty_block(driver):
+    offsets, total, end, at, buf = ask(driver, "", [])
+    assert (offsets, total, end, at) == ([], 0, 0, []) == (*layout([]), [])
+    assert buf == b"\xcd" * 16
