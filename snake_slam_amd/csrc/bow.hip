@@ -834,30 +834,28 @@ int snk_bow_transform(snk_bow_vocab* v, const uint64_t (*desc)[4], int n, int le
     SNK_REQUIRE(n == 0 || (words && values && node_id && features && word_of_feature && node_of_feature), "NULL output array with n > 0");
     SNK_HIP_CHECK(hipSetDevice(v->device));
     const size_t cap = (size_t)(n > 0 ? n : 1);
-    // in: n | desc.  out: words | node_id | node_start | features | word_of | node_of | n_words, n_nodes | values
-    const size_t i_desc = 16, in_b = i_desc + cap * 32;
-    const size_t o_nid = cap * 4, o_ns = o_nid + cap * 4, o_ft = o_ns + (cap + 1) * 4, o_wof = o_ft + cap * 4, o_nof = o_wof + cap * 4,
-                 o_cnt = o_nof + cap * 4, o_val = align16(o_cnt + 8), out_b = o_val + cap * 8;
+    // in: n (a 16-byte header, the rest zero) | desc.  out: words | node_id | node_start | features | word_of | node_of | n_words, n_nodes | values
+    // through the vocabulary's own buffers and stream
+    Block in, out;
+    const int head[4] = {n, 0, 0, 0};
+    const int i_n = in.add(head, 16), i_desc = in.add(n > 0 ? desc : nullptr, cap * 32);
+    const int r_w = out.add(nullptr, cap * 4), r_nid = out.add(nullptr, cap * 4), r_ns = out.add(nullptr, (cap + 1) * 4), r_ft = out.add(nullptr, cap * 4),
+              r_wof = out.add(nullptr, cap * 4), r_nof = out.add(nullptr, cap * 4), r_cnt = out.add(nullptr, 8), r_val = out.add(nullptr, cap * 8);
     int rc;
-    if ((rc = v->in.reserve(in_b)) != SNK_OK || (rc = v->out.reserve(out_b)) != SNK_OK || (rc = v->h_in.reserve(in_b)) != SNK_OK ||
-        (rc = v->h_out.reserve(out_b)) != SNK_OK)
-        return rc;
-    char* hi = v->h_in.as<char>();
-    memset(hi, 0, i_desc);
-    *reinterpret_cast<int*>(hi) = n;
-    if (n > 0) memcpy(hi + i_desc, desc, (size_t)n * 32);
+    if ((rc = stage_reserve(v->in, in.bytes, v->h_in, in.bytes, v->out, out.end(), v->h_out, out.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(in, v->h_in, v->in, v->stream)) != SNK_OK) return rc;
     char* di = v->in.as<char>();
     char* d  = v->out.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(di, hi, i_desc + (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
-    BowOut O{reinterpret_cast<int*>(d), reinterpret_cast<double*>(d + o_val), reinterpret_cast<int*>(d + o_cnt), reinterpret_cast<int*>(d + o_nid),
-             reinterpret_cast<int*>(d + o_ns), reinterpret_cast<int*>(d + o_ft), reinterpret_cast<int*>(d + o_cnt + 4)};
-    if ((rc = transform_launch(v, reinterpret_cast<const u64*>(di + i_desc), reinterpret_cast<const int*>(di), 1, (int)cap, levelsup, O,
-                               reinterpret_cast<int*>(d + o_wof), reinterpret_cast<int*>(d + o_nof))) != SNK_OK)
+    BowOut O{out.at<int>(d, r_w),  out.at<double>(d, r_val), out.at<int>(d, r_cnt), out.at<int>(d, r_nid),
+             out.at<int>(d, r_ns), out.at<int>(d, r_ft),     out.at<int>(d, r_cnt) + 1};
+    if ((rc = transform_launch(v, in.at<const u64>(di, i_desc), in.at<const int>(di, i_n), 1, (int)cap, levelsup, O, out.at<int>(d, r_wof),
+                               out.at<int>(d, r_nof))) != SNK_OK)
         return rc;
-    char* h = v->h_out.as<char>();
-    if ((rc = copy_sync(h, d, out_b, hipMemcpyDeviceToHost, v->stream)) != SNK_OK) return rc;
-    const int nw = reinterpret_cast<const int*>(h + o_cnt)[0], nn = reinterpret_cast<const int*>(h + o_cnt)[1];
-    if (nw < 0 || nw > n || nn < 0 || nn > n || reinterpret_cast<const int*>(h + o_ns)[nn] < 0 || reinterpret_cast<const int*>(h + o_ns)[nn] > n)
+    if ((rc = stage_download(v->h_out, 0, v->out, 0, out.end(), v->stream)) != SNK_OK) return rc;
+    char* h       = v->h_out.as<char>();
+    const int* ns = out.at<const int>(h, r_ns);
+    const int nw = out.at<const int>(h, r_cnt)[0], nn = out.at<const int>(h, r_cnt)[1];
+    if (nw < 0 || nw > n || nn < 0 || nn > n || ns[nn] < 0 || ns[nn] > n)
     {
         set_error("bow: device returned %d words / %d nodes for %d features", nw, nn, n);
         return SNK_ERR_HIP;
@@ -866,16 +864,16 @@ int snk_bow_transform(snk_bow_vocab* v, const uint64_t (*desc)[4], int n, int le
     *n_nodes = nn;
     if (nw > 0)
     {
-        memcpy(words, h, (size_t)nw * 4);
-        memcpy(values, h + o_val, (size_t)nw * 8);
+        memcpy(words, out.at<char>(h, r_w), (size_t)nw * 4);
+        memcpy(values, out.at<char>(h, r_val), (size_t)nw * 8);
     }
-    memcpy(node_start, h + o_ns, (size_t)(nn + 1) * 4);
-    if (nn > 0) memcpy(node_id, h + o_nid, (size_t)nn * 4);
+    memcpy(node_start, ns, (size_t)(nn + 1) * 4);
+    if (nn > 0) memcpy(node_id, out.at<char>(h, r_nid), (size_t)nn * 4);
     if (n > 0)
     {
-        memcpy(features, h + o_ft, (size_t)reinterpret_cast<const int*>(h + o_ns)[nn] * 4);
-        memcpy(word_of_feature, h + o_wof, (size_t)n * 4);
-        memcpy(node_of_feature, h + o_nof, (size_t)n * 4);
+        memcpy(features, out.at<char>(h, r_ft), (size_t)ns[nn] * 4);
+        memcpy(word_of_feature, out.at<char>(h, r_wof), (size_t)n * 4);
+        memcpy(node_of_feature, out.at<char>(h, r_nof), (size_t)n * 4);
     }
     return SNK_OK;
 }
@@ -1115,68 +1113,65 @@ int snk_match_loop_bow(snk_matcher* m, const uint64_t (*desc1)[4], const uint8_t
     }
     SNK_HIP_CHECK(hipSetDevice(m->device));
     // per side: n, n_nodes | desc | node_id | node_start | features | has_mp
-    size_t off[2][6], at = 0;
+    // (every array has `cap` entries and is filled as far as the keyframe has any: the parts have no source, the rest of the block is zero)
+    enum { HEAD, DESC, NODE_ID, NODE_START, FEATURES, HAS_MP };
+    Block in, out;
+    int part[2][6];
     size_t cap[2];
     for (int s = 0; s < 2; ++s)
     {
-        cap[s]    = (size_t)std::max(std::max(nf[s], bw[s]->n_nodes), 1);
-        off[s][0] = at;
-        off[s][1] = at + 16;
-        off[s][2] = off[s][1] + cap[s] * 32;
-        off[s][3] = off[s][2] + cap[s] * 4;
-        off[s][4] = off[s][3] + (cap[s] + 1) * 4;
-        off[s][5] = off[s][4] + cap[s] * 4;
-        at        = align16(off[s][5] + cap[s]);
+        cap[s] = (size_t)std::max(std::max(nf[s], bw[s]->n_nodes), 1);
+        const size_t bytes[6] = {8, cap[s] * 32, cap[s] * 4, (cap[s] + 1) * 4, cap[s] * 4, cap[s]};
+        for (int k = 0; k < 6; ++k) part[s][k] = in.add(nullptr, bytes[k]);
     }
-    const size_t in_b = at, o_pairs = align16(16 + cap[0] * 4), out_b = o_pairs + cap[0] * 8;  // out: n_pairs | match12 | pairs
+    // out: n_pairs | match12 | pairs (device only)
+    const int r_cnt = out.add(nullptr, 4), r_match = out.add(nullptr, cap[0] * 4), r_pairs = out.add(nullptr, cap[0] * 8);
     int rc;
-    if ((rc = m->q.reserve(in_b)) != SNK_OK || (rc = m->out.reserve(out_b)) != SNK_OK || (rc = m->h_in.reserve(in_b)) != SNK_OK ||
-        (rc = m->h_res.reserve(out_b)) != SNK_OK)
-        return rc;
+    if ((rc = stage_reserve(m, in.bytes, out.end())) != SNK_OK) return rc;
     char* h = m->h_in.as<char>();
-    memset(h, 0, in_b);
+    memset(h, 0, in.bytes);
     const uint64_t (*dsc[2])[4] = {desc1, desc2};
     const uint8_t* hmp[2]       = {has_mp1, has_mp2};
     for (int s = 0; s < 2; ++s)
     {
         const snk_bow_features& f = *bw[s];
-        int* head                 = reinterpret_cast<int*>(h + off[s][0]);
+        int* head                 = in.at<int>(h, part[s][HEAD]);
         head[0]                   = nf[s];
         head[1]                   = f.n_nodes;
         if (nf[s] > 0)
         {
-            memcpy(h + off[s][1], dsc[s], (size_t)nf[s] * 32);
-            memcpy(h + off[s][5], hmp[s], (size_t)nf[s]);
+            memcpy(in.at<char>(h, part[s][DESC]), dsc[s], (size_t)nf[s] * 32);
+            memcpy(in.at<char>(h, part[s][HAS_MP]), hmp[s], (size_t)nf[s]);
         }
         if (f.n_nodes > 0)
         {
-            memcpy(h + off[s][2], f.node_id, (size_t)f.n_nodes * 4);
-            memcpy(h + off[s][3], f.node_start, (size_t)(f.n_nodes + 1) * 4);
-            if (f.node_start[f.n_nodes] > 0) memcpy(h + off[s][4], f.features, (size_t)f.node_start[f.n_nodes] * 4);
+            memcpy(in.at<char>(h, part[s][NODE_ID]), f.node_id, (size_t)f.n_nodes * 4);
+            memcpy(in.at<char>(h, part[s][NODE_START]), f.node_start, (size_t)(f.n_nodes + 1) * 4);
+            if (f.node_start[f.n_nodes] > 0) memcpy(in.at<char>(h, part[s][FEATURES]), f.features, (size_t)f.node_start[f.n_nodes] * 4);
         }
     }
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
     char* d = m->q.as<char>();
     char* o = m->out.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(d, h, in_b, hipMemcpyHostToDevice, m->stream));
     MatchSide S[2];
     for (int s = 0; s < 2; ++s)
-        S[s] = MatchSide{reinterpret_cast<const u64*>(d + off[s][1]), reinterpret_cast<const int*>(d + off[s][0]),
-                         reinterpret_cast<const u8*>(d + off[s][5]), reinterpret_cast<const int*>(d + off[s][2]),
-                         reinterpret_cast<const int*>(d + off[s][3]), reinterpret_cast<const int*>(d + off[s][4]),
-                         reinterpret_cast<const int*>(d + off[s][0] + 4), (int)cap[s]};
-    hipLaunchKernelGGL(bow_match_kernel, dim3(1), dim3(256), 0, m->stream, S[0], S[1], threshold, ratio, reinterpret_cast<int*>(o + 16),
-                       reinterpret_cast<int*>(o + o_pairs), reinterpret_cast<int*>(o));
+        S[s] = MatchSide{in.at<const u64>(d, part[s][DESC]),       in.at<const int>(d, part[s][HEAD]),       in.at<const u8>(d, part[s][HAS_MP]),
+                         in.at<const int>(d, part[s][NODE_ID]),    in.at<const int>(d, part[s][NODE_START]), in.at<const int>(d, part[s][FEATURES]),
+                         in.at<const int>(d, part[s][HEAD]) + 1,   (int)cap[s]};
+    hipLaunchKernelGGL(bow_match_kernel, dim3(1), dim3(256), 0, m->stream, S[0], S[1], threshold, ratio, out.at<int>(o, r_match),
+                       out.at<int>(o, r_pairs), out.at<int>(o, r_cnt));
     SNK_LAUNCH_CHECK();
-    char* back = m->h_res.as<char>();
-    if ((rc = copy_sync(back, o, o_pairs, hipMemcpyDeviceToHost, m->stream)) != SNK_OK) return rc;
-    const int k = *reinterpret_cast<const int*>(back);
+    const size_t back_b = out.parts[(size_t)r_pairs].offset;  // n_pairs | match12 come back
+    if ((rc = stage_download(m, 0, back_b)) != SNK_OK) return rc;
+    char* back  = m->h_res.as<char>();
+    const int k = *out.at<const int>(back, r_cnt);
     if (k < 0 || k > n1)
     {
         set_error("bow: device returned %d matches for %d features", k, n1);
         return SNK_ERR_HIP;
     }
     *n_matches = k;
-    if (n1 > 0) memcpy(match12, back + 16, (size_t)n1 * 4);
+    if (n1 > 0) memcpy(match12, out.at<char>(back, r_match), (size_t)n1 * 4);
     return SNK_OK;
 }
 }

@@ -1006,19 +1006,17 @@ int snk_bf_knn2(snk_matcher* m, const uint64_t (*query)[4], int nq, const uint64
     SNK_HIP_CHECK(hipSetDevice(m->device));
     int rc;
     // query | train in ONE device block, through the pinned staging buffer: one upload, one download (see matcher_handle.hpp)
-    const size_t qb = (size_t)nq * 32, tb = (size_t)(nt > 0 ? nt : 1) * 32, ob = (size_t)nq * sizeof(snk_knn2);
-    if ((rc = m->q.reserve(qb + tb)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(ob)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(qb + tb)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(ob)) != SNK_OK) return rc;
-    memcpy(m->h_in.p, query, qb);
-    if (nt > 0) memcpy(m->h_in.as<char>() + qb, train, (size_t)nt * 32);
-    SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, qb + (nt > 0 ? (size_t)nt * 32 : 0), hipMemcpyHostToDevice, m->stream));
-    rc = launch_knn2(m, m->q.as<uint64_t>(), nullptr, nq, nq, reinterpret_cast<const uint64_t*>(m->q.as<char>() + qb), nullptr,
-                     nt > 0 ? nt : 1, nt, 1, m->out.as<snk_knn2>());
+    // (an empty train set still has room for one descriptor: the kernels' capacity is >= 1)
+    Block in;
+    const size_t ob = (size_t)nq * sizeof(snk_knn2);
+    const int i_q = in.add(query, (size_t)nq * 32), i_t = in.add(nt > 0 ? train : nullptr, (size_t)(nt > 0 ? nt : 1) * 32);
+    if ((rc = stage_reserve(m, in.bytes, ob)) != SNK_OK) return rc;
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char* d = m->q.as<char>();
+    rc      = launch_knn2(m, in.at<const uint64_t>(d, i_q), nullptr, nq, nq, in.at<const uint64_t>(d, i_t), nullptr, nt > 0 ? nt : 1, nt, 1,
+                          m->out.as<snk_knn2>());
     if (rc != SNK_OK) return rc;
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, m->out.p, ob, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if ((rc = stage_download(m, 0, ob)) != SNK_OK) return rc;
     memcpy(out, m->h_res.p, ob);
     return SNK_OK;
 }
@@ -1046,21 +1044,19 @@ int snk_bf_filter(snk_matcher* m, const snk_knn2* knn, int nq, int threshold, fl
     SNK_HIP_CHECK(hipSetDevice(m->device));
     int rc;
     // aux: count (16 bytes) | pairs: ONE copy back (the count first and the n pairs after it were two round trips)
-    const size_t kb = (size_t)nq * sizeof(snk_knn2), pb = 16 + (size_t)nq * 8;
-    if ((rc = m->out.reserve(kb)) != SNK_OK) return rc;
-    if ((rc = m->aux.reserve(pb)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(kb)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(pb)) != SNK_OK) return rc;
-    memcpy(m->h_in.p, knn, kb);
-    SNK_HIP_CHECK(hipMemcpyAsync(m->out.p, m->h_in.p, kb, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(bf_filter_kernel, dim3(1), dim3(256), 0, m->stream, m->out.as<snk_knn2>(), (const int*)nullptr,
+    // (the kNN-2 records go up into `out`, where snk_bf_knn2 leaves them on the device)
+    Block in, res;
+    const int i_knn = in.add(knn, (size_t)nq * sizeof(snk_knn2)), r_cnt = res.add(nullptr, 4), r_pairs = res.add(nullptr, (size_t)nq * 8);
+    if ((rc = stage_reserve(m->out, in.bytes, m->h_in, in.bytes, m->aux, res.end(), m->h_res, res.end())) != SNK_OK) return rc;
+    if ((rc = stage_upload(in, m->h_in, m->out, m->stream)) != SNK_OK) return rc;
+    char* ab = m->aux.as<char>();
+    hipLaunchKernelGGL(bf_filter_kernel, dim3(1), dim3(256), 0, m->stream, in.at<const snk_knn2>(m->out.as<char>(), i_knn), (const int*)nullptr,
                        nq, nq, threshold, ratio, definition(DEF_BF_FILTER_THRESHOLD_STRICT), definition(DEF_BF_FILTER_RATIO_STRICT),
-                       reinterpret_cast<int2*>(m->aux.as<char>() + 16), m->aux.as<int>());
+                       res.at<int2>(ab, r_pairs), res.at<int>(ab, r_cnt));
     SNK_LAUNCH_CHECK();
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, m->aux.p, pb, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const int n = *m->h_res.as<int>();
-    if (n > 0) memcpy(pairs, m->h_res.as<char>() + 16, (size_t)n * 8);
+    if ((rc = stage_download(m->h_res, 0, m->aux, 0, res.end(), m->stream)) != SNK_OK) return rc;
+    const int n = *res.at<int>(m->h_res.as<char>(), r_cnt);
+    if (n > 0) memcpy(pairs, res.at<char>(m->h_res.as<char>(), r_pairs), (size_t)n * 8);
     *n_pairs = n;
     return SNK_OK;
 }
@@ -1089,6 +1085,12 @@ static int make_scales(const float* level_scale, int n_levels, LevelScales* ls)
     return SNK_OK;
 }
 
+static bool stereo_force_network()
+{
+    static const bool v = getenv("SNK_STEREO_SORT_NETWORK") != nullptr;  // A/B, tests: the bitonic network
+    return v;
+}
+
 int snk_stereo_match(snk_matcher* m, const snk_kp64* left, const uint64_t (*desc_left)[4], int nl,
                      const snk_kp64* right, const uint64_t (*desc_right)[4], int nr, double bf, const float* level_scale,
                      int n_levels, int relaxed, float* right_points, float* depth, int* n_matches)
@@ -1104,34 +1106,27 @@ int snk_stereo_match(snk_matcher* m, const snk_kp64* left, const uint64_t (*desc
     if (nl == 0 || nr == 0) return SNK_OK;
     SNK_REQUIRE(left && desc_left && right && desc_right && right_points && depth, "NULL buffer");
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    const size_t kl = (size_t)nl * sizeof(snk_kp64), kr = (size_t)nr * sizeof(snk_kp64);
     // ONE device block (aux): left kps | right kps | left descriptors | right descriptors | right_points | depth | count, filled through
     // the pinned staging buffer with one copy; right_points | depth | count come back with one copy (nine copies from / to pageable
     // memory before round 4)
-    auto al16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_kr = al16(kl), o_dl = al16(o_kr + kr), o_dr = al16(o_dl + (size_t)nl * 32), o_rp = al16(o_dr + (size_t)nr * 32);
-    const size_t o_dp = o_rp + (size_t)nl * 4, o_cnt = o_dp + (size_t)nl * 4, in_b = o_cnt + 4, res_b = in_b - o_rp;
-    if ((rc = m->aux.reserve(in_b)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in_b)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(res_b)) != SNK_OK) return rc;
-    char* ab   = m->aux.as<char>();
-    char* hb   = m->h_in.as<char>();
-    float* rp  = reinterpret_cast<float*>(ab + o_rp);
-    float* dp  = reinterpret_cast<float*>(ab + o_dp);
-    int* d_cnt = reinterpret_cast<int*>(ab + o_cnt);
-    const uint4* d_dl = reinterpret_cast<const uint4*>(ab + o_dl);
-    const uint4* d_dr = reinterpret_cast<const uint4*>(ab + o_dr);
-    memcpy(hb, left, kl);
-    memcpy(hb + o_kr, right, kr);
-    memcpy(hb + o_dl, desc_left, (size_t)nl * 32);
-    memcpy(hb + o_dr, desc_right, (size_t)nr * 32);
-    memcpy(hb + o_rp, right_points, (size_t)nl * 4);
-    memcpy(hb + o_dp, depth, (size_t)nl * 4);
-    memset(hb + o_cnt, 0, 4);
-    SNK_HIP_CHECK(hipMemcpyAsync(ab, hb, in_b, hipMemcpyHostToDevice, m->stream));
-    const u32* srt = nullptr;
-    static const bool sort_network = getenv("SNK_STEREO_SORT_NETWORK") != nullptr;  // A/B, tests: the bitonic network
-    const StereoForm form = stereo_host_form(nr, sort_network);
+    Block blk;
+    const int zero = 0;
+    const int i_kl = blk.add(left, (size_t)nl * sizeof(snk_kp64)), i_kr = blk.add(right, (size_t)nr * sizeof(snk_kp64)),
+              i_dl = blk.add(desc_left, (size_t)nl * 32), i_dr = blk.add(desc_right, (size_t)nr * 32), i_rp = blk.add(right_points, (size_t)nl * 4),
+              i_dp = blk.add(depth, (size_t)nl * 4), i_cnt = blk.add(&zero, 4);
+    const size_t tail = blk.parts[(size_t)i_rp].offset, res_b = blk.end() - tail;
+    if ((rc = stage_reserve(m->aux, blk.bytes, m->h_in, blk.bytes, m->aux, 0, m->h_res, res_b)) != SNK_OK) return rc;
+    if ((rc = stage_upload(blk, m->h_in, m->aux, m->stream)) != SNK_OK) return rc;
+    char* ab              = m->aux.as<char>();
+    const snk_kp64* d_kl  = blk.at<const snk_kp64>(ab, i_kl);
+    const snk_kp64* d_kr  = blk.at<const snk_kp64>(ab, i_kr);
+    const uint4* d_dl     = blk.at<const uint4>(ab, i_dl);
+    const uint4* d_dr     = blk.at<const uint4>(ab, i_dr);
+    float* rp             = blk.at<float>(ab, i_rp);
+    float* dp             = blk.at<float>(ab, i_dp);
+    int* d_cnt            = blk.at<int>(ab, i_cnt);
+    const u32* srt        = nullptr;
+    const StereoForm form = stereo_host_form(nr, stereo_force_network());
     if (form != StereoForm::unindexed)
     {
         if ((rc = m->out.reserve((size_t)nr * 4)) != SNK_OK) return rc;
@@ -1145,28 +1140,27 @@ int snk_stereo_match(snk_matcher* m, const snk_kp64* left, const uint64_t (*desc
             const size_t lds = std::max(((size_t)2 * (ST_COUNT_ROWS + 1) + (size_t)2 * nrc) * 4, (size_t)np2 * 4);
             if ((rc = set_max_lds_once(reinterpret_cast<const void*>(stereo_count_kernel), (2 * (ST_COUNT_ROWS + 1) + 2 * ST_SORT_MAX) * 4)) != SNK_OK)
                 return rc;
-            hipLaunchKernelGGL(stereo_count_kernel, dim3(1), dim3(256), lds, m->stream, (const snk_kp64*)(ab + o_kr), (const int*)nullptr, nrc, nr,
+            hipLaunchKernelGGL(stereo_count_kernel, dim3(1), dim3(256), lds, m->stream, d_kr, (const int*)nullptr, nrc, nr,
                                ls.iround_mode, m->out.as<u32>(), (int*)nullptr, (float*)nullptr, (float*)nullptr, 0);
         }
         else
-            hipLaunchKernelGGL(stereo_sort_kernel, dim3(1), dim3(256), (size_t)np2 * 4, m->stream, (const snk_kp64*)(ab + o_kr),
+            hipLaunchKernelGGL(stereo_sort_kernel, dim3(1), dim3(256), (size_t)np2 * 4, m->stream, d_kr,
                                (const int*)nullptr, nr, nr, ls.iround_mode, m->out.as<u32>());
         srt = m->out.as<u32>();
     }
     if (srt)
-        hipLaunchKernelGGL(stereo_kernel16, dim3(ceil_div(nl, 16), 1), dim3(256), (size_t)nr * 4, m->stream, (const snk_kp64*)ab, d_dl,
-                           (const int*)nullptr, nl, nl, (const snk_kp64*)(ab + o_kr), d_dr, (const int*)nullptr, nr, nr, bf, ls, relaxed, rp, dp,
+        hipLaunchKernelGGL(stereo_kernel16, dim3(ceil_div(nl, 16), 1), dim3(256), (size_t)nr * 4, m->stream, d_kl, d_dl,
+                           (const int*)nullptr, nl, nl, d_kr, d_dr, (const int*)nullptr, nr, nr, bf, ls, relaxed, rp, dp,
                            d_cnt, srt);
     else
-        hipLaunchKernelGGL(stereo_kernel, dim3(ceil_div(nl, 4), 1), dim3(256), 0, m->stream, (const snk_kp64*)ab, d_dl, (const int*)nullptr,
-                           nl, nl, (const snk_kp64*)(ab + o_kr), d_dr, (const int*)nullptr, nr, nr, bf, ls, relaxed, rp, dp, d_cnt, srt);
+        hipLaunchKernelGGL(stereo_kernel, dim3(ceil_div(nl, 4), 1), dim3(256), 0, m->stream, d_kl, d_dl, (const int*)nullptr,
+                           nl, nl, d_kr, d_dr, (const int*)nullptr, nr, nr, bf, ls, relaxed, rp, dp, d_cnt, srt);
     SNK_LAUNCH_CHECK();
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, ab + o_rp, res_b, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const char* hr = m->h_res.as<char>();
-    memcpy(right_points, hr, (size_t)nl * 4);
-    memcpy(depth, hr + (size_t)nl * 4, (size_t)nl * 4);
-    memcpy(n_matches, hr + (size_t)nl * 8, 4);
+    if ((rc = stage_download(m->h_res, 0, m->aux, tail, res_b, m->stream)) != SNK_OK) return rc;
+    const auto back = [&](int part) { return m->h_res.as<char>() + (blk.parts[(size_t)part].offset - tail); };  // h_res holds the tail only
+    memcpy(right_points, back(i_rp), (size_t)nl * 4);
+    memcpy(depth, back(i_dp), (size_t)nl * 4);
+    memcpy(n_matches, back(i_cnt), 4);
     return SNK_OK;
 }
 
@@ -1200,8 +1194,7 @@ int snk::stereo_match_batch_dev_impl(snk_matcher* m, const snk_kp64* left_dev, c
     SNK_HIP_CHECK(hipSetDevice(m->device));
     const u32* srt = nullptr;
     static const bool no_frame_kernel = getenv("SNK_STEREO_NO_FRAME_KERNEL") != nullptr;  // A/B measurements
-    static const bool sort_network    = getenv("SNK_STEREO_SORT_NETWORK") != nullptr;     // A/B, tests: the bitonic network
-    const StereoForm form = stereo_batch_form(nr_cap, batch, no_frame_kernel, sort_network);
+    const StereoForm form = stereo_batch_form(nr_cap, batch, no_frame_kernel, stereo_force_network());
     // the counting kernel of the small-batch path resets the counter and does the prefill itself; every other path pays the fills
     if (form != StereoForm::count16)
     {

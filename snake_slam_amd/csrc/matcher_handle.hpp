@@ -26,8 +26,11 @@ struct snk_matcher : snk::HandleBase
 
 namespace snk
 {
-// The map-side host entries (covis, localmap, mappoint, scene, triangulate) stage a call the same way: the input arrays as one Block
-// (stage.hpp) through `h_in` into `q` with one DMA, the results from `out` through `h_res` with one DMA back.
+// Every host entry that takes host pointers stages a call the same way: the input arrays as one Block (stage.hpp) through a pinned
+// buffer into a device buffer with one DMA, the results from a device buffer through a pinned buffer with one DMA back.  The forms
+// that take a matcher alone use `h_in` -> `q` and `out` -> `h_res` (the map-side entries, pose, P3P, Sim3, kNN-2, the BoW matcher, the
+// projection matchers); the general forms name the buffers (stereo and rectify keep their one block in `aux`, the grid answers from
+// `aux2`, the filter reads `out` and answers from `aux`, snk_bow_transform has the vocabulary's own four buffers and stream).
 
 // start[0 .. n]: begins at 0, never decreases
 inline int check_starts(const int32_t* start, int n, const char* begin_msg, const char* order_msg)
@@ -37,29 +40,45 @@ inline int check_starts(const int32_t* start, int n, const char* begin_msg, cons
     return SNK_OK;
 }
 
-inline int stage_reserve(snk_matcher* m, size_t in_bytes, size_t out_bytes)
+// each buffer with what the call asks of it: the device sizes may carry an entry's slack, `res_bytes` is only what comes back
+inline int stage_reserve(DevBuf& in, size_t in_dev_bytes, HostBuf& h_in, size_t in_bytes, DevBuf& out, size_t out_dev_bytes, HostBuf& h_res,
+                         size_t res_bytes)
 {
     int rc;
-    if ((rc = m->q.reserve(in_bytes)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_bytes)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in_bytes)) != SNK_OK) return rc;
-    return m->h_res.reserve(out_bytes);
+    if ((rc = in.reserve(in_dev_bytes)) != SNK_OK) return rc;
+    if ((rc = out.reserve(out_dev_bytes)) != SNK_OK) return rc;
+    if ((rc = h_in.reserve(in_bytes)) != SNK_OK) return rc;
+    return h_res.reserve(res_bytes);
+}
+// `slack`: what an entry has always asked of `q` and `out` beyond its blocks
+inline int stage_reserve(snk_matcher* m, size_t in_bytes, size_t out_bytes, size_t slack = 0)
+{
+    return stage_reserve(m->q, in_bytes + slack, m->h_in, in_bytes, m->out, out_bytes + slack, m->h_res, out_bytes);
 }
 
-// after stage_reserve(m, in.bytes, ...): the parts into `h_in`, then the whole block to `q` on the handle's stream
+// after stage_reserve: the parts into the pinned buffer, then the whole block to the device buffer
+inline int stage_upload(const Block& in, HostBuf& h_in, DevBuf& dev, hipStream_t stream)
+{
+    in.copy(h_in.as<char>());
+    SNK_HIP_CHECK(hipMemcpyAsync(dev.p, h_in.p, in.bytes, hipMemcpyHostToDevice, stream));
+    return SNK_OK;
+}
 inline int stage_upload(snk_matcher* m, const Block& in)
 {
-    in.copy(m->h_in.as<char>());
-    SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, in.bytes, hipMemcpyHostToDevice, m->stream));
-    return SNK_OK;
+    return stage_upload(in, m->h_in, m->q, m->stream);
 }
 
-// out[offset .. offset + bytes) to the same place of `h_res`; returns when it is there
+// dev[offset .. offset + bytes) to h_res[host_offset ..); returns when it is there
+inline int stage_download(HostBuf& h_res, size_t host_offset, const DevBuf& dev, size_t offset, size_t bytes, hipStream_t stream)
+{
+    SNK_HIP_CHECK(hipMemcpyAsync(h_res.as<char>() + host_offset, static_cast<const char*>(dev.p) + offset, bytes, hipMemcpyDeviceToHost, stream));
+    SNK_HIP_CHECK(hipStreamSynchronize(stream));
+    return SNK_OK;
+}
+// out[offset .. offset + bytes) to the same place of `h_res`
 inline int stage_download(snk_matcher* m, size_t offset, size_t bytes)
 {
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.as<char>() + offset, m->out.as<char>() + offset, bytes, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    return SNK_OK;
+    return stage_download(m->h_res, offset, m->out, offset, bytes, m->stream);
 }
 
 // snk_stereo_match_batch_dev with the option of doing Frame::allocateTmp's -1000 prefill of right_points / depth itself (the one-call front-end)

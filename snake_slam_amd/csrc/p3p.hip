@@ -344,18 +344,16 @@ int ransac_host(snk_matcher* m, const snk_p3p_params* params, snk_p3p_problem* p
     }
     SNK_REQUIRE(total < (size_t)1 << 28, "too many pairs");
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    const size_t np    = (size_t)n_problems;
-    const size_t o_wps = (np * sizeof(P3PMeta) + 15) & ~(size_t)15, o_nip = o_wps + total * 24, in_b = o_nip + total * 16;
-    // results: P3PResult[np] | list[total] | mask[total]
-    const size_t r_list = np * sizeof(P3PResult), r_mask = r_list + total * 4, out_b = r_mask + total;
+    const size_t np = (size_t)n_problems;
+    // up: P3PMeta[np] | wps[total] | nips[total] (the problems' rows one after the other)      back: P3PResult[np] | list[total] | mask[total]
+    Block in, out;
+    const int i_meta = in.add(nullptr, np * sizeof(P3PMeta)), i_wps = in.add(nullptr, total * 24), i_nip = in.add(nullptr, total * 16);
+    const int r_res = out.add(nullptr, np * sizeof(P3PResult)), r_list = out.add(nullptr, total * 4), r_mask = out.add(nullptr, total);
     int rc;
-    if ((rc = m->q.reserve(in_b + 64)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_b + 64)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in_b)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_b)) != SNK_OK) return rc;
-    char* stage    = m->h_in.as<char>();
-    P3PMeta* meta  = reinterpret_cast<P3PMeta*>(stage);
-    size_t off     = 0;
+    if ((rc = stage_reserve(m, in.bytes, out.end(), 64)) != SNK_OK) return rc;
+    char* stage   = m->h_in.as<char>();
+    P3PMeta* meta = in.at<P3PMeta>(stage, i_meta);
+    size_t off    = 0;
     for (int i = 0; i < n_problems; ++i)
     {
         const snk_p3p_problem& P = problems[i];
@@ -364,25 +362,23 @@ int ransac_host(snk_matcher* m, const snk_p3p_params* params, snk_p3p_problem* p
         memcpy(meta[i].pose, P.pose, 56);
         if (P.n > 0)
         {
-            memcpy(stage + o_wps + off * 24, P.wps, (size_t)P.n * 24);
-            memcpy(stage + o_nip + off * 16, P.nips, (size_t)P.n * 16);
+            memcpy(in.at<char>(stage, i_wps) + off * 24, P.wps, (size_t)P.n * 24);
+            memcpy(in.at<char>(stage, i_nip) + off * 16, P.nips, (size_t)P.n * 16);
         }
         off += (size_t)P.n;
     }
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
     char* d = m->q.as<char>();
     char* o = m->out.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(d, stage, in_b, hipMemcpyHostToDevice, m->stream));
     if ((rc = set_max_lds_once(reinterpret_cast<const void*>(p3p_ransac_kernel<false>), (int)lds_bytes(P3P_MAX_PAIRS))) != SNK_OK) return rc;
     P3PFrames F{};
-    hipLaunchKernelGGL(p3p_ransac_kernel<false>, dim3(n_problems), dim3(256), lds_bytes(n_max), m->stream,
-                       reinterpret_cast<const P3PMeta*>(d), reinterpret_cast<const double*>(d + o_wps),
-                       reinterpret_cast<const double*>(d + o_nip), F, params->iterations, params->residual_threshold, (u64)params->seed, n_max,
-                       reinterpret_cast<u8*>(o + r_mask), reinterpret_cast<int*>(o + r_list), reinterpret_cast<P3PResult*>(o), dbg);
+    hipLaunchKernelGGL(p3p_ransac_kernel<false>, dim3(n_problems), dim3(256), lds_bytes(n_max), m->stream, in.at<const P3PMeta>(d, i_meta),
+                       in.at<const double>(d, i_wps), in.at<const double>(d, i_nip), F, params->iterations, params->residual_threshold,
+                       (u64)params->seed, n_max, out.at<u8>(o, r_mask), out.at<int>(o, r_list), out.at<P3PResult>(o, r_res), dbg);
     SNK_LAUNCH_CHECK();
+    if ((rc = stage_download(m, 0, out.end())) != SNK_OK) return rc;
     char* back = m->h_res.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(back, o, out_b, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const P3PResult* res = reinterpret_cast<const P3PResult*>(back);
+    const P3PResult* res = out.at<const P3PResult>(back, r_res);
     off                  = 0;
     for (int i = 0; i < n_problems; ++i)
     {
@@ -398,8 +394,8 @@ int ransac_host(snk_matcher* m, const snk_p3p_params* params, snk_p3p_problem* p
         P.best_solution  = res[i].best_solution;
         if (P.n > 0)
         {
-            memcpy(P.inlier_mask, back + r_mask + off, (size_t)P.n);
-            memcpy(P.inlier_matches, back + r_list + off * 4, (size_t)res[i].inliers * 4);
+            memcpy(P.inlier_mask, out.at<char>(back, r_mask) + off, (size_t)P.n);
+            memcpy(P.inlier_matches, out.at<char>(back, r_list) + off * 4, (size_t)res[i].inliers * 4);
         }
         off += (size_t)P.n;
     }

@@ -778,6 +778,12 @@ extern "C" int snk_track_backproject_batch_dev(snk_matcher* m, const snk_frames_
     return SNK_OK;
 }
 
+static bool pose_no_lds()
+{
+    static const bool v = getenv("SNK_POSE_NO_LDS") != nullptr;  // A/B: matches re-read from global memory in every step
+    return v;
+}
+
 extern "C" int snk_pose_refine(snk_matcher* m, const snk_camera* cam, const snk_pose_options* opt, snk_pose_problem* problems,
                                int n_problems)
 {
@@ -798,19 +804,15 @@ extern "C" int snk_pose_refine(snk_matcher* m, const snk_camera* cam, const snk_
     }
     SNK_REQUIRE(total < (size_t)1 << 30, "too many matches");
     SNK_HIP_CHECK(hipSetDevice(m->device));
-    const size_t np     = (size_t)n_problems;
-    const size_t o_wps  = np * sizeof(PoseMeta);
-    const size_t o_obs  = o_wps + total * 24;
-    const size_t in_b   = o_obs + total * sizeof(snk_pose_obs);
-    const size_t o_pose = (total + 7) & ~(size_t)7, o_inl = o_pose + np * 56, out_b = o_inl + np * 4;
+    const size_t np = (size_t)n_problems;
+    // up: PoseMeta[np] | wps[total] | obs[total] (the problems' rows one after the other)      back: outlier[total] | pose[np] | inliers[np]
+    Block in, out;
+    const int i_meta = in.add(nullptr, np * sizeof(PoseMeta)), i_wps = in.add(nullptr, total * 24), i_obs = in.add(nullptr, total * sizeof(snk_pose_obs));
+    const int r_outl = out.add(nullptr, total), r_pose = out.add(nullptr, np * 56), r_inl = out.add(nullptr, np * 4);
     int rc;
-    if ((rc = m->q.reserve(in_b + 64)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_b + 64)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in_b)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_b)) != SNK_OK) return rc;
-    // stage inputs contiguously in pinned memory, one upload
+    if ((rc = stage_reserve(m, in.bytes, out.end(), 64)) != SNK_OK) return rc;
     char* stage    = m->h_in.as<char>();
-    PoseMeta* meta = reinterpret_cast<PoseMeta*>(stage);
+    PoseMeta* meta = in.at<PoseMeta>(stage, i_meta);
     size_t off     = 0;
     int n_max      = 0;
     for (int i = 0; i < n_problems; ++i)
@@ -827,15 +829,19 @@ extern "C" int snk_pose_refine(snk_matcher* m, const snk_camera* cam, const snk_
         M.w_trans = P.w_trans;
         if (P.n > 0)
         {
-            memcpy(&stage[o_wps + off * 24], P.wps, (size_t)P.n * 24);
-            memcpy(&stage[o_obs + off * sizeof(snk_pose_obs)], P.obs, (size_t)P.n * sizeof(snk_pose_obs));
+            memcpy(in.at<char>(stage, i_wps) + off * 24, P.wps, (size_t)P.n * 24);
+            memcpy(in.at<char>(stage, i_obs) + off * sizeof(snk_pose_obs), P.obs, (size_t)P.n * sizeof(snk_pose_obs));
         }
         off += (size_t)P.n;
         n_max = P.n > n_max ? P.n : n_max;
     }
-    char* d = m->q.as<char>();
-    char* o = m->out.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(d, stage, in_b, hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    const PoseMeta* d_meta    = in.at<const PoseMeta>(m->q.as<char>(), i_meta);
+    const double* d_wps       = in.at<const double>(m->q.as<char>(), i_wps);
+    const snk_pose_obs* d_obs = in.at<const snk_pose_obs>(m->q.as<char>(), i_obs);
+    u8* d_outl                = out.at<u8>(m->out.as<char>(), r_outl);
+    double* d_pose            = out.at<double>(m->out.as<char>(), r_pose);
+    int* d_inl                = out.at<int>(m->out.as<char>(), r_inl);
     CamD C{cam->fx, cam->fy, cam->cx, cam->cy, cam->bf};
     // the form by the call's shape (dispatch.hpp): ~200 matches per frame and more: four wavefronts per frame, with the matches of a
     // problem in LDS for its 40 steps (as in the device-resident form): one problem per call is a chain of latencies, and a
@@ -843,41 +849,35 @@ extern "C" int snk_pose_refine(snk_matcher* m, const snk_camera* cam, const snk_
     // (eight wavefronts per problem for calls with one or a few large problems -- the reference's call is ONE frame of ~900 matches,
     // a chain of latencies on an empty chip -- measured nothing: 0.229 vs 0.224 ms per call, round 4; a step is bound by its serial
     // part: reduction, 6 x 6 solve, pose hand-over)
-    static const bool no_lds = getenv("SNK_POSE_NO_LDS") != nullptr;
-    switch (pose_host_form(total, n_problems, no_lds))
+    switch (pose_host_form(total, n_problems, pose_no_lds()))
     {
     case PoseForm::wave4_lds:
     {
         const int lds_matches = pose_host_carve(n_max, n_problems);
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(pose_kernel<4, true>), pose_dyn_max())) != SNK_OK) return rc;
-        hipLaunchKernelGGL((pose_kernel<4, true>), dim3(n_problems), dim3(256), (size_t)lds_matches * POSE_MATCH_BYTES, m->stream,
-                           reinterpret_cast<const PoseMeta*>(d), reinterpret_cast<const double*>(d + o_wps),
-                           reinterpret_cast<const snk_pose_obs*>(d + o_obs), reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose),
-                           reinterpret_cast<int*>(o + o_inl), C, *opt, lds_matches);
+        hipLaunchKernelGGL((pose_kernel<4, true>), dim3(n_problems), dim3(256), (size_t)lds_matches * POSE_MATCH_BYTES, m->stream, d_meta, d_wps,
+                           d_obs, d_outl, d_pose, d_inl, C, *opt, lds_matches);
         break;
     }
     case PoseForm::wave4_global:
-        hipLaunchKernelGGL((pose_kernel<4, false>), dim3(n_problems), dim3(256), 0, m->stream, reinterpret_cast<const PoseMeta*>(d),
-                           reinterpret_cast<const double*>(d + o_wps), reinterpret_cast<const snk_pose_obs*>(d + o_obs),
-                           reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose), reinterpret_cast<int*>(o + o_inl), C, *opt, 0);
+        hipLaunchKernelGGL((pose_kernel<4, false>), dim3(n_problems), dim3(256), 0, m->stream, d_meta, d_wps, d_obs, d_outl, d_pose, d_inl, C,
+                           *opt, 0);
         break;
     default:  // wave1 (the host entry has no two-wavefront form)
-        hipLaunchKernelGGL((pose_kernel<1, false>), dim3(n_problems), dim3(64), 0, m->stream, reinterpret_cast<const PoseMeta*>(d),
-                           reinterpret_cast<const double*>(d + o_wps), reinterpret_cast<const snk_pose_obs*>(d + o_obs),
-                           reinterpret_cast<u8*>(o), reinterpret_cast<double*>(o + o_pose), reinterpret_cast<int*>(o + o_inl), C, *opt, 0);
+        hipLaunchKernelGGL((pose_kernel<1, false>), dim3(n_problems), dim3(64), 0, m->stream, d_meta, d_wps, d_obs, d_outl, d_pose, d_inl, C,
+                           *opt, 0);
         break;
     }
     SNK_LAUNCH_CHECK();
+    if ((rc = stage_download(m, 0, out.end())) != SNK_OK) return rc;
     char* back = m->h_res.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(back, o, out_b, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    off = 0;
+    off        = 0;
     for (int i = 0; i < n_problems; ++i)
     {
         snk_pose_problem& P = problems[i];
-        if (P.n > 0) memcpy(P.outlier, &back[off], (size_t)P.n);
-        memcpy(P.pose, &back[o_pose + (size_t)i * 56], 56);
-        memcpy(&P.inliers, &back[o_inl + (size_t)i * 4], 4);
+        if (P.n > 0) memcpy(P.outlier, out.at<char>(back, r_outl) + off, (size_t)P.n);
+        memcpy(P.pose, out.at<char>(back, r_pose) + (size_t)i * 56, 56);
+        memcpy(&P.inliers, out.at<char>(back, r_inl) + (size_t)i * 4, 4);
         off += (size_t)P.n;
     }
     return SNK_OK;
@@ -924,7 +924,6 @@ static int refine_batch_impl(snk_matcher* m, const snk_frames_dev* frames, const
     else GATHER_LAUNCH(false);
 #undef GATHER_LAUNCH
     CamD C{cam->fx, cam->fy, cam->cx, cam->cy, cam->bf};
-    static const bool no_lds = getenv("SNK_POSE_NO_LDS") != nullptr;  // A/B: matches re-read from global memory in every step
     // matches of a frame kept in LDS (56 bytes each): the whole local map when few frames are in flight (one workgroup per CU
     // anyway), otherwise at most ~1300, so that TWO frames share a compute unit -- what the kernel's ~250 registers admit (two
     // wavefronts per SIMD; until round 4 the carve was sized for four frames, 656 matches, and a frame with the usual ~770 read
@@ -947,7 +946,7 @@ static int refine_batch_impl(snk_matcher* m, const snk_frames_dev* frames, const
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 256;
         return v > 0 ? v : 256;
     }();
-    const PoseForm form   = pose_batch_form(stride, batch, n_cu, waves_env, no_lds);
+    const PoseForm form   = pose_batch_form(stride, batch, n_cu, waves_env, pose_no_lds());
     const int lds_matches = pose_batch_carve(stride, batch, lds_env, form == PoseForm::wave2_lds);  // dispatch.hpp
     const size_t match_lds = (size_t)lds_matches * POSE_MATCH_BYTES;
     if (form == PoseForm::wave2_lds || form == PoseForm::wave4_lds)

@@ -210,21 +210,20 @@ int snk_rectify(snk_matcher* m, const snk_rectification* rect, const snk_keypoin
     SNK_REQUIRE(kps && out, "NULL buffer");
     SNK_HIP_CHECK(hipSetDevice(m->device));
     // aux: keypoints in | undistorted out | normalized out (16-byte aligned pieces); through the pinned staging buffers, one copy each way
-    const size_t kin = ((size_t)n * sizeof(snk_keypoint) + 15) & ~(size_t)15, kout = (size_t)n * sizeof(snk_kp64), nb = (size_t)n * 16;
-    const size_t res_b = kout + (normalized ? nb : 0);
-    if ((st = m->aux.reserve(kin + kout + nb)) != SNK_OK) return st;
-    if ((st = m->h_in.reserve(kin)) != SNK_OK) return st;
-    if ((st = m->h_res.reserve(res_b)) != SNK_OK) return st;
-    char* ab = m->aux.as<char>();
-    memcpy(m->h_in.p, kps, (size_t)n * sizeof(snk_keypoint));
-    SNK_HIP_CHECK(hipMemcpyAsync(ab, m->h_in.p, (size_t)n * sizeof(snk_keypoint), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(rectify_kernel, dim3(ceil_div(n, 256), 1), dim3(256), 0, m->stream, rc, (const snk_keypoint*)ab,
-                       (const int*)nullptr, n, n, (snk_kp64*)(ab + kin), normalized ? reinterpret_cast<double2*>(ab + kin + kout) : nullptr);
+    Block in, res;  // the result block follows the input block in aux
+    const size_t kout = (size_t)n * sizeof(snk_kp64), nb = (size_t)n * 16;
+    const int i_kps = in.add(kps, (size_t)n * sizeof(snk_keypoint)), r_out = res.add(nullptr, kout), r_norm = res.add(nullptr, nb);
+    const size_t res_b = normalized ? res.end() : kout;
+    if ((st = stage_reserve(m->aux, in.bytes + res.end(), m->h_in, in.bytes, m->aux, 0, m->h_res, res_b)) != SNK_OK) return st;
+    if ((st = stage_upload(in, m->h_in, m->aux, m->stream)) != SNK_OK) return st;
+    char* rb = m->aux.as<char>() + in.bytes;
+    hipLaunchKernelGGL(rectify_kernel, dim3(ceil_div(n, 256), 1), dim3(256), 0, m->stream, rc, in.at<const snk_keypoint>(m->aux.as<char>(), i_kps),
+                       (const int*)nullptr, n, n, res.at<snk_kp64>(rb, r_out), normalized ? res.at<double2>(rb, r_norm) : nullptr);
     SNK_LAUNCH_CHECK();
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, ab + kin, res_b, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(out, m->h_res.p, kout);
-    if (normalized) memcpy(normalized, m->h_res.as<char>() + kout, nb);
+    if ((st = stage_download(m->h_res, 0, m->aux, in.bytes, res_b, m->stream)) != SNK_OK) return st;
+    char* hr = m->h_res.as<char>();
+    memcpy(out, res.at<char>(hr, r_out), kout);
+    if (normalized) memcpy(normalized, res.at<char>(hr, r_norm), nb);
     return SNK_OK;
 }
 

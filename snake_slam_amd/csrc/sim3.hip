@@ -410,17 +410,16 @@ int ransac_host(snk_matcher* m, const snk_sim3_params* params, snk_sim3_problem*
     SNK_HIP_CHECK(hipSetDevice(m->device));
     const int lds_cap = n_max < SIM3_LDS_PAIRS ? n_max : SIM3_LDS_PAIRS, slab_cap = n_max - lds_cap;
     const size_t np   = (size_t)n_problems;
-    const size_t o_p1 = (np * sizeof(Sim3Meta) + 15) & ~(size_t)15, o_p2 = o_p1 + total * 24, o_i1 = o_p2 + total * 24, o_i2 = o_i1 + total * 16,
-                 in_b = o_i2 + total * 16;
-    const size_t r_mask = np * sizeof(Sim3Result), out_b = r_mask + total;  // results: Sim3Result[np] | mask[total]
+    // up: Sim3Meta[np] | points1 | points2 | ips1 | ips2 (the problems' rows one after the other)      back: Sim3Result[np] | mask[total]
+    Block in, out;
+    const int i_meta = in.add(nullptr, np * sizeof(Sim3Meta)), i_p1 = in.add(nullptr, total * 24), i_p2 = in.add(nullptr, total * 24),
+              i_i1 = in.add(nullptr, total * 16), i_i2 = in.add(nullptr, total * 16);
+    const int r_res = out.add(nullptr, np * sizeof(Sim3Result)), r_mask = out.add(nullptr, total);
     int rc;
-    if ((rc = m->q.reserve(in_b + 64)) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(out_b + 64)) != SNK_OK) return rc;
+    if ((rc = stage_reserve(m, in.bytes, out.end(), 64)) != SNK_OK) return rc;
     if ((rc = m->aux2.reserve(np * (size_t)slab_cap * 80 + 64)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(in_b)) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(out_b)) != SNK_OK) return rc;
     char* stage    = m->h_in.as<char>();
-    Sim3Meta* meta = reinterpret_cast<Sim3Meta*>(stage);
+    Sim3Meta* meta = in.at<Sim3Meta>(stage, i_meta);
     size_t off     = 0;
     for (int i = 0; i < n_problems; ++i)
     {
@@ -434,28 +433,26 @@ int ransac_host(snk_matcher* m, const snk_sim3_params* params, snk_sim3_problem*
         meta[i].scale = P.scale;
         if (P.n > 0)
         {
-            memcpy(stage + o_p1 + off * 24, P.points1, (size_t)P.n * 24);
-            memcpy(stage + o_p2 + off * 24, P.points2, (size_t)P.n * 24);
-            memcpy(stage + o_i1 + off * 16, P.ips1, (size_t)P.n * 16);
-            memcpy(stage + o_i2 + off * 16, P.ips2, (size_t)P.n * 16);
+            memcpy(in.at<char>(stage, i_p1) + off * 24, P.points1, (size_t)P.n * 24);
+            memcpy(in.at<char>(stage, i_p2) + off * 24, P.points2, (size_t)P.n * 24);
+            memcpy(in.at<char>(stage, i_i1) + off * 16, P.ips1, (size_t)P.n * 16);
+            memcpy(in.at<char>(stage, i_i2) + off * 16, P.ips2, (size_t)P.n * 16);
         }
         off += (size_t)P.n;
     }
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
     char* d = m->q.as<char>();
     char* o = m->out.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(d, stage, in_b, hipMemcpyHostToDevice, m->stream));
     if ((rc = set_max_lds_once(reinterpret_cast<const void*>(sim3_ransac_kernel<false>), (int)lds_bytes(SIM3_LDS_PAIRS, 0))) != SNK_OK) return rc;
     Sim3Pairs F{};
-    hipLaunchKernelGGL(sim3_ransac_kernel<false>, dim3(n_problems), dim3(256), lds_bytes(lds_cap, 0), m->stream,
-                       reinterpret_cast<const Sim3Meta*>(d), reinterpret_cast<const double*>(d + o_p1), reinterpret_cast<const double*>(d + o_p2),
-                       reinterpret_cast<const double*>(d + o_i1), reinterpret_cast<const double*>(d + o_i2), F, 0, params->compute_scale,
-                       params->threshold, (u64)params->seed, lds_cap, 0, m->aux2.as<double>(), slab_cap, reinterpret_cast<u8*>(o + r_mask),
-                       reinterpret_cast<Sim3Result*>(o), dbg);
+    hipLaunchKernelGGL(sim3_ransac_kernel<false>, dim3(n_problems), dim3(256), lds_bytes(lds_cap, 0), m->stream, in.at<const Sim3Meta>(d, i_meta),
+                       in.at<const double>(d, i_p1), in.at<const double>(d, i_p2), in.at<const double>(d, i_i1), in.at<const double>(d, i_i2), F, 0,
+                       params->compute_scale, params->threshold, (u64)params->seed, lds_cap, 0, m->aux2.as<double>(), slab_cap,
+                       out.at<u8>(o, r_mask), out.at<Sim3Result>(o, r_res), dbg);
     SNK_LAUNCH_CHECK();
-    char* back = m->h_res.as<char>();
-    SNK_HIP_CHECK(hipMemcpyAsync(back, o, out_b, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const Sim3Result* res = reinterpret_cast<const Sim3Result*>(back);
+    if ((rc = stage_download(m, 0, out.end())) != SNK_OK) return rc;
+    char* back            = m->h_res.as<char>();
+    const Sim3Result* res = out.at<const Sim3Result>(back, r_res);
     off                   = 0;
     for (int i = 0; i < n_problems; ++i)
     {
@@ -469,7 +466,7 @@ int ransac_host(snk_matcher* m, const snk_sim3_params* params, snk_sim3_problem*
         P.scale          = res[i].scale;
         P.inliers        = res[i].inliers;
         P.best_iteration = res[i].best_iteration;
-        if (P.n > 0) memcpy(P.inlier_mask, back + r_mask + off, (size_t)P.n);
+        if (P.n > 0) memcpy(P.inlier_mask, out.at<char>(back, r_mask) + off, (size_t)P.n);
         off += (size_t)P.n;
     }
     return SNK_OK;

@@ -1462,42 +1462,37 @@ int snk_feature_grid(snk_matcher* m, const snk_kp64* undistorted, int n, const s
     SNK_HIP_CHECK(hipSetDevice(m->device));
     const size_t nc = (size_t)cols * rows + 1;
     int rc;
-    if ((rc = m->aux.reserve((size_t)(n > 0 ? n : 1) * sizeof(snk_kp64))) != SNK_OK) return rc;
-    if ((rc = m->aux2.reserve((size_t)(n > 0 ? n : 1) * 4 + nc * 4)) != SNK_OK) return rc;
+    // aux: the keypoints | aux2: permutation, cell starts -- one copy each way (an empty frame keeps room for one feature: the kernels' capacity is >= 1)
+    Block in, out;
+    const size_t np1 = (size_t)(n > 0 ? n : 1);
+    const int i_kps = in.add(n ? undistorted : nullptr, np1 * sizeof(snk_kp64)), r_perm = out.add(nullptr, np1 * 4), r_cs = out.add(nullptr, nc * 4);
+    if ((rc = stage_reserve(m->aux, in.bytes, m->h_in, in.bytes, m->aux2, out.end(), m->h_res, out.end())) != SNK_OK) return rc;
+    if (n && (rc = stage_upload(in, m->h_in, m->aux, m->stream)) != SNK_OK) return rc;
     int n_pow2 = 1;
     while (n_pow2 < n) n_pow2 <<= 1;
     if (n_pow2 < 2) n_pow2 = 2;
-    int* d_perm = m->aux2.as<int>();
-    int* d_cs   = d_perm + (n > 0 ? n : 1);
-    if ((rc = m->h_in.reserve((size_t)(n > 0 ? n : 1) * sizeof(snk_kp64))) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve((size_t)(n > 0 ? n : 1) * 4 + nc * 4)) != SNK_OK) return rc;
-    if (n)
-    {
-        memcpy(m->h_in.p, undistorted, (size_t)n * sizeof(snk_kp64));  // pinned staging: see matcher_handle.hpp
-        SNK_HIP_CHECK(hipMemcpyAsync(m->aux.p, m->h_in.p, (size_t)n * sizeof(snk_kp64), hipMemcpyHostToDevice, m->stream));
-    }
+    const snk_kp64* d_kps = in.at<const snk_kp64>(m->aux.as<char>(), i_kps);
+    int* d_perm           = out.at<int>(m->aux2.as<char>(), r_perm);
+    int* d_cs             = out.at<int>(m->aux2.as<char>(), r_cs);
     const GridForm form = grid_form(n, cols * rows, grid_use_network());
     if (debug_plan_lines()) print_grid_plan(n, cols * rows, 1, form);
     if (form == GridForm::count)
     {
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_count_kernel), GRID_COUNT_LDS_MAX)) != SNK_OK) return rc;
         hipLaunchKernelGGL(grid_count_kernel, dim3(1), dim3(256), grid_count_lds(n, cols * rows), m->stream,
-                           m->aux.as<snk_kp64>(), (const int*)nullptr, n, n > 0 ? n : 1, bounds->min_x, bounds->min_y, cols, rows, d_perm,
+                           d_kps, (const int*)nullptr, n, n > 0 ? n : 1, bounds->min_x, bounds->min_y, cols, rows, d_perm,
                            (int*)nullptr, d_cs);
     }
     else
     {
         if ((rc = set_max_lds_once(reinterpret_cast<const void*>(grid_kernel), GRID_MAX_FEATURES * 4)) != SNK_OK) return rc;
-        hipLaunchKernelGGL(grid_kernel, dim3(1), dim3(256), (size_t)n_pow2 * 4, m->stream, m->aux.as<snk_kp64>(), (const int*)nullptr,
+        hipLaunchKernelGGL(grid_kernel, dim3(1), dim3(256), (size_t)n_pow2 * 4, m->stream, d_kps, (const int*)nullptr,
                            n, n > 0 ? n : 1, bounds->min_x, bounds->min_y, cols, rows, d_perm, (int*)nullptr, d_cs);
     }
     SNK_LAUNCH_CHECK();
-    // permutation | cell starts are adjacent in aux2: one copy back
-    const size_t np1 = (size_t)(n > 0 ? n : 1);
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, d_perm, (np1 + nc) * 4, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    if (n) memcpy(perm, m->h_res.p, (size_t)n * 4);
-    memcpy(cell_start, m->h_res.as<int>() + np1, nc * 4);
+    if ((rc = stage_download(m->h_res, 0, m->aux2, 0, out.end(), m->stream)) != SNK_OK) return rc;
+    if (n) memcpy(perm, out.at<char>(m->h_res.as<char>(), r_perm), (size_t)n * 4);
+    memcpy(cell_start, out.at<char>(m->h_res.as<char>(), r_cs), nc * 4);
     return SNK_OK;
 }
 
@@ -1581,28 +1576,26 @@ int snk_match_project_coarse(snk_matcher* m, const snk_frame_view* frame, const 
     if ((rc = upload_frame(m, frame, &F)) != SNK_OK) return rc;
     if (n_pts == 0) return SNK_OK;
     const size_t np = (size_t)n_pts;
-    // q: points | out: best, bins, match | t: claim | cnt: count
-    if ((rc = m->q.reserve(np * sizeof(snk_lm_coarse))) != SNK_OK) return rc;
-    if ((rc = m->out.reserve(np * 12 + 64)) != SNK_OK) return rc;
+    // q: points | out: best, bins (device only), then match, count: the block that comes back | t: claim | cnt: count
+    Block in, work, res;
+    const int i_pts = in.add(pts, np * sizeof(snk_lm_coarse)), w_best = work.add(nullptr, np * 4), w_bins = work.add(nullptr, np * 4);
+    const int r_match = res.add(nullptr, np * 4), r_cnt = res.add(nullptr, 4);
+    if ((rc = stage_reserve(m->q, in.bytes, m->h_in, in.bytes, m->out, work.bytes + res.end() + 64, m->h_res, res.end())) != SNK_OK) return rc;
     if ((rc = m->t.reserve((size_t)(F.n > 0 ? F.n : 1) * 4)) != SNK_OK) return rc;
     if ((rc = m->cnt.reserve(64)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(np * sizeof(snk_lm_coarse))) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(np * 4 + 4)) != SNK_OK) return rc;
-    int* d_best = m->out.as<int>();
-    int* d_bins = d_best + np;
-    int* d_match = d_bins + np;  // match[np] | count: one block, one copy back
-    memcpy(m->h_in.p, pts, np * sizeof(snk_lm_coarse));
-    SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, np * sizeof(snk_lm_coarse), hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char* ob    = m->out.as<char>();
+    int* d_best = work.at<int>(ob, w_best);
+    int* d_bins = work.at<int>(ob, w_bins);
     const int ppw = track_points_per_wave(n_pts, track_switches().ppw);
-    hipLaunchKernelGGL(coarse_kernel, dim3(ceil_div(n_pts, 4 * ppw)), dim3(256), 0, m->stream, F, C, S, m->q.as<snk_lm_coarse>(), n_pts, ppw,
-                       th, feature_error, direction, d_best, d_bins);
+    hipLaunchKernelGGL(coarse_kernel, dim3(ceil_div(n_pts, 4 * ppw)), dim3(256), 0, m->stream, F, C, S, in.at<const snk_lm_coarse>(m->q.as<char>(), i_pts),
+                       n_pts, ppw, th, feature_error, direction, d_best, d_bins);
     hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(256), 0, m->stream, d_best, d_bins, n_pts, F.taken, m->t.as<int>(), F.n, 1,
-                       d_match, d_match + np);
+                       res.at<int>(ob + work.bytes, r_match), res.at<int>(ob + work.bytes, r_cnt));
     SNK_LAUNCH_CHECK();
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, d_match, np * 4 + 4, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(match_idx, m->h_res.p, np * 4);
-    memcpy(n_matches, m->h_res.as<char>() + np * 4, 4);
+    if ((rc = stage_download(m->h_res, 0, m->out, work.bytes, res.end(), m->stream)) != SNK_OK) return rc;
+    memcpy(match_idx, res.at<char>(m->h_res.as<char>(), r_match), np * 4);
+    memcpy(n_matches, res.at<char>(m->h_res.as<char>(), r_cnt), 4);
     return SNK_OK;
 }
 
@@ -1623,31 +1616,27 @@ int snk_match_project_fine(snk_matcher* m, const snk_frame_view* frame, const sn
     if ((rc = upload_frame(m, frame, &F)) != SNK_OK) return rc;
     if (n_pts == 0) return SNK_OK;
     const size_t np = (size_t)n_pts;
-    if ((rc = m->q.reserve(np * sizeof(snk_lm_fine))) != SNK_OK) return rc;
-    const size_t res_b = np * 4 + 4 + np;  // match[np] | count | visible[np]: one block, one copy back
-    if ((rc = m->out.reserve(np * 4 + res_b + 64)) != SNK_OK) return rc;
+    // q: points | out: best (device only), then match, count, visible: the block that comes back | t: claim | cnt: count
+    Block in, work, res;
+    const int i_pts = in.add(pts, np * sizeof(snk_lm_fine)), w_best = work.add(nullptr, np * 4);
+    const int r_match = res.add(nullptr, np * 4), r_cnt = res.add(nullptr, 4), r_vis = res.add(nullptr, np);
+    if ((rc = stage_reserve(m->q, in.bytes, m->h_in, in.bytes, m->out, work.bytes + res.end() + 64, m->h_res, res.end())) != SNK_OK) return rc;
     if ((rc = m->t.reserve((size_t)(F.n > 0 ? F.n : 1) * 4)) != SNK_OK) return rc;
     if ((rc = m->cnt.reserve(64)) != SNK_OK) return rc;
-    if ((rc = m->h_in.reserve(np * sizeof(snk_lm_fine))) != SNK_OK) return rc;
-    if ((rc = m->h_res.reserve(res_b)) != SNK_OK) return rc;
-    int* d_best  = m->out.as<int>();
-    int* d_match = d_best + np;
-    int* d_cnt   = d_match + np;
-    u8* d_vis    = reinterpret_cast<u8*>(d_cnt + 1);
-    memcpy(m->h_in.p, pts, np * sizeof(snk_lm_fine));
-    SNK_HIP_CHECK(hipMemcpyAsync(m->q.p, m->h_in.p, np * sizeof(snk_lm_fine), hipMemcpyHostToDevice, m->stream));
+    if ((rc = stage_upload(m, in)) != SNK_OK) return rc;
+    char* rb    = m->out.as<char>() + work.bytes;
+    int* d_best = work.at<int>(m->out.as<char>(), w_best);
     const int ppw = track_points_per_wave(n_pts, track_switches().ppw);
-    hipLaunchKernelGGL(fine_kernel, dim3(ceil_div(n_pts, 4 * ppw)), dim3(256), 0, m->stream, F, C, S, m->q.as<snk_lm_fine>(), n_pts, ppw, th,
-                       ratio, d_best, d_vis);
+    hipLaunchKernelGGL(fine_kernel, dim3(ceil_div(n_pts, 4 * ppw)), dim3(256), 0, m->stream, F, C, S, in.at<snk_lm_fine>(m->q.as<char>(), i_pts), n_pts,
+                       ppw, th, ratio, d_best, res.at<u8>(rb, r_vis));
     hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(256), 0, m->stream, d_best, (const int*)nullptr, n_pts, F.taken,
-                       m->t.as<int>(), F.n, 0, d_match, d_cnt);
+                       m->t.as<int>(), F.n, 0, res.at<int>(rb, r_match), res.at<int>(rb, r_cnt));
     SNK_LAUNCH_CHECK();
-    SNK_HIP_CHECK(hipMemcpyAsync(m->h_res.p, d_match, res_b, hipMemcpyDeviceToHost, m->stream));
-    SNK_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const char* hr = m->h_res.as<char>();
-    memcpy(match_idx, hr, np * 4);
-    memcpy(n_matches, hr + np * 4, 4);
-    memcpy(visible, hr + np * 4 + 4, np);
+    if ((rc = stage_download(m->h_res, 0, m->out, work.bytes, res.end(), m->stream)) != SNK_OK) return rc;
+    char* hr = m->h_res.as<char>();
+    memcpy(match_idx, res.at<char>(hr, r_match), np * 4);
+    memcpy(n_matches, res.at<char>(hr, r_cnt), 4);
+    memcpy(visible, res.at<char>(hr, r_vis), np);
     // lmp.valid after the search is `visible` (a point keeps valid = 1 exactly when it passes every cull, which is where
     // IncreaseVisible() is called, SnakeORBMatcher.cpp:397-431): the 96-byte records are not copied back for one byte each
     for (size_t i = 0; i < np; ++i) pts[i].valid = visible[i];

@@ -48,6 +48,14 @@ def p3p_cases():
 
 
 @functools.lru_cache(maxsize=None)
+def p3p_odd_batch(k):
+    """5, 0 and 33 pairs in one call (tests/test_p3p_gpu.py): the parts of the staged blocks end off a 16-byte boundary"""
+    from test_p3p_gpu import odd_batch
+
+    return odd_batch(4400 + 10 * k)
+
+
+@functools.lru_cache(maxsize=None)
 def p3p_frames(k):
     from test_p3p_chain_gpu import make_frames
 
@@ -59,6 +67,14 @@ def sim3_cases():
     """three of sim3_numpy.gpu_cases(): n = 64, 65 and 200 with 30 % wrong pairs and 1 px noise"""
     cs = S3.gpu_cases()
     return [next(c for c in cs if len(c["P1"]) == n and c["outlier_share"] == 0.3 and c["noise_px"] == 1.0) for n in (64, 65, 200)]
+
+
+@functools.lru_cache(maxsize=None)
+def sim3_odd_batch(k):
+    """3, 0 and 65 pairs in one call (tests/test_sim3_gpu.py)"""
+    from test_sim3_gpu import odd_batch
+
+    return odd_batch(4500 + 10 * k)
 
 
 @functools.lru_cache(maxsize=None)
@@ -176,12 +192,20 @@ def front_cases():
     rng = np.random.default_rng(SEED + 4242)
     stereo = [make_stereo_case(rng, 300, 280) for _ in range(3)]
     bf_sets = [(rand_desc(rng, 257), rand_desc(rng, 301)) for _ in range(3)]
-    track = []
-    for _ in range(3):
+    track, fine = [], []
+    for i in range(3):
         frame, cam, pose, ls, world, _ = T.make_tracking_case(orc, rng, n_clutter=300, m_pts=250)
         skip = (rng.random(len(world["pos"])) < 0.1).astype(np.uint8)
         track.append((frame, cam, pose, ls, T.lm_coarse(orc, world), (world["pos"], world["desc"], skip)))
-    return dict(stereo=stereo, bf=bf_sets, track=track)
+        # the fine matcher's 251 records: the 250 points and the first once more (both want the same feature); a generator of their own,
+        # so that the cases above stay what they were
+        f = T.lm_fine(orc, np.random.default_rng(SEED + 4343 + i), world, pose, ls)
+        fine.append(np.concatenate([f, f[:1]]))
+    # 301 raw keypoints for rectify: a snk_keypoint has 24 bytes, so the array ends off a 16-byte boundary
+    from test_oracle_preprocess import make_kps
+
+    rect = [make_kps(orc, 301, 700 + i) for i in range(3)]
+    return dict(stereo=stereo, bf=bf_sets, track=track, fine=fine, rect=rect)
 
 
 @functools.lru_cache(maxsize=None)
@@ -189,6 +213,14 @@ def pose_case(k):
     import pose_helpers as PH
 
     return PH.make_problem(77 + k, 300, outlier_frac=0.2)
+
+
+@functools.lru_cache(maxsize=None)
+def pose_odd_batch(k):
+    """1, 0, 37 and 299 matches in one call (tests/test_pose_gpu.py): 337 in all, an odd total, one problem empty"""
+    import pose_helpers as PH
+
+    return [PH.make_problem(150 + 10 * k + i, n, outlier_frac=0.2) for i, n in enumerate((1, 0, 37, 299))]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -288,7 +320,10 @@ def run_p3p(H, k):
     k %= 3
     s = H["objs"][0]
     res = s.solve_batch([dict(wps=c["wps"], nips=c["nips"]) for c in p3p_cases()[k]])
-    out = b"".join(cat(r["pose"], r["mask"], r["matches"]) + i32(r["inliers"], *r["best"]) for r in res)
+    start = [0.0, 0.0, 0.0, 1.0, 1.0, 2.0, 3.0]
+    odd = s.solve_batch([dict(wps=c["wps"], nips=c["nips"], pose=start) for c in p3p_odd_batch(k)])
+    assert odd[1]["inliers"] == 0 and odd[1]["best"] == (-1, -1) and np.array_equal(odd[1]["pose"], start)  # n = 0: the pose as it came in
+    out = b"".join(cat(r["pose"], r["mask"], r["matches"]) + i32(r["inliers"], *r["best"]) for r in res + odd)
     with on(H):
         got = p3p_dev_call(H, k)
         out += cat(*(t.cpu().numpy() for t in got))
@@ -360,7 +395,11 @@ def run_sim3(H, k):
             # 100 then 60 + k: the iteration table is refilled when a parameter it depends on changes
             for max_it in (100, 60 + k):
                 out += cat(*(t.cpu().numpy() for t in sim3_dev_call(H, k, cs, max_it)))
-    return out
+    p, T0, s0 = rs.params, [0.0, 0.0, 0.0, 1.0, 1.0, 2.0, 3.0], 0.5
+    p.iterations, p.compute_scale, p.max_iterations, p.seed = 100, 1, 100, 0x5EED0000ABCD + k
+    odd = rs.solve_batch([dict(points1=c["P1"], points2=c["P2"], ips1=c["ip1"], ips2=c["ip2"], T=T0, scale=s0) for c in sim3_odd_batch(k)])
+    assert odd[1]["inliers"] == 0 and odd[1]["best"] == -1 and np.array_equal(odd[1]["T"], T0) and odd[1]["scale"] == s0  # n = 0: as it came in
+    return out + b"".join(cat(r["T"], r["mask"]) + np.float64(r["scale"]).tobytes() + i32(r["inliers"], r["best"]) for r in odd)
 
 
 def make_tri(device=0, stream=None):
@@ -717,10 +756,23 @@ def make_stereo(device=0, stream=None):
     return _base(device, st, [Preprocess(device, st.cuda_stream)])
 
 
+def stereo_rect():
+    """EuRoC cam0 with its distortion, as Preprocess::undistortKeypoints has it"""
+    from snake_slam_amd.matcher import Rectification
+    from test_oracle_preprocess import EUROC_D, EUROC_K
+
+    return Rectification.make(EUROC_K, EUROC_D)
+
+
 def run_stereo(H, k):
     left, dl, right, dr, bf, ls = front_cases()["stereo"][k % 3]
-    n, rp, dp = H["objs"][0].StereoMatching(left, dl, right, dr, bf, ls, True)
-    return i32(n) + cat(rp, dp)
+    pp = H["objs"][0]
+    n, rp, dp = pp.StereoMatching(left, dl, right, dr, bf, ls, True)
+    # undistortKeypoints on the same handle, with and without the normalized points
+    und, norm = pp.rectify(stereo_rect(), front_cases()["rect"][k % 3], True)
+    und2, none = pp.rectify(stereo_rect(), front_cases()["rect"][k % 3], False)
+    assert none is None
+    return i32(n) + cat(rp, dp, und, norm, und2)
 
 
 def make_track(device=0, stream=None):
@@ -737,11 +789,16 @@ def track_bind(H, k):
 def track_search(H, k):
     """on the BOUND frame (frame = None): the coarse matcher, then the keyframe matcher -- which leaves its match count in the handle's
     counter buffer, the one the map-point refresh counts its wide points in"""
-    _, cam, pose, ls, pts, (pos, desc, skip) = front_cases()["track"][k % 3]
+    from snake_slam_amd.tracking import FeatureGrid
+
+    frame, cam, pose, ls, pts, (pos, desc, skip) = front_cases()["track"][k % 3]
     m = H["objs"][0]
     n, idx = m.SearchByProjectionFrameFrame2(None, cam, pose, pts, 15.0, 75, 0, ls)
     n_kf, idx_kf = m.SearchByProjectionFrameToKeyframe(None, cam, pose, pos, desc, skip, 15.0, 100)
-    return i32(n, n_kf) + cat(idx, idx_kf)
+    # the frame's grid (snk_feature_grid, from the keypoints in reverse order) and the fine matcher, on the seam's handle too
+    perm, cell_start, _, _ = FeatureGrid.create(m, frame["bounds"], frame["kps"][::-1])
+    n_f, idx_f, vis, valid = m.SearchByProjection2(None, cam, pose, front_cases()["fine"][k % 3], 5.0, 0.8, ls)
+    return i32(n, n_kf, n_f) + cat(idx, idx_kf, perm, cell_start, idx_f, vis, valid)
 
 
 def run_track(H, k):
@@ -761,7 +818,9 @@ def run_pose(H, k):
 
     pr = pose_case(k % 3)
     pose, outl, inl = H["objs"][0].refinePose(PH.CAM, pr["pose0"], pr["wps"], pr["obs"])
-    return cat(pose, outl) + i32(inl)
+    odd = H["objs"][0].refine_batch(PH.CAM, [dict(pose=p["pose0"], wps=p["wps"], obs=p["obs"]) for p in pose_odd_batch(k % 3)])
+    assert odd[1][2] == 0 and len(odd[1][1]) == 0  # n = 0: no inlier, no flag
+    return cat(pose, outl) + i32(inl) + b"".join(cat(p, o) + i32(n) for p, o, n in odd)
 
 
 SEAMS = {"p3p": (make_p3p, run_p3p), "sim3": (make_sim3, run_sim3), "tri": (make_tri, run_tri), "mappoint": (make_mappoint, run_mappoint),

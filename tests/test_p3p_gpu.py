@@ -65,6 +65,36 @@ def test_small_all_outlier_and_empty_inputs_return_cleanly(solver):
     assert r["inliers"] == 0 and r["best"] == (-1, -1) and np.array_equal(r["pose"], start)
 
 
+def odd_batch(seed=4400):
+    """three problems of 5, 0 and 33 pairs (30 % wrong pairs, 1 px noise): 38 pairs in all, so the world points (24 bytes a pair), the
+    match list and the mask end off a 16-byte boundary and the parts behind them begin on padding (stage.hpp); one problem is empty.
+    Shared with the p3p seam of tests/backend_cases.py."""
+    return [P.make_case(n, 0.3, 1.0, seed + i) for i, n in enumerate((5, 0, 33))]
+
+
+def test_batch_whose_parts_end_off_a_16_byte_boundary(solver):
+    """The winner's part of p3p_numpy.check_device_against_restatement, against the restatement under the problem's index; the empty
+    problem by what the header says of n < 4: the pose as it came in, no inlier, no winner."""
+    cs, seed, start = odd_batch(), 0xABCDEF0123456789, [0.0, 0.0, 0.0, 1.0, 1.0, 2.0, 3.0]
+    solver.params.iterations, solver.params.residual_threshold, solver.params.seed = 250, P.THRESHOLD, seed
+    res = solver.solve_batch([dict(wps=c["wps"], nips=c["nips"], pose=start) for c in cs])
+    for i, (r, c) in enumerate(zip(res, cs)):
+        n = len(c["wps"])
+        assert len(r["mask"]) == n and r["inliers"] == int(r["mask"].sum()) == len(r["matches"])
+        assert np.array_equal(r["matches"], np.nonzero(r["mask"])[0])
+        if n == 0:
+            assert r["inliers"] == 0 and r["best"] == (-1, -1) and np.array_equal(r["pose"], start)
+            continue
+        w = P.ransac(c["wps"], c["nips"], 250, P.THRESHOLD, seed, problem=i, pose=start)
+        H, (kb, _) = w["hyp"], w["best"]
+        if P.winner_is_exact(w):
+            assert r["best"] == w["best"] and r["inliers"] == w["inliers"], (i, r["best"], w["best"])
+            assert np.array_equal(r["mask"], w["mask"]) and np.array_equal(r["matches"], w["matches"])
+            assert P.device_pose_distance(r["pose"], H["R"][kb, w["slot"]], H["t"][kb, w["slot"]]) <= P.pose_tolerance()
+        elif kb >= 0:
+            assert r["inliers"] >= H["counts_lo"][kb, w["slot"]]
+
+
 def test_batch_uses_the_problem_index_and_two_runs_give_identical_bytes(solver):
     probs = [dict(wps=c["wps"], nips=c["nips"]) for c in CASES[6:]]
     solver.params.iterations, solver.params.residual_threshold, solver.params.seed = 250, P.THRESHOLD, 0xABCDEF0123456789

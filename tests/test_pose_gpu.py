@@ -74,6 +74,23 @@ def test_batch_of_frames_one_launch(orc):
         ref.close()
 
 
+def test_batch_whose_parts_end_off_a_16_byte_boundary(orc):
+    """1, 0, 37 and 299 matches in one call: 337 in all, so the world points (24 bytes a match) and the outlier bytes end off a 16-byte
+    boundary and the parts behind them begin on padding (stage.hpp); one problem is empty."""
+    from snake_slam_amd.tracking import PoseRefinement
+
+    prs = [PH.make_problem(50 + i, n, outlier_frac=0.2) for i, n in enumerate((1, 0, 37, 299))]
+    ref = PoseRefinement()
+    try:
+        res = ref.refine_batch(PH.CAM, [dict(pose=p["pose0"], wps=p["wps"], obs=p["obs"]) for p in prs])
+        for got, pr in zip(res, prs):
+            assert len(got[1]) == len(pr["wps"])
+            compare(orc, got, pr, orc.pose_options())
+        assert res[1][2] == 0 and len(res[1][1]) == 0
+    finally:
+        ref.close()
+
+
 def test_smooth_variant_with_prediction_prior(orc):
     from snake_slam_amd.tracking import PoseRefinement
 

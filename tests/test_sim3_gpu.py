@@ -106,6 +106,39 @@ def test_zero_iterations_use_the_table_count(solver, n):
     assert r["T"].tobytes() == a[0]["T"].tobytes() and r["inliers"] == a[0]["inliers"]
 
 
+def odd_batch(seed=4500):
+    """three problems of 3, 0 and 65 pairs (Sim3, 30 % wrong pairs, 1 px noise, 100 iterations): 68 pairs in all, so the mask ends off
+    a 16-byte boundary and begins on the padding behind three result records (stage.hpp); one problem is empty, and 65 crosses the
+    64 / 65 case.  Shared with the sim3 seam of tests/backend_cases.py."""
+    return [S.make_case(n, 0.3, 1.0, True, 100, seed + i) for i, n in enumerate((3, 0, 65))]
+
+
+def test_batch_whose_parts_end_off_a_16_byte_boundary(solver):
+    """The winner's part of sim3_numpy.check_device_against_restatement, against the restatement under the problem's index; the empty
+    problem by what the header says of n < 3: T and scale as they came in, no inlier, no winner."""
+    cs, seed, T0, s0 = odd_batch(), 0xABCDEF0123456789, [0.0, 0.0, 0.0, 1.0, 1.0, 2.0, 3.0], 0.5
+    probs = [dict(setup(solver, c, 100), T=T0, scale=s0) for c in cs]
+    solver.params.seed = seed
+    res = solver.solve_batch(probs)
+    for i, (r, c) in enumerate(zip(res, cs)):
+        n = len(c["P1"])
+        assert len(r["mask"]) == n and r["inliers"] == int(r["mask"].sum())
+        if n == 0:
+            assert r["inliers"] == 0 and r["best"] == -1 and np.array_equal(r["T"], T0) and r["scale"] == s0
+            continue
+        w = S.ransac(c["P1"], c["P2"], c["ip1"], c["ip2"], 100, c["threshold"], True, seed, problem=i, T=T0, scale=s0)
+        H, kb = w["hyp"], w["best"]
+        if S.winner_is_exact(w):
+            assert r["best"] == kb and r["inliers"] == w["inliers"] and np.array_equal(r["mask"], w["mask"]), (i, r["best"], kb)
+            assert S.device_distance(r["T"], r["scale"], H["R"][kb], H["t"][kb], H["s"][kb]) <= S.transform_tolerance()
+        elif kb >= 0:
+            assert r["inliers"] >= H["counts_lo"][kb]
+        else:
+            assert r["best"] == -1 or H["borderline"][r["best"]]
+        if r["best"] < 0:
+            assert r["inliers"] == 0 and np.array_equal(r["T"], T0) and r["scale"] == s0
+
+
 def test_batch_uses_the_problem_index_and_two_runs_give_identical_bytes(solver):
     sel = [c for c in CASES if c["compute_scale"] and len(c["P1"]) >= 63]
     probs = [setup(solver, c, 300) for c in sel]

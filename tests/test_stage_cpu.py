@@ -1,4 +1,4 @@
-"""CPU: snake_slam_amd/csrc/stage.hpp -- the layout every map-side host entry stages its arrays in -- compiled with plain g++ (no HIP)
+"""CPU: snake_slam_amd/csrc/stage.hpp -- the layout the host entries stage their arrays in -- compiled with plain g++ (no HIP)
 into tests/cpp/stage_driver.cpp.  Offsets, `bytes` and `end()` must equal the restatement below; `copy` must write exactly the parts
 that have a source and a size, and leave every other byte of the buffer (the padding, the parts without a source, 16 bytes behind the
 block) as it found it."""
