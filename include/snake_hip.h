@@ -1431,6 +1431,26 @@ SNK_API int snk_ba_sync(snk_ba* h);
 SNK_API int snk_ba_set_problem(snk_ba* h, const snk_ba_problem* problem);
 SNK_API int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count);
 
+/* The same hand-over from DEVICE memory -- BARecRel::create (LocalBundleAdjustment.cpp:359) on the scenes a device-side MakeLocalScene
+ * (LocalBundleAdjustment.cpp:94-346) left there: out_dev is the struct snk_scene_gather_batch_dev takes, a host struct of device pointers
+ * (result [n_q] on the device too) with its four caps.  Problem s is row s with the sizes result[s].n_img / n_pt / n_obs / n_rpc, caller
+ * order = the row's order; K and bf apply to every problem.  A row with status != SNK_SCENE_OK has all counts 0 and becomes an EMPTY
+ * problem in slot s, so problem indices stay query indices -- and, like any problem without a free camera, an empty problem takes the
+ * whole batch off the point-major pass: compact such rows away before the call where that matters.  rpc == NULL: no constraints.
+ * obs_src, img_kf, pt_id and pt_valid are not read.  The values and the sorted observation arrays are written by kernels straight into
+ * the handle's buffers; the host reads back about five bytes per observation of structure (free-camera indices, constant flags, point
+ * starts, the constraint records) for the list stages that still run there, where snk_ba_set_problems carries 40 and more up.  A batch
+ * with a problem of more than 8192 points, or with a point that holds more than 1024 valid observations, is staged instead: its rows
+ * are copied down and go through snk_ba_set_problems' own path; the result is the same.
+ * ORDER: the rows must be complete on the BA handle's stream, or the caller has synchronised their producer; the call waits for the
+ * handle's stream, not for any other.  The rest of the contract is snk_ba_set_problems': the arrays are copied and need not stay
+ * alive, n_q <= 65535, the implicit form takes one problem, any failure leaves NO problem set; after success every other snk_ba_* entry
+ * point behaves as after snk_ba_set_problems on the same data.  Everything is checked before a kernel reads a row: a NULL handle,
+ * struct, K, result or row array other than rpc / obs_src / img_kf / pt_id / pt_valid, a cap outside [1, limit] (the limits of
+ * snk_scene_gather), n_q outside 1..65535, and -- the n_q records are read first, one small copy and one wait -- a record with a
+ * negative count or a count above its cap (n_rpc above win_cap): SNK_ERR_INVALID_ARG.  Nothing past a row's counts is read. */
+SNK_API int snk_ba_set_problems_dev(snk_ba* h, int n_q, const snk_scene_out* out_dev, const double K[4], double bf);
+
 /* Saiga's BAOptions::buildExplizitSchur: the reference's local BA asks for the explicit Schur complement
  * (Snake/Optimizer/LocalBundleAdjustment.cpp:59), its global BA leaves it unset (Snake/Optimizer/GlobalBundleAdjustment.cpp:32-43)
  * and gets the implicit form.  1 (the default): the reduced camera system S is formed as a dense n6 x n6 matrix.  0: S is never

@@ -155,6 +155,7 @@ SIGNATURES = {
     "snk_ba_set_explicit_schur": (i32, [vp, i32]),
     "snk_ba_set_problem": (i32, [vp, vp]),
     "snk_ba_set_problems": (i32, [vp, vp, i32]),
+    "snk_ba_set_problems_dev": (i32, [vp, i32, vp, vp, f64]),
     "snk_ba_set_outliers": (i32, [vp, i32, vp]),
     "snk_ba_solve": (i32, [vp, i32, vp, vp]),
     "snk_ba_solve_async": (i32, [vp, i32]),

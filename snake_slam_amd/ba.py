@@ -105,6 +105,28 @@ class BARec:
         self.last_pack_ms, self.last_set_problems_ms = (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3
         self._scenes = scenes
 
+    def create_dev(self, out: dict, K, bf: float) -> None:
+        """snk_ba_set_problems_dev: the hand-over from the DEVICE rows of ``LocalSceneBuilder.gather_dev`` (``out``: the dict of device
+        tensors that ``scene.out_struct`` takes: the rows, ``result`` [n_q, 6] int32 and the four caps).  Problem s is row s; a row whose
+        status is not OK is an empty problem.  The rows must be complete on this handle's stream, or their producer synchronised.  Only
+        the n_q result records come to the host here (the sizes that ``state`` / ``residuals`` / ``solve_local_scene`` allocate by)."""
+        import time
+
+        from .scene import OK, out_struct
+
+        cout = out_struct(out)
+        n_q = int(out["result"].shape[0])
+        k = (C.c_double * 4)(*[float(x) for x in K])
+        self._scenes = []
+        t0 = time.perf_counter()
+        _lib.check(self._lib.snk_ba_set_problems_dev(self._h, n_q, C.byref(cout), k, float(bf)), "snk_ba_set_problems_dev")
+        self.last_pack_ms, self.last_set_problems_ms = 0.0, (time.perf_counter() - t0) * 1e3
+        res = np.ascontiguousarray(out["result"].cpu().numpy()).reshape(n_q, -1).view(np.int32).reshape(n_q, 6)  # (int32 or raw bytes)
+        has_rpc = out.get("rpc") is not None
+        sizes = [(int(r[1]), int(r[2]), int(r[3]), int(r[4]) if has_rpc else 0) if int(r[5]) == OK else (0, 0, 0, 0) for r in res]
+        # what the other methods read of a scene: the lengths
+        self._scenes = [dict(pose=range(ni), pt=range(npt), obs_img=range(no), rpc=range(nr), K=list(K), bf=float(bf)) for ni, npt, no, nr in sizes]
+
     def _solve(self, iterations):
         n = len(self._scenes)
         ci = np.zeros(n, np.float64)

@@ -1746,6 +1746,38 @@ class BARec
         check(snk_ba_set_explicit_schur(h_, buildExplizitSchur ? 1 : 0), "snk_ba_set_explicit_schur");
         check(snk_ba_set_problem(h_, &p), "snk_ba_set_problem");
     }
+    // The hand-over from DEVICE rows (snk_ba_set_problems_dev): out_dev is what LocalSceneBuilder's device form filled, a host struct of
+    // device pointers; problem s is row s, a row whose status is not SNK_SCENE_OK an empty problem.  The rows must be complete on the
+    // handle's stream (the default one here) or their producer synchronised.  No Scene stands behind these problems: solveAll() and
+    // handle() (snk_ba_get_state, snk_ba_residuals, snk_ba_solve_local_scene per problem) read the results.
+    void createDev(int n_q, const snk_scene_out& out_dev, const double K[4], double bf)
+    {
+        scene_ = nullptr;
+        count_ = 0;
+        if (h_ && std::memcmp(&created_with_, &optimizationOptions, sizeof(snk_ba_options)) != 0)
+        {
+            snk_ba_destroy(h_);
+            h_ = nullptr;
+        }
+        if (!h_)
+        {
+            check(snk_ba_create(&optimizationOptions, device_, nullptr, &h_), "snk_ba_create");
+            created_with_ = optimizationOptions;
+        }
+        check(snk_ba_set_explicit_schur(h_, buildExplizitSchur ? 1 : 0), "snk_ba_set_explicit_schur");
+        check(snk_ba_set_problems_dev(h_, n_q, &out_dev, K, bf), "snk_ba_set_problems_dev");
+        count_ = n_q;
+    }
+    // initAndSolve() of every problem createDev loaded
+    std::vector<OptimizationResults> solveAll()
+    {
+        std::vector<double> ci((size_t)count_ + 1), cf((size_t)count_ + 1);
+        check(snk_ba_solve(h_, optimizationOptions.max_iterations, ci.data(), cf.data()), "snk_ba_solve");
+        std::vector<OptimizationResults> r((size_t)count_);
+        for (int b = 0; b < count_; ++b) r[(size_t)b].cost_initial = ci[(size_t)b], r[(size_t)b].cost_final = cf[(size_t)b];
+        return r;
+    }
+    snk_ba* handle() const { return h_; }
     OptimizationResults initAndSolve() { return solve(); }
     OptimizationResults solve()
     {
@@ -1794,6 +1826,7 @@ class BARec
     int device_;
     snk_ba* h_    = nullptr;
     Scene* scene_ = nullptr;
+    int count_    = 0;  // problems createDev loaded
     snk_ba_options created_with_{};
     std::vector<uint8_t> all_const_;
 };

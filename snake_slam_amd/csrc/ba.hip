@@ -4603,7 +4603,8 @@ int snk_ba_destroy(snk_ba* h)
                      &h->d_W, &h->d_ptv, &h->d_Vinv, &h->d_bp, &h->d_cost, &h->d_cost_new, &h->d_U, &h->d_camstart,
                      &h->d_camitems, &h->d_blkstart, &h->d_blkent, &h->d_S, &h->d_rhs, &h->d_x, &h->d_chi2,
                      &h->d_pcgw, &h->d_optidx, &h->d_wvpt, &h->d_rpcmeta, &h->d_rpcnext, &h->d_camrpcstart,
-                     &h->d_camrpcitems, &h->d_blkrpc, &h->d_rpcout, &h->d_becnt, &h->d_probcond, &h->d_campart, &h->d_ccstart, &h->d_ccitems};
+                     &h->d_camrpcitems, &h->d_blkrpc, &h->d_rpcout, &h->d_becnt, &h->d_probcond, &h->d_campart, &h->d_ccstart, &h->d_ccitems, &h->d_hoplace,
+                     &h->d_hoout};
     for (DevBuf* b : all) b->release();
     h->h_stage.release();
     h->drop_graphs();

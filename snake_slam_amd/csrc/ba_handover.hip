@@ -19,6 +19,10 @@
 //                       gather_cam_records, gather_set_records, block_entries_count / _scan / _fill
 //   check_lists         SNK_BA_CHECK_LISTS=1: the device-built lists against the host builder and the caller's arrays
 //   report              SNK_BA_PROFILE_CREATE=1: the two [snk_ba_set_problems] lines
+// snk_ba_set_problems_dev takes the scenes as device rows (snk_scene_out): dev_stage -- ho_count_kernel, a read-back, ho_fill_kernel, a
+// read-back -- stands where size_pass, place_problems and fill_and_send do, dev_check compares it with them under SNK_BA_CHECK_LISTS=1,
+// and build_problem_lists .. report run unchanged on a host shadow of the problems.  Batches the kernels do not take (handover_core.hpp)
+// are copied down (RowsOnHost) and go through the stages above.
 // A stage that fails returns the error code; the guard in snk_ba_set_problems then leaves the handle without a problem set.
 #include "ba_types.hpp"
 
@@ -120,6 +124,7 @@ __global__ __launch_bounds__(256) void gather_set_records(Arrays A, SetObs* __re
 // run are a bit mask (BE_WORDS x 64 bits in registers); ballot(c2 in mask) ranks the lane inside the chunk for block (c1, c2).
 // Order inside a block = list order of c1 = ascending observation index = ascending point: the host builder's order.
 constexpr int BE_WORDS = 8, BE_MAX_CAMS = 64 * BE_WORDS;
+static_assert(BE_MAX_CAMS == HO_DUP_MAX_CAMS, "the dup rule of handover_core.hpp covers the cameras the device builder takes");
 __device__ inline void block_entry_item(const Arrays& A, const Prob& pr, int c1, int chunk, int lane, int& a, int& p, int& r0, int& r1,
                                         unsigned long long (&mask)[BE_WORDS])
 {
@@ -288,6 +293,161 @@ int upload(DevBuf& b, const V& v, CopyTab& tab)
     return SNK_OK;
 }
 
+// ---- the device stage of snk_ba_set_problems_dev ---------------------------------------------------------------------------------
+// The caller's rows are on the device (snk_scene_out): what size_pass, place_problems and fill_problem do on the host threads -- and the
+// bus carries up afterwards -- is done by two kernels, one workgroup per problem, with the rules of handover_core.hpp.  The host reads
+// back what its later stages need (camidx, pt_const, ptstart, the sorted o_cam, five ints per problem) and places the problems between
+// the two launches.  Nothing is placed by the return value of an atomic: the histogram's LDS additions commute, and the order inside a
+// point is the caller's by construction (chunks in order, ho_chunk_rank inside a chunk).
+struct HoRows  // the rows of snk_scene_out that are read
+{
+    int img_cap, pt_cap, obs_cap;
+    const double* pose;
+    const uint8_t* img_const;
+    const double* pt;
+    const uint8_t* pt_const;
+    const int* obs_img;
+    const int* obs_pt;
+    const double* obs_uv;
+    const double* obs_depth;
+    const double* obs_weight;
+};
+
+// values, free-camera indices, valid observations per point -> pt_start; HoOut::nfc / no / k_over8 / long_run
+__global__ __launch_bounds__(HO_THREADS) void ho_count_kernel(HoRows R, const HoPlace* __restrict__ place, HoOut* __restrict__ out, double* __restrict__ d_pose,
+                                                              double* __restrict__ d_pt, unsigned char* __restrict__ d_ptc, int* __restrict__ d_camidx,
+                                                              int* __restrict__ d_ptstart)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ho_smem[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const HoPlace pl = place[b];
+    unsigned* s_misc = reinterpret_cast<unsigned*>(ho_smem);  // [0, 8) block_scan, [8] k_over8, [9] long_run
+    int* s_cnt  = reinterpret_cast<int*>(s_misc + HO_MISC);   // [n_pt] valid observations
+    int* s_free = s_cnt + pl.n_pt;                             // [n_pt] observations by free cameras
+    const size_t ri = (size_t)b * R.img_cap, rp = (size_t)b * R.pt_cap, ro = (size_t)b * R.obs_cap;
+    const uint8_t* img_const = R.img_const + ri;
+    const uint8_t* pt_const  = R.pt_const + rp;
+    for (int k = tid; k < 7 * pl.n_img; k += HO_THREADS) d_pose[7 * (size_t)pl.img_at + k] = R.pose[7 * ri + k];
+    for (int k = tid; k < 3 * pl.n_pt; k += HO_THREADS) d_pt[3 * (size_t)pl.pt_at + k] = R.pt[3 * rp + k];
+    for (int p = tid; p < pl.n_pt; p += HO_THREADS)
+    {
+        d_ptc[(size_t)pl.pt_at + p] = pt_const[p] ? 1 : 0;
+        s_cnt[p] = 0, s_free[p] = 0;
+    }
+    if (tid == 0) s_misc[8] = 0u, s_misc[9] = 0u;
+    int pass = 0, nfc = 0;
+    for (int i0 = 0; i0 < pl.n_img; i0 += HO_THREADS)  // (uniform trip count: every lane scans)
+    {
+        const int i    = i0 + tid;
+        const int free = i < pl.n_img && !img_const[i] ? 1 : 0;
+        int tot;
+        const int before = block_scan<HO_THREADS>(free, tot, s_misc, pass);
+        if (i < pl.n_img) d_camidx[(size_t)pl.img_at + i] = ho_cam_index(!free, nfc + before);
+        nfc += tot;
+    }
+    __syncthreads();
+    for (int o = tid; o < pl.n_obs; o += HO_THREADS)
+    {
+        const int i = R.obs_img[ro + o], p = R.obs_pt[ro + o];
+        if (ho_obs_valid(i, p, pl.n_img, pl.n_pt, img_const, pt_const)) atomicAdd(&s_cnt[p], 1);
+        if (ho_obs_by_free_camera(i, p, pl.n_img, pl.n_pt, img_const)) atomicAdd(&s_free[p], 1);
+    }
+    __syncthreads();
+    int no = 0;
+    for (int p0 = 0; p0 < pl.n_pt; p0 += HO_THREADS)
+    {
+        const int p = p0 + tid;
+        const int v = p < pl.n_pt ? s_cnt[p] : 0;
+        int tot;
+        const int before = block_scan<HO_THREADS>(v, tot, s_misc, pass);
+        if (p < pl.n_pt)
+        {
+            d_ptstart[(size_t)pl.ps_at + p] = no + before;
+            if (ho_k_over8(s_free[p])) s_misc[8] = 1u;  // (every writer writes the same word)
+            if (!ho_run_taken(v)) s_misc[9] = 1u;
+        }
+        no += tot;
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+        d_ptstart[(size_t)pl.ps_at + pl.n_pt] = no;
+        HoOut r;
+        r.nfc = nfc, r.no = no, r.k_over8 = (int)s_misc[8], r.long_run = (int)s_misc[9], r.dup = 0;
+        out[b] = r;
+    }
+}
+
+// the sorted observation arrays (and o_cam, which the host's readback needs before the problem table exists); HoOut::dup
+__global__ __launch_bounds__(HO_THREADS) void ho_fill_kernel(HoRows R, const HoPlace* __restrict__ place, HoOut* __restrict__ out, const int* __restrict__ d_camidx,
+                                                             const int* __restrict__ d_ptstart, int* __restrict__ o_img, int* o_cam, double2* __restrict__ o_uv,
+                                                             double* __restrict__ o_depth, double* __restrict__ o_weight, int* __restrict__ o_orig)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ho_smem[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const HoPlace pl = place[b];
+    const HoOut cnt  = out[b];  // what ho_count_kernel left
+    unsigned* s_misc = reinterpret_cast<unsigned*>(ho_smem);  // [0] dup
+    int* s_keys = reinterpret_cast<int*>(s_misc + HO_MISC);   // [HO_THREADS] the chunk's points, -1: not valid
+    int* s_cur  = s_keys + HO_THREADS;                        // [n_pt] next free slot of the point
+    const size_t ri = (size_t)b * R.img_cap, rp = (size_t)b * R.pt_cap, ro = (size_t)b * R.obs_cap;
+    const uint8_t* img_const = R.img_const + ri;
+    const uint8_t* pt_const  = R.pt_const + rp;
+    const int* cidx          = d_camidx + pl.img_at;
+    for (int p = tid; p < pl.n_pt; p += HO_THREADS) s_cur[p] = d_ptstart[(size_t)pl.ps_at + p];
+    if (tid == 0) s_misc[0] = 0u;
+    __syncthreads();
+    for (int c0 = 0; c0 < pl.n_obs; c0 += HO_THREADS)  // consecutive chunks in caller order
+    {
+        const int o = c0 + tid;
+        int i = 0, p = 0;
+        bool valid = false;
+        if (o < pl.n_obs)
+        {
+            i = R.obs_img[ro + o], p = R.obs_pt[ro + o];
+            valid = ho_obs_valid(i, p, pl.n_img, pl.n_pt, img_const, pt_const);
+        }
+        s_keys[tid] = valid ? p : -1;
+        __syncthreads();
+        int before = 0, total = 0, base = 0;
+        if (valid)
+        {
+            ho_chunk_rank(s_keys, HO_THREADS / 4, tid, before, total);
+            base = s_cur[p];
+        }
+        __syncthreads();  // every cursor of the chunk is read, every key compared
+        if (valid)
+        {
+            if (before + 1 == total) s_cur[p] = base + total;  // the point's last observation of the chunk: one writer per cursor
+            const size_t go = (size_t)pl.obs_at + base + before;
+            if (base + before >= cnt.no) continue;  // (rows that changed between the two kernels: never outside the problem's range)
+            o_img[go]    = i;
+            o_cam[go]    = cidx[i];
+            o_uv[go]     = make_double2(R.obs_uv[2 * (ro + o)], R.obs_uv[2 * (ro + o) + 1]);
+            o_depth[go]  = R.obs_depth[ro + o];
+            o_weight[go] = R.obs_weight[ro + o];
+            o_orig[go]   = pl.orig_at + o;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();  // s_cur[p] is now the END of point p's run; the workgroup's o_cam is written
+    if (ho_dup_words(cnt.nfc) > 0)
+        for (int s = tid; s < cnt.no; s += HO_THREADS)
+        {
+            int lo = -1, hi = pl.n_pt - 1;  // the smallest p with s_cur[p] > s: end(lo) <= s < end(hi)
+            while (hi - lo > 1)
+            {
+                const int mid = (lo + hi) >> 1;
+                if (s_cur[mid] <= s) lo = mid;
+                else hi = mid;
+            }
+            const int begin = hi > 0 ? s_cur[hi - 1] : 0;
+            if (ho_cam_seen_before(o_cam + pl.obs_at, begin, s)) s_misc[0] = 1u;
+        }
+    __syncthreads();
+    if (tid == 0) out[b].dup = (int)s_misc[0];
+}
+
 // ---- what the stages hand to each other ----
 
 // Written by size_pass (nfc, no, k_over8), place_problems (*_at) and fill_problem (dup); read by every later stage.
@@ -453,11 +613,16 @@ struct PointSets
     }
 };
 
-struct HandOver  // one snk_ba_set_problems call
+struct RowsOnHost;
+
+struct HandOver  // one snk_ba_set_problems or snk_ba_set_problems_dev call
 {
     snk_ba* const h;
-    const snk_ba_problem* const problems;
+    // the caller's problems; snk_ba_set_problems_dev: a host shadow of the device rows (sizes, K, bf; img_const, pt_const and rpc point
+    // at pinned read-backs; the pose, point and observation pointers are NULL), or the downloaded rows under SNK_BA_CHECK_LISTS
+    const snk_ba_problem* problems;
     const int count;
+    const bool dev;  // snk_ba_set_problems_dev: the values and the sorted observation arrays are written on the device (dev_stage)
     const bool imp;  // implicit Schur form (snk_ba_set_explicit_schur): one scene; nothing sized (free cameras)^2 is built or allocated
     BaLists& L;      // the handle's pinned lists, capacity kept from the previous set
     const Switches sw;
@@ -484,15 +649,24 @@ struct HandOver  // one snk_ba_set_problems call
     const bool dup_on_device;
     CopyTab tab{}, tab2{};  // the upload (host -> device, zero fills) and the device-to-device copies behind it
     std::chrono::steady_clock::time_point t_begin, t_lists, t_up, t_rs;
+    long long bytes_up = 0, bytes_down = 0;    // over the bus, host -> device and device -> host (SNK_BA_PROFILE_CREATE)
+    long long dev_stage_us = 0, readback_us = 0;  // snk_ba_set_problems_dev: the two kernels (with their waits), the copies down
+    bool dev_long_run = false;                  // dev_stage met a point with more than HO_MAX_RUN observations: the batch is staged
 
-    HandOver(snk_ba* handle, const snk_ba_problem* p, int n)
-        : h(handle), problems(p), count(n), imp(handle->explicit_schur == 0), L(handle->lists), sw(Switches::read()),
-          want_big_items(n >= 256 && !sw.alt_paths), early_upload(n >= 16), dup_on_device(n >= 16)
+    // device rows: every count derives o_pt / o_cam / o_ptfree / cam_items on the device and copies device-to-device
+    HandOver(snk_ba* handle, const snk_ba_problem* p, int n, bool from_device = false)
+        : h(handle), problems(p), count(n), dev(from_device), imp(handle->explicit_schur == 0), L(handle->lists), sw(Switches::read()),
+          want_big_items(n >= 256 && !sw.alt_paths), early_upload(n >= 16 || from_device), dup_on_device(n >= 16 || from_device)
     {
     }
 
     int check_arguments();
     int reserve_lists();
+    void pick_threads();
+    int dev_stage(const snk_scene_out& rows, snk_ba_problem* shadow);
+    int dev_check(const snk_scene_out& rows, RowsOnHost& host_rows, const std::vector<snk_scene_result>& rec);
+    int later_stages();
+    int host_hand_over();
     int size_pass();
     int place_problems();
     void fill_problem(int b);
@@ -606,9 +780,13 @@ int HandOver::reserve_lists()
         t_pt += (size_t)std::max(problems[b].n_pt, 0);
         t_obs += (size_t)std::max(problems[b].n_obs, 0);
     }
-    L.pose.reserve(7 * t_img), L.pt.reserve(3 * t_pt), L.ptc.reserve(t_pt), L.camidx.reserve(t_img), L.ptstart.reserve(t_pt + (size_t)count);
-    L.ouv2.reserve(2 * t_obs), L.odepth.reserve(t_obs), L.oweight.reserve(t_obs), L.optfree.reserve(t_obs), L.oimg.reserve(t_obs);
-    L.ocam.reserve(t_obs), L.oorig.reserve(t_obs), L.optidx.reserve(t_obs), L.camitems.reserve(t_obs);
+    L.ptc.reserve(t_pt), L.camidx.reserve(t_img), L.ptstart.reserve(t_pt + (size_t)count), L.ocam.reserve(t_obs), L.camitems.reserve(t_obs);
+    if (!dev)  // (device rows: the values and the other observation arrays never exist on the host)
+    {
+        L.pose.reserve(7 * t_img), L.pt.reserve(3 * t_pt);
+        L.ouv2.reserve(2 * t_obs), L.odepth.reserve(t_obs), L.oweight.reserve(t_obs), L.optfree.reserve(t_obs), L.oimg.reserve(t_obs);
+        L.oorig.reserve(t_obs), L.optidx.reserve(t_obs);
+    }
     // ... and so are the lists of the point-major pass when they will be built (batches, big scenes): on a 300-keyframe
     // scene the doubling of setobs / cblkstart / cblkitems through fresh pinned allocations was 17 of the 26 ms of a
     // first hand-over (the same scene again on the handle, capacities kept: 8 ms)
@@ -639,7 +817,7 @@ int HandOver::reserve_lists()
 // places directly -- disjoint ranges, no locks.  The later stages only READ these lists.  Same contents as the serial
 // builder : SNK_BA_CHECK_LISTS and the bit-identity tests of the variants suite cover it.
 // size_pass writes PreProb::nfc / no / k_over8 and big_items.
-int HandOver::size_pass()
+void HandOver::pick_threads()
 {
     if (count >= 16)
     {
@@ -650,6 +828,11 @@ int HandOver::size_pass()
     }
     else if (sw.host_threads > 0 && count >= 2)
         n_threads = std::min(sw.host_threads, count);  // tests force the threaded form on small batches
+}
+
+int HandOver::size_pass()
+{
+    pick_threads();
     SNK_TRY(threaded(0, count, [&](int b)
     {
         const snk_ba_problem& P = problems[b];
@@ -658,12 +841,7 @@ int HandOver::size_pass()
         for (int i = 0; i < P.n_img; ++i) q.nfc += P.img_const[i] ? 0 : 1;
         int no = 0;
         for (int o = 0; o < P.n_obs; ++o)
-        {
-            const int i = P.obs_img[o], p = P.obs_pt[o];
-            if (i < 0 || i >= P.n_img || p < 0 || p >= P.n_pt) continue;
-            if (P.img_const[i] && P.pt_const[p]) continue;  // reference LocalBundleAdjustment.cpp:286
-            ++no;
-        }
+            if (ho_obs_valid(P.obs_img[o], P.obs_pt[o], P.n_img, P.n_pt, P.img_const, P.pt_const)) ++no;  // handover_core.hpp
         q.no  = no;
         q.dup = 0;
         q.k_over8 = 0;
@@ -673,9 +851,9 @@ int HandOver::size_pass()
             std::vector<unsigned char> kfree((size_t)P.n_pt, 0);
             for (int o = 0; o < P.n_obs; ++o)
             {
-                const int i = P.obs_img[o], p = P.obs_pt[o];
-                if (i < 0 || i >= P.n_img || p < 0 || p >= P.n_pt || P.img_const[i]) continue;
-                if (++kfree[(size_t)p] > 8) q.k_over8 = 1;
+                const int p = P.obs_pt[o];
+                if (!ho_obs_by_free_camera(P.obs_img[o], p, P.n_img, P.n_pt, P.img_const)) continue;
+                if (ho_k_over8(++kfree[(size_t)p])) q.k_over8 = 1;
             }
         }
     }));
@@ -684,6 +862,248 @@ int HandOver::size_pass()
         big_items = true;
         for (int b = 0; b < count; ++b) big_items = big_items && !pre[(size_t)b].k_over8;
     }
+    return SNK_OK;
+}
+
+// ---- snk_ba_set_problems_dev: size_pass, place_problems and fill_and_send on the device ----
+// Reads the sizes of the shadow problems; writes d_pose .. d_oorig and d_ocam in full, PreProb, and what the later host stages read of L
+// (camidx, ptc, ptstart, ocam); completes the shadow (img_const, pt_const, rpc).  Two launches, two waits: the problems' places in the
+// observation arrays depend on the valid counts (obs_off advances by them in merge_decide), which the first kernel reports.
+int HandOver::dev_stage(const snk_scene_out& rows, snk_ba_problem* shadow)
+{
+    using clk = std::chrono::steady_clock;
+    auto us_since = [](clk::time_point a) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - a).count(); };
+    hipStream_t st = h->stream;
+    pick_threads();
+    size_t a_img = 0, a_pt = 0, a_ps = 0;
+    long long a_orig = 0;
+    int max_np = 0, max_rpc = 0;
+    L.hoplace.resize((size_t)count), L.hoout.resize((size_t)count);
+    for (int b = 0; b < count; ++b)
+    {
+        const snk_ba_problem& P = problems[b];
+        PreProb& q = pre[(size_t)b];
+        q.img_at = a_img, q.pt_at = a_pt, q.ps_at = a_ps, q.obs_at = 0, q.orig_at = (int)a_orig;
+        HoPlace& pl = L.hoplace[(size_t)b];
+        pl.n_img = P.n_img, pl.n_pt = P.n_pt, pl.n_obs = P.n_obs;
+        pl.img_at = (int)a_img, pl.pt_at = (int)a_pt, pl.ps_at = (int)a_ps, pl.orig_at = (int)a_orig, pl.obs_at = 0;
+        a_img += (size_t)P.n_img, a_pt += (size_t)P.n_pt, a_ps += (size_t)P.n_pt + 1, a_orig += P.n_obs;
+        SNK_REQUIRE(a_orig < (1ll << 31) && a_ps < ((size_t)1 << 31) && a_img * 7 < ((size_t)1 << 31), "scene list too large (observations)");
+        max_np = std::max(max_np, P.n_pt), max_rpc = std::max(max_rpc, P.n_rpc);
+    }
+    HoRows R;
+    R.img_cap = rows.img_cap, R.pt_cap = rows.pt_cap, R.obs_cap = rows.obs_cap;
+    R.pose = rows.pose, R.img_const = rows.img_const, R.pt = rows.pt, R.pt_const = rows.pt_const;
+    R.obs_img = rows.obs_img, R.obs_pt = rows.obs_pt, R.obs_uv = rows.obs_uv, R.obs_depth = rows.obs_depth, R.obs_weight = rows.obs_weight;
+    SNK_TRY(h->d_pose.reserve(std::max<size_t>(a_img, 1) * 7 * sizeof(double)));
+    SNK_TRY(h->d_pt.reserve(std::max<size_t>(a_pt, 1) * 3 * sizeof(double)));
+    SNK_TRY(h->d_ptc.reserve(std::max<size_t>(a_pt, 1)));
+    SNK_TRY(h->d_camidx.reserve(std::max<size_t>(a_img, 1) * sizeof(int)));
+    SNK_TRY(h->d_ptstart.reserve(a_ps * sizeof(int)));
+    SNK_TRY(h->d_hoplace.reserve((size_t)count * sizeof(HoPlace)));
+    SNK_TRY(h->d_hoout.reserve((size_t)count * sizeof(HoOut)));
+    SNK_TRY(set_max_lds_once(reinterpret_cast<const void*>(ho_count_kernel), (int)ho_count_carve(HO_MAX_PTS)));
+    SNK_TRY(set_max_lds_once(reinterpret_cast<const void*>(ho_fill_kernel), (int)ho_fill_carve(HO_MAX_PTS)));
+    auto t0 = clk::now();
+    SNK_HIP_CHECK(hipMemcpyAsync(h->d_hoplace.p, L.hoplace.data(), (size_t)count * sizeof(HoPlace), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ho_count_kernel, dim3(count), dim3(HO_THREADS), ho_count_carve(max_np), st, R, h->d_hoplace.as<const HoPlace>(), h->d_hoout.as<HoOut>(),
+                       h->d_pose.as<double>(), h->d_pt.as<double>(), h->d_ptc.as<unsigned char>(), h->d_camidx.as<int>(), h->d_ptstart.as<int>());
+    SNK_LAUNCH_CHECK();
+    SNK_HIP_CHECK(hipStreamSynchronize(st));
+    dev_stage_us += us_since(t0);
+    // first readback: the counts, and the structure that depends on no placement
+    t0 = clk::now();
+    L.camidx.resize(a_img), L.ptc.resize(a_pt), L.ptstart.resize(a_ps), L.imgc.resize(std::max<size_t>(a_img, 1));
+    SNK_HIP_CHECK(hipMemcpyAsync(L.hoout.data(), h->d_hoout.p, (size_t)count * sizeof(HoOut), hipMemcpyDeviceToHost, st));
+    if (a_img) SNK_HIP_CHECK(hipMemcpyAsync(L.camidx.data(), h->d_camidx.p, a_img * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (a_pt) SNK_HIP_CHECK(hipMemcpyAsync(L.ptc.data(), h->d_ptc.p, a_pt, hipMemcpyDeviceToHost, st));
+    SNK_HIP_CHECK(hipMemcpyAsync(L.ptstart.data(), h->d_ptstart.p, a_ps * sizeof(int), hipMemcpyDeviceToHost, st));
+    L.rpcrows.resize((size_t)count * (size_t)std::max(max_rpc, 1));
+    if (max_rpc > 0)  // the first n_rpc records of every row (the rows are win_cap apart)
+        SNK_HIP_CHECK(hipMemcpy2DAsync(L.rpcrows.data(), (size_t)max_rpc * sizeof(snk_ba_rpc), rows.rpc, (size_t)rows.win_cap * sizeof(snk_ba_rpc),
+                                       (size_t)max_rpc * sizeof(snk_ba_rpc), (size_t)count, hipMemcpyDeviceToHost, st));
+    SNK_HIP_CHECK(hipStreamSynchronize(st));
+    bytes_up += (long long)count * (long long)sizeof(HoPlace);
+    bytes_down += (long long)count * (long long)sizeof(HoOut) + (long long)(a_img * 4 + a_pt + a_ps * 4) +
+                  (long long)count * max_rpc * (long long)sizeof(snk_ba_rpc);
+    readback_us += us_since(t0);
+    size_t a_obs = 0;
+    for (int b = 0; b < count; ++b)
+    {
+        const HoOut& r = L.hoout[(size_t)b];
+        PreProb& q     = pre[(size_t)b];
+        SNK_REQUIRE(r.nfc >= 0 && r.nfc <= problems[b].n_img && r.no >= 0 && r.no <= problems[b].n_obs, "the device stage of the hand-over answered a count out of range");
+        if (r.long_run) dev_long_run = true;
+        q.nfc = r.nfc, q.no = r.no, q.dup = 0;
+        q.k_over8 = want_big_items && r.k_over8 ? 1 : 0;  // (size_pass looks only then)
+        q.obs_at = a_obs;
+        L.hoplace[(size_t)b].obs_at = (int)a_obs;
+        a_obs += (size_t)r.no;
+        SNK_REQUIRE(a_obs < ((size_t)1 << 31), "scene list too large (observations)");
+    }
+    if (dev_long_run) return SNK_OK;  // the caller stages the batch
+    if (want_big_items)
+    {
+        big_items = true;
+        for (int b = 0; b < count; ++b) big_items = big_items && !pre[(size_t)b].k_over8;
+    }
+    const size_t n_o = std::max<size_t>(a_obs, 1);
+    SNK_TRY(h->d_oimg.reserve(n_o * sizeof(int)));
+    SNK_TRY(h->d_ouv.reserve(n_o * 2 * sizeof(double)));
+    SNK_TRY(h->d_odepth.reserve(n_o * sizeof(double)));
+    SNK_TRY(h->d_oweight.reserve(n_o * sizeof(double)));
+    SNK_TRY(h->d_oorig.reserve(n_o * sizeof(int)));
+    SNK_TRY(h->d_ocam.reserve(n_o * sizeof(int)));
+    SNK_TRY(h->d_optfree.reserve(n_o));
+    SNK_TRY(h->d_optidx.reserve(n_o * sizeof(int)));
+    t0 = clk::now();
+    SNK_HIP_CHECK(hipMemcpyAsync(h->d_hoplace.p, L.hoplace.data(), (size_t)count * sizeof(HoPlace), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ho_fill_kernel, dim3(count), dim3(HO_THREADS), ho_fill_carve(max_np), st, R, h->d_hoplace.as<const HoPlace>(), h->d_hoout.as<HoOut>(),
+                       (const int*)h->d_camidx.as<int>(), (const int*)h->d_ptstart.as<int>(), h->d_oimg.as<int>(), h->d_ocam.as<int>(), h->d_ouv.as<double2>(),
+                       h->d_odepth.as<double>(), h->d_oweight.as<double>(), h->d_oorig.as<int>());
+    SNK_LAUNCH_CHECK();
+    SNK_HIP_CHECK(hipStreamSynchronize(st));
+    dev_stage_us += us_since(t0);
+    // second readback: the sorted free-camera indices, dup
+    t0 = clk::now();
+    L.ocam.resize(a_obs);
+    if (a_obs) SNK_HIP_CHECK(hipMemcpyAsync(L.ocam.data(), h->d_ocam.p, a_obs * sizeof(int), hipMemcpyDeviceToHost, st));
+    SNK_HIP_CHECK(hipMemcpyAsync(L.hoout.data(), h->d_hoout.p, (size_t)count * sizeof(HoOut), hipMemcpyDeviceToHost, st));
+    SNK_HIP_CHECK(hipStreamSynchronize(st));
+    bytes_up += (long long)count * (long long)sizeof(HoPlace);
+    bytes_down += (long long)count * (long long)sizeof(HoOut) + (long long)a_obs * 4;
+    readback_us += us_since(t0);
+    for (int b = 0; b < count; ++b)
+    {
+        PreProb& q = pre[(size_t)b];
+        q.dup      = L.hoout[(size_t)b].dup ? 1 : 0;
+        unsigned char* ic = L.imgc.data() + q.img_at;
+        const int* cidx   = L.camidx.data() + q.img_at;
+        for (int i = 0; i < problems[b].n_img; ++i) ic[i] = cidx[i] < 0 ? 1 : 0;
+        shadow[b].img_const = ic;
+        shadow[b].pt_const  = L.ptc.data() + q.pt_at;
+        shadow[b].rpc       = problems[b].n_rpc > 0 ? L.rpcrows.data() + (size_t)b * (size_t)max_rpc : nullptr;
+    }
+    sec.lap(SEC_VALUES_SORT);
+    return SNK_OK;
+}
+
+// The caller's rows [n_q][cap] copied down as tight rows of the largest count each: the staged hand-over of batches the kernels do not
+// take, and SNK_BA_CHECK_LISTS.  Pinned, released with the object.
+struct RowsOnHost
+{
+    HostBuf pose, imgc, pt, ptc, oimg, opt, ouv, odepth, oweight, rpc;
+    std::vector<snk_ba_problem> problems;
+    long long bytes = 0;
+    ~RowsOnHost()
+    {
+        for (HostBuf* b : {&pose, &imgc, &pt, &ptc, &oimg, &opt, &ouv, &odepth, &oweight, &rpc}) b->release();
+    }
+    int fetch(const snk_scene_out& rows, const std::vector<snk_scene_result>& rec, const double K[4], double bf, hipStream_t st)
+    {
+        const size_t n = rec.size();
+        int m_img = 0, m_pt = 0, m_obs = 0, m_rpc = 0;
+        for (const snk_scene_result& r : rec)
+            m_img = std::max(m_img, r.n_img), m_pt = std::max(m_pt, r.n_pt), m_obs = std::max(m_obs, r.n_obs), m_rpc = std::max(m_rpc, r.n_rpc);
+        auto get = [&](HostBuf& dst, const void* src, size_t elem, int most, int cap) -> int
+        {
+            if (most == 0) return SNK_OK;
+            int rc = dst.reserve(n * (size_t)most * elem);
+            if (rc != SNK_OK) return rc;
+            SNK_HIP_CHECK(hipMemcpy2DAsync(dst.p, (size_t)most * elem, src, (size_t)cap * elem, (size_t)most * elem, n, hipMemcpyDeviceToHost, st));
+            bytes += (long long)(n * (size_t)most * elem);
+            return SNK_OK;
+        };
+        int rc;
+        if ((rc = get(pose, rows.pose, 56, m_img, rows.img_cap)) != SNK_OK) return rc;
+        if ((rc = get(imgc, rows.img_const, 1, m_img, rows.img_cap)) != SNK_OK) return rc;
+        if ((rc = get(pt, rows.pt, 24, m_pt, rows.pt_cap)) != SNK_OK) return rc;
+        if ((rc = get(ptc, rows.pt_const, 1, m_pt, rows.pt_cap)) != SNK_OK) return rc;
+        if ((rc = get(oimg, rows.obs_img, 4, m_obs, rows.obs_cap)) != SNK_OK) return rc;
+        if ((rc = get(opt, rows.obs_pt, 4, m_obs, rows.obs_cap)) != SNK_OK) return rc;
+        if ((rc = get(ouv, rows.obs_uv, 16, m_obs, rows.obs_cap)) != SNK_OK) return rc;
+        if ((rc = get(odepth, rows.obs_depth, 8, m_obs, rows.obs_cap)) != SNK_OK) return rc;
+        if ((rc = get(oweight, rows.obs_weight, 8, m_obs, rows.obs_cap)) != SNK_OK) return rc;
+        if ((rc = get(rpc, rows.rpc, sizeof(snk_ba_rpc), m_rpc, rows.win_cap)) != SNK_OK) return rc;
+        SNK_HIP_CHECK(hipStreamSynchronize(st));
+        problems.assign(n, snk_ba_problem{});
+        for (size_t b = 0; b < n; ++b)
+        {
+            snk_ba_problem& P = problems[b];
+            P.n_img = rec[b].n_img, P.n_pt = rec[b].n_pt, P.n_obs = rec[b].n_obs, P.n_rpc = rec[b].n_rpc;
+            // (a row without entries keeps a valid pointer where the batch has any: only its first `count` entries are ever read)
+            P.pose       = reinterpret_cast<double(*)[7]>(pose.as<char>() + b * (size_t)m_img * 56);
+            P.img_const  = imgc.as<uint8_t>() + b * (size_t)m_img;
+            P.pt         = reinterpret_cast<double(*)[3]>(pt.as<char>() + b * (size_t)m_pt * 24);
+            P.pt_const   = ptc.as<uint8_t>() + b * (size_t)m_pt;
+            P.obs_img    = oimg.as<int32_t>() + b * (size_t)m_obs;
+            P.obs_pt     = opt.as<int32_t>() + b * (size_t)m_obs;
+            P.obs_uv     = reinterpret_cast<const double(*)[2]>(ouv.as<char>() + b * (size_t)m_obs * 16);
+            P.obs_depth  = odepth.as<double>() + b * (size_t)m_obs;
+            P.obs_weight = oweight.as<double>() + b * (size_t)m_obs;
+            P.rpc        = P.n_rpc > 0 ? rpc.as<snk_ba_rpc>() + b * (size_t)m_rpc : nullptr;
+            for (int k = 0; k < 4; ++k) P.K[k] = K[k];
+            P.bf = bf;
+        }
+        return SNK_OK;
+    }
+};
+
+// SNK_BA_CHECK_LISTS=1 on device rows: the rows come down, the host builder fills L from them, and every array the device stage wrote
+// must equal the host's element for element.  L then holds what a host hand-over would, and `problems` the downloaded rows: the later
+// stages and check_lists run as they do there.
+int HandOver::dev_check(const snk_scene_out& rows, RowsOnHost& host_rows, const std::vector<snk_scene_result>& rec)
+{
+    hipStream_t st = h->stream;
+    const std::vector<PreProb> dev_pre = pre;
+    const bool dev_big = big_items;
+    auto down = [&](auto& v, const DevBuf& src, size_t n) -> int
+    {
+        v.resize(n);
+        if (n) SNK_HIP_CHECK(hipMemcpyAsync(v.data(), src.p, n * sizeof(v[0]), hipMemcpyDeviceToHost, st));
+        return SNK_OK;
+    };
+    size_t a_img = L.camidx.size(), a_pt = L.ptc.size(), a_ps = L.ptstart.size(), a_obs = L.ocam.size();
+    std::vector<double> g_pose, g_pt, g_uv, g_depth, g_weight;
+    std::vector<unsigned char> g_ptc;
+    std::vector<int> g_camidx, g_ptstart, g_oimg, g_ocam, g_oorig;
+    SNK_TRY(down(g_pose, h->d_pose, 7 * a_img));
+    SNK_TRY(down(g_pt, h->d_pt, 3 * a_pt));
+    SNK_TRY(down(g_ptc, h->d_ptc, a_pt));
+    SNK_TRY(down(g_camidx, h->d_camidx, a_img));
+    SNK_TRY(down(g_ptstart, h->d_ptstart, a_ps));
+    SNK_TRY(down(g_oimg, h->d_oimg, a_obs));
+    SNK_TRY(down(g_ocam, h->d_ocam, a_obs));
+    SNK_TRY(down(g_oorig, h->d_oorig, a_obs));
+    SNK_TRY(down(g_uv, h->d_ouv, 2 * a_obs));
+    SNK_TRY(down(g_depth, h->d_odepth, a_obs));
+    SNK_TRY(down(g_weight, h->d_oweight, a_obs));
+    SNK_TRY(host_rows.fetch(rows, rec, problems[0].K, problems[0].bf, st));  // (synchronises)
+    problems = host_rows.problems.data();
+    SNK_TRY(size_pass());
+    SNK_TRY(place_problems());
+    SNK_TRY(threaded(0, count, [&](int b) { fill_problem(b); }));
+    SNK_REQUIRE(big_items == dev_big, "SNK_BA_CHECK_LISTS: the device stage's big-items decision differs from the host builder's");
+    for (int b = 0; b < count; ++b)
+    {
+        const PreProb &d = dev_pre[(size_t)b], &w = pre[(size_t)b];
+        SNK_REQUIRE(d.nfc == w.nfc && d.no == w.no && d.k_over8 == w.k_over8 && d.dup == w.dup,
+                    "SNK_BA_CHECK_LISTS: the device stage's nfc / no / k_over8 / dup differ from the host builder's");
+        SNK_REQUIRE(d.img_at == w.img_at && d.pt_at == w.pt_at && d.ps_at == w.ps_at && d.obs_at == w.obs_at && d.orig_at == w.orig_at,
+                    "SNK_BA_CHECK_LISTS: the device stage's places differ from the host builder's");
+    }
+    auto same = [](const auto& g, const auto& l) { return g.size() == l.size() && (g.empty() || memcmp(g.data(), l.data(), g.size() * sizeof(g[0])) == 0); };
+    SNK_REQUIRE(same(g_pose, L.pose), "SNK_BA_CHECK_LISTS: device-written pose differs from the host builder's");
+    SNK_REQUIRE(same(g_pt, L.pt), "SNK_BA_CHECK_LISTS: device-written pt differs from the host builder's");
+    SNK_REQUIRE(same(g_ptc, L.ptc), "SNK_BA_CHECK_LISTS: device-written pt_const differs from the host builder's");
+    SNK_REQUIRE(same(g_camidx, L.camidx), "SNK_BA_CHECK_LISTS: device-written cam_idx differs from the host builder's");
+    SNK_REQUIRE(same(g_ptstart, L.ptstart), "SNK_BA_CHECK_LISTS: device-written pt_start differs from the host builder's");
+    SNK_REQUIRE(same(g_oimg, L.oimg), "SNK_BA_CHECK_LISTS: device-written o_img differs from the host builder's");
+    SNK_REQUIRE(same(g_ocam, L.ocam), "SNK_BA_CHECK_LISTS: device-written o_cam differs from the host builder's");
+    SNK_REQUIRE(same(g_oorig, L.oorig), "SNK_BA_CHECK_LISTS: device-written o_orig differs from the host builder's");
+    SNK_REQUIRE(same(g_uv, L.ouv2), "SNK_BA_CHECK_LISTS: device-written o_uv differs from the host builder's");
+    SNK_REQUIRE(same(g_depth, L.odepth), "SNK_BA_CHECK_LISTS: device-written o_depth differs from the host builder's");
+    SNK_REQUIRE(same(g_weight, L.oweight), "SNK_BA_CHECK_LISTS: device-written o_weight differs from the host builder's");
     return SNK_OK;
 }
 
@@ -718,16 +1138,19 @@ void HandOver::fill_problem(int b)
     // free cameras
     int* cidx = L.camidx.data() + q.img_at;
     int nfc   = 0;
-    for (int i = 0; i < P.n_img; ++i) cidx[i] = P.img_const[i] ? -1 : nfc++;
+    for (int i = 0; i < P.n_img; ++i)
+    {
+        cidx[i] = ho_cam_index(P.img_const[i] != 0, nfc);
+        nfc += P.img_const[i] ? 0 : 1;
+    }
     // valid observations, counting sort by point (stable: caller order inside a point)
     int* pstart = L.ptstart.data() + q.ps_at;
     for (int p = 0; p <= P.n_pt; ++p) pstart[p] = 0;
     std::vector<char> valid((size_t)P.n_obs, 0);
     for (int o = 0; o < P.n_obs; ++o)
     {
-        const int i = P.obs_img[o], p = P.obs_pt[o];
-        if (i < 0 || i >= P.n_img || p < 0 || p >= P.n_pt) continue;
-        if (P.img_const[i] && P.pt_const[p]) continue;
+        const int p = P.obs_pt[o];
+        if (!ho_obs_valid(P.obs_img[o], p, P.n_img, P.n_pt, P.img_const, P.pt_const)) continue;
         valid[(size_t)o] = 1;
         pstart[p + 1]++;
     }
@@ -738,7 +1161,7 @@ void HandOver::fill_problem(int b)
     unsigned char* q_free = L.optfree.data() + obs_at;
     double *q_uv = L.ouv2.data() + 2 * obs_at, *q_d = L.odepth.data() + obs_at, *q_w = L.oweight.data() + obs_at;
     // free cameras seen so far per point (device-built block entries: no camera twice on a point)
-    const int seen_words = nfc <= BE_MAX_CAMS ? (nfc + 63) >> 6 : 0;
+    const int seen_words = ho_dup_words(nfc);
     std::vector<unsigned long long> seen((size_t)P.n_pt * (size_t)seen_words, 0ull);
     std::vector<int> fill(pstart, pstart + P.n_pt);
     for (int o = 0; o < P.n_obs; ++o)
@@ -802,6 +1225,7 @@ int HandOver::send_chunk(int b0, int b1)
     {
         unsigned big = 0;
         for (int e = 0; e < tabE.n; ++e) big = std::max(big, tabE.bytes[e]);
+        for (int e = 0; e < tabE.n; ++e) bytes_up += tabE.bytes[e];
         const int gxe = (int)std::min(256u, std::max(16u, big >> 16));
         hipLaunchKernelGGL(copy_table_kernel, dim3(gxe, tabE.n), dim3(256), 0, h->stream, tabE);
         SNK_LAUNCH_CHECK();
@@ -1467,10 +1891,10 @@ int HandOver::upload_rest()
     SNK_TRY(upload(h->d_prob, L.probs, tab));
     if (!early_upload) { SNK_TRY(upload(h->d_pose, L.pose, tab)); }
     if (!dup_on_device) { SNK_TRY(upload(h->d_pose0, L.pose, tab)); }
-    else SNK_TRY(dup(h->d_pose0, h->d_pose, L.pose.size() * sizeof(double)));
+    else SNK_TRY(dup(h->d_pose0, h->d_pose, (size_t)tot.img_off * 7 * sizeof(double)));  // (by the totals: device rows leave L.pose empty)
     if (!early_upload) { SNK_TRY(upload(h->d_pt, L.pt, tab)); }
     if (!dup_on_device) { SNK_TRY(upload(h->d_pt0, L.pt, tab)); }
-    else SNK_TRY(dup(h->d_pt0, h->d_pt, L.pt.size() * sizeof(double)));
+    else SNK_TRY(dup(h->d_pt0, h->d_pt, (size_t)tot.pt_off * 3 * sizeof(double)));
     if (!early_upload)
     {
         SNK_TRY(upload(h->d_ptc, L.ptc, tab));
@@ -1515,7 +1939,7 @@ int HandOver::upload_rest()
     SNK_TRY(upload(h->d_camrpcitems, L.camrpcitems, tab));
     SNK_TRY(upload(h->d_blkrpc, L.blkrpc, tab));
     if (!dup_on_device) { SNK_TRY(upload(h->d_pt_new, L.pt, tab)); }  // points without observations stay put
-    else SNK_TRY(dup(h->d_pt_new, h->d_pt, L.pt.size() * sizeof(double)));
+    else SNK_TRY(dup(h->d_pt_new, h->d_pt, (size_t)tot.pt_off * 3 * sizeof(double)));
     t_up = std::chrono::steady_clock::now();
     return SNK_OK;
 }
@@ -1591,6 +2015,7 @@ int HandOver::zero_and_launch()
         // enough workgroups per array to keep the bus busy: one per 64 KB of the largest list, 16 .. 256
         unsigned big = 0;
         for (int e = 0; e < tab.n; ++e) big = std::max(big, tab.bytes[e]);
+        for (int e = 0; e < tab.n; ++e) bytes_up += tab.src[e] ? tab.bytes[e] : 0;  // (tab2 is device to device)
         // (more workgroups per array do not shorten it: 16.3 / 18.3 / 17.1 / 15.2 us with one per 64 / 16 / 4 / 1 KB, r03ag)
         const int gx = (int)std::min(256u, std::max(16u, big >> 16));
         hipLaunchKernelGGL(copy_table_kernel, dim3(gx, tab.n), dim3(256), 0, st, tab);
@@ -1791,6 +2216,30 @@ int HandOver::check_lists()
     return SNK_OK;
 }
 
+// the stages behind the fill pass (host arrays) or the device stage (device rows)
+int HandOver::later_stages()
+{
+    SNK_TRY(build_problem_lists());
+    SNK_TRY(merge_decide());
+    SNK_TRY(merge_copy());
+    SNK_TRY(publish_totals());
+    SNK_TRY(plan_block_entries());
+    SNK_TRY(upload_rest());
+    SNK_TRY(reserve_work());
+    SNK_TRY(zero_and_launch());
+    SNK_TRY(check_lists());
+    return report();
+}
+
+int HandOver::host_hand_over()
+{
+    SNK_TRY(reserve_lists());
+    SNK_TRY(size_pass());
+    SNK_TRY(place_problems());
+    SNK_TRY(fill_and_send());
+    return later_stages();
+}
+
 // SNK_BA_PROFILE_CREATE=1: host-side cost of the hand-over, in microseconds
 int HandOver::report()
 {
@@ -1806,6 +2255,8 @@ int HandOver::report()
             sec.us(SEC_VALUES_SORT), sec.us(SEC_OBS_ARRAYS), sec.us(SEC_WAVE_ITEMS), sec.us(SEC_CAMERA_LISTS), sec.us(SEC_BLOCK_ENTRIES),
             sec.us(SEC_BLOCK_LISTS) + sec.us(SEC_GROUPING) + sec.us(SEC_WORK_ITEMS), sec.us(SEC_GROUPING), sec.us(SEC_WORK_ITEMS), sec.us(SEC_BLOCK_LISTS),
             sec.us(SEC_CONSTRAINTS), sec.us(SEC_REST));
+    fprintf(stderr, "[snk_ba_set_problems] input %s: device stage %lld us, readback %lld us, over the bus %lld bytes up, %lld bytes down\n",
+            dev ? "device rows" : "host arrays", dev_stage_us, readback_us, bytes_up, bytes_down);
     return SNK_OK;
 }
 #undef SNK_TRY
@@ -1851,20 +2302,82 @@ int snk_ba_set_problems(snk_ba* h, const snk_ba_problem* problems, int count)
     SNK_HIP_CHECK(hipSetDevice(h->device));
     SNK_HIP_CHECK(hipStreamSynchronize(h->stream));
     h->drop_graphs();
-    if ((rc = ho.reserve_lists()) != SNK_OK) return rc;
-    if ((rc = ho.size_pass()) != SNK_OK) return rc;
-    if ((rc = ho.place_problems()) != SNK_OK) return rc;
-    if ((rc = ho.fill_and_send()) != SNK_OK) return rc;
-    if ((rc = ho.build_problem_lists()) != SNK_OK) return rc;
-    if ((rc = ho.merge_decide()) != SNK_OK) return rc;
-    if ((rc = ho.merge_copy()) != SNK_OK) return rc;
-    if ((rc = ho.publish_totals()) != SNK_OK) return rc;
-    if ((rc = ho.plan_block_entries()) != SNK_OK) return rc;
-    if ((rc = ho.upload_rest()) != SNK_OK) return rc;
-    if ((rc = ho.reserve_work()) != SNK_OK) return rc;
-    if ((rc = ho.zero_and_launch()) != SNK_OK) return rc;
-    if ((rc = ho.check_lists()) != SNK_OK) return rc;
-    if ((rc = ho.report()) != SNK_OK) return rc;
+    if ((rc = ho.host_hand_over()) != SNK_OK) return rc;
+    no_set_on_failure.ok = true;
+    return SNK_OK;
+}
+
+int snk_ba_set_problems_dev(snk_ba* h, int n_q, const snk_scene_out* out_dev, const double K[4], double bf)
+{
+    SNK_REQUIRE(h != nullptr, "ba is NULL");
+    h->count       = 0;  // as snk_ba_set_problems: whatever happens below, a failure leaves no problem set
+    h->state_fresh = false;
+    struct NoSetOnFailure
+    {
+        snk_ba* h;
+        bool ok = false;
+        ~NoSetOnFailure()
+        {
+            if (!ok) h->count = 0, h->state_fresh = false;
+        }
+    } no_set_on_failure{h};
+    // everything is checked before a kernel reads a row
+    SNK_REQUIRE(out_dev != nullptr && K != nullptr, "out_dev / K is NULL");
+    SNK_REQUIRE(n_q >= 1 && n_q <= 65535, "count must be 1..65535");
+    const bool imp = h->explicit_schur == 0;
+    SNK_REQUIRE(!imp || n_q == 1, "the implicit Schur form takes one problem (snk_ba_set_explicit_schur)");
+    const snk_scene_out& rows = *out_dev;
+    SNK_REQUIRE(rows.win_cap >= 1 && rows.win_cap <= SNK_SCENE_MAX_WINDOW && rows.pt_cap >= 1 && rows.pt_cap <= SNK_LMAP_MAX_PTS && rows.img_cap >= 1 &&
+                    rows.img_cap <= SNK_SCENE_MAX_IMG && rows.obs_cap >= 1 && rows.obs_cap <= SNK_SCENE_MAX_OBS,
+                "a cap of the rows is outside its range");
+    SNK_REQUIRE(rows.result && rows.pose && rows.img_const && rows.pt && rows.pt_const && rows.obs_img && rows.obs_pt && rows.obs_uv && rows.obs_depth &&
+                    rows.obs_weight,
+                "NULL row arrays");
+    SNK_HIP_CHECK(hipSetDevice(h->device));
+    SNK_HIP_CHECK(hipStreamSynchronize(h->stream));  // the rows are complete on this stream (or the caller has synchronised their producer)
+    std::vector<snk_scene_result> rec((size_t)n_q);
+    int rc;
+    if ((rc = copy_sync(rec.data(), rows.result, (size_t)n_q * sizeof(snk_scene_result), hipMemcpyDeviceToHost, h->stream)) != SNK_OK) return rc;
+    bool kernels_take = true;
+    for (snk_scene_result& r : rec)
+    {
+        SNK_REQUIRE(r.n_img >= 0 && r.n_pt >= 0 && r.n_obs >= 0 && r.n_rpc >= 0, "negative problem size");
+        SNK_REQUIRE(r.n_img <= rows.img_cap && r.n_pt <= rows.pt_cap && r.n_obs <= rows.obs_cap && r.n_rpc <= rows.win_cap, "a record's count exceeds the row's cap");
+        if (r.status != SNK_SCENE_OK) r.n_img = r.n_pt = r.n_obs = r.n_rpc = 0;  // an empty problem in its slot; the row is not read
+        if (rows.rpc == nullptr) r.n_rpc = 0;
+        kernels_take = kernels_take && ho_kernels_take(r.n_pt);
+    }
+    h->implicit = imp;
+    h->drop_graphs();
+    const long long rec_bytes = (long long)n_q * (long long)sizeof(snk_scene_result);
+    RowsOnHost host_rows;
+    if (kernels_take)
+    {
+        std::vector<snk_ba_problem> shadow((size_t)n_q, snk_ba_problem{});
+        for (int b = 0; b < n_q; ++b)
+        {
+            snk_ba_problem& P = shadow[(size_t)b];
+            P.n_img = rec[(size_t)b].n_img, P.n_pt = rec[(size_t)b].n_pt, P.n_obs = rec[(size_t)b].n_obs, P.n_rpc = rec[(size_t)b].n_rpc;
+            for (int k = 0; k < 4; ++k) P.K[k] = K[k];
+            P.bf = bf;
+        }
+        HandOver ho(h, shadow.data(), n_q, true);
+        ho.bytes_down = rec_bytes;
+        if ((rc = ho.reserve_lists()) != SNK_OK) return rc;
+        if ((rc = ho.dev_stage(rows, shadow.data())) != SNK_OK) return rc;
+        if (!ho.dev_long_run)
+        {
+            if (ho.sw.check_lists && (rc = ho.dev_check(rows, host_rows, rec)) != SNK_OK) return rc;
+            if ((rc = ho.later_stages()) != SNK_OK) return rc;
+            no_set_on_failure.ok = true;
+            return SNK_OK;
+        }
+    }
+    // a batch the kernels do not take (handover_core.hpp): the rows come down and go through the host builder
+    if ((rc = host_rows.fetch(rows, rec, K, bf, h->stream)) != SNK_OK) return rc;
+    HandOver ho(h, host_rows.problems.data(), n_q);
+    ho.bytes_down = rec_bytes + host_rows.bytes;
+    if ((rc = ho.host_hand_over()) != SNK_OK) return rc;
     no_set_on_failure.ok = true;
     return SNK_OK;
 }

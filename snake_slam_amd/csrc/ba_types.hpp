@@ -260,6 +260,12 @@ struct BaLists
     pvec<RpcMeta> rpcmeta;
     pvec<int4> blkent;
     pvec<State> states;
+    // snk_ba_set_problems_dev: the per-problem records to and from ho_count_kernel / ho_fill_kernel, the constant-image flags and the
+    // constraint rows read back for the host stages (sized and written by the call itself: clear() leaves them alone)
+    pvec<HoPlace> hoplace;
+    pvec<HoOut> hoout;
+    pvec<unsigned char> imgc;
+    pvec<snk_ba_rpc> rpcrows;
     void clear()
     {
         probs.clear(), pose.clear(), pt.clear(), ouv2.clear(), odepth.clear(), oweight.clear(), ptc.clear(), optfree.clear();
@@ -350,6 +356,7 @@ struct Handle : HandleBase
     HostBuf h_stage;  // pinned staging of the small per-call transfers (outlier masks)
     DevBuf d_becnt;   // per (camera, 64-item chunk, camera) counters of the device-built block entries
     DevBuf d_probcond;  // the problem table of a conditional extra iteration (select_marked)
+    DevBuf d_hoplace, d_hoout;  // HoPlace / HoOut per problem (snk_ba_set_problems_dev)
     DevBuf d_campart, d_ccstart, d_ccitems;  // per (work item, free camera) sums of schur_fused<3, true> and the per-camera lists of them
     bool state_fresh = false;                // the device state is the uploaded initial one (no solve since the hand-over)
     bool blk_built = true;                   // the camera-pair block entries of the current problem set exist on the device (see ba_sets_will_run)

@@ -7,6 +7,7 @@
 #pragma once
 #include <cstddef>
 
+#include "handover_core.hpp"  // the BA hand-over from device rows: which problems its kernels take, their carves (HO_*, ho_*)
 #include "orb_layout.hpp"
 
 #ifndef SNK_POSE_RED_STEPS  // DPP steps of pose_kernel's 27 sums before they meet in LDS: 4 = rows of 16 lanes, 2 = quads (pose.hip)
