@@ -1666,6 +1666,168 @@ SNK_API int snk_match_loop_bow_batch_dev(snk_matcher* m, const snk_frames_dev* f
                                          int32_t* pairs_dev, int32_t* n_pairs_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Keyframe culling (snk-simp v1)
+ * ------------------------------------------------------------------------------------------
+ * Simplification::KeyFrameCullingGraph and Redundancy (Snake/Optimizer/Simplification.cpp:148-358, :75-146), Keyframe::MatchCount and
+ * ComputeDepthRange (Snake/Map/Keyframe.cpp:68-77, :175-206) for many keyframes per call, in two stages: per-keyframe statistics from
+ * the map tables, then the decision from the connection lists.  saiga's WeightedUndirectedGraph is not part of the reference checkout:
+ * the graph rules (edge weight, spanning tree, weakest link) are [DEFINED] in DESIGN.md section 3l and restated in tests/simp_numpy.py.
+ * Every query of a call sees the same tables.  EraseKeyframe (:55), the re-queue of the three best covisible keyframes (:50-63: the last
+ * three entries of q's list), UpdateConnections of :207 and the choice of how many verdicts of one call to apply stay with the caller. */
+
+#define SNK_SIMP_MAX_NODES 256  /* q and its connections of weight >= min_matches_in_graph; node_cap at most */
+#define SNK_SIMP_MAX_FEAT 16384 /* feat_cap at most: a float per feature of the query in LDS */
+
+#define SNK_SIMP_OK 0
+#define SNK_SIMP_SKIPPED 1        /* the query keyframe is bad (Simplification.cpp:93, :217) */
+#define SNK_SIMP_FEAT_OVERFLOW 2  /* the query has more than feat_cap features */
+#define SNK_SIMP_NODES_OVERFLOW 3 /* more than node_cap nodes: no decision */
+#define SNK_SIMP_BAD_INDEX 4      /* device forms: an id, a start or a feature index outside its range */
+
+#define SNK_SIMP_NONE 0 /* no decision (status != SNK_SIMP_OK) */
+#define SNK_SIMP_FACTOR 1
+#define SNK_SIMP_NO_CONN 2
+#define SNK_SIMP_ANGLE 3
+#define SNK_SIMP_MATCHES 4
+#define SNK_SIMP_REDUNDANCY 5
+#define SNK_SIMP_LINK 6 /* reasons 1 .. 6 cull */
+#define SNK_SIMP_KEEP_IMU_WEIGHTS 7
+#define SNK_SIMP_KEEP_TIME_GAP 8
+#define SNK_SIMP_KEEP_BRANCH 9
+#define SNK_SIMP_KEEP_DISCONNECTED 10
+#define SNK_SIMP_KEEP_LINK 11
+
+/* The map as tables: the layouts and names of snk_covis_map / snk_scene_map.  Host pointers for snk_simp_stats, device pointers for the
+ * _batch_dev form. */
+typedef struct snk_simp_map
+{
+    int32_t n_kf, n_points, n_obs, n_feat;
+    const uint8_t* kf_bad;      /* [n_kf] */
+    const double* kf_pose;      /* [n_kf][7] world -> camera: qx qy qz qw tx ty tz */
+    const int32_t* feat_start;  /* [n_kf + 1], feat_start[0] = 0 */
+    const int32_t* feat_point;  /* [n_feat] point ids, -1: none */
+    const float* feat_depth;    /* [n_feat] frame->depth[i] */
+    const int32_t* feat_octave; /* [n_feat] undistorted_keypoints[i].octave */
+    const int32_t* obs_start;   /* [n_points + 1], obs_start[0] = 0 */
+    const int32_t (*obs)[2];    /* [n_obs] GetObservationList() in list order as (kf, feature index inside the keyframe) */
+    const uint8_t* pt_flags;    /* [n_points] SNK_COVIS_PT_BAD; the other bits are not read */
+    const double* pt_pos;       /* [n_points][3] */
+} snk_simp_map;
+
+typedef struct snk_simp_stats_params
+{
+    int32_t min_obs;  /* MatchCount's argument; Simplification.cpp:282 passes 3 */
+    int32_t stereo;   /* settings.inputType != Mono (:107): features deeper than th_depth do not enter the redundancy */
+    float th_depth;   /* :109; equality counts */
+    int32_t feat_cap; /* features of one query at most, 1 .. SNK_SIMP_MAX_FEAT */
+} snk_simp_stats_params;
+
+/* One query of stage 1.  status != SNK_SIMP_OK: median_depth = -1, the counts and the redundancy 0. */
+typedef struct snk_simp_stats_result
+{
+    float median_depth;  /* ComputeDepthRange(true); -1 (the member's initial value, Keyframe.h:125) where n_depth == 0 */
+    int32_t n_depth;     /* features with a point, bad points included (Keyframe.cpp:189) */
+    int32_t match_count; /* MatchCount(min_obs) */
+    int32_t n_mps;       /* nMPs of Redundancy */
+    int32_t n_redundant; /* nRedundantObservations */
+    float redundancy;    /* (float)n_redundant / (float)n_mps; 0 / 0 is NaN and compares false, as in the reference */
+    int32_t status;
+} snk_simp_stats_result;
+
+/* Stage 1 for the keyframes q[0 .. n_q).  ComputeDepthRange(always = true) — Snake/Map/Keyframe.cpp:183-205: for every feature of q with
+ * a point (bad ones too) z = (float)(row 3 of R(q) . p + t_z) in double, in the operation order simp_core.hpp states; median_depth is
+ * the element (n_depth - 1) / 2 of the ascending order, [DEFINED] the total order of the IEEE bit patterns (-0 before +0; the inputs are
+ * finite).  MatchCount(min_obs) — Keyframe.cpp:68-77: the features whose point is not bad and has at least min_obs observations,
+ * [DEFINED] GetNumObservations() = obs_start[p + 1] - obs_start[p].  Redundancy — Simplification.cpp:98-145: over the features with a
+ * point that is not bad (stereo: feat_depth <= th_depth only) n_mps += 1; a list longer than 3 is walked in order, entries of q itself
+ * skipped, those with feat_octave[feat_start[k] + f] <= the feature's octave + 1 counted; 3 or more: n_redundant += 1.  Bad observer
+ * keyframes count.  q bad (:93): SNK_SIMP_SKIPPED.  The caller leaves its cached median alone where n_depth == 0 (Keyframe.cpp:199-202).
+ * Everything is checked before anything is launched: a NULL array with a non-zero count, starts that do not begin at 0 or decrease, a
+ * query, a point id, an observation's keyframe or feature index outside its range, n_kf > SNK_COVIS_MAX_KF, feat_cap outside
+ * [1, SNK_SIMP_MAX_FEAT]: SNK_ERR_INVALID_ARG.  n_q == 0 is valid.  The results do not depend on the kernel form
+ * (SNK_SIMP_LONG_MIN=<n> moves the length from which a wavefront walks a list, read once). */
+SNK_API int snk_simp_stats(snk_matcher* m, const snk_simp_map* map, const snk_simp_stats_params* params, int n_q, const int32_t* q,
+                           snk_simp_stats_result* out);
+
+/* The same (Keyframe.cpp:68-77, :183-205, Simplification.cpp:98-145) with every table, q_dev and out_dev on the device.  Asynchronous on
+ * the handle's stream, no host round trip.  The scalars are checked on the host; the kernel checks what the host cannot see, as
+ * snk_covis_update_batch_dev does -- a query outside [0, n_kf), a feature range outside [0, n_feat] or decreasing, a point id outside
+ * [-1, n_points), an obs_start outside [0, n_obs] or decreasing, an observation's keyframe outside [0, n_kf) -- and an observation's
+ * feature index outside its keyframe's range: that query has status = SNK_SIMP_BAD_INDEX, nothing outside the ranges is read, the
+ * other queries are unaffected.  Only the lists a query walks are checked. */
+SNK_API int snk_simp_stats_batch_dev(snk_matcher* m, const snk_simp_map* map_dev, const snk_simp_stats_params* params, int n_q,
+                                     const int32_t* q_dev, snk_simp_stats_result* out_dev);
+
+/* The keyframe side of the decision.  Host pointers for snk_simp_decide, device pointers for the _batch_dev form.  kf_prev, kf_next and
+ * kf_time are all NULL or all present. */
+typedef struct snk_simp_graph
+{
+    int32_t n_kf, n_list;
+    const uint8_t* kf_bad;                  /* [n_kf] */
+    const double* kf_pose;                  /* [n_kf][7] */
+    const float* kf_cull_factor;            /* [n_kf] kf->cull_factor */
+    const double* kf_median_depth;          /* [n_kf] the cached member: the caller fills the entries <= 0 from stage 1 before the call (the
+                                               lazy rule of Keyframe.cpp:177); read as it is, -1 included */
+    const int32_t* kf_prev;                 /* [n_kf] previousKF as a slot, -1: none */
+    const int32_t* kf_next;                 /* [n_kf] nextKF */
+    const double* kf_time;                  /* [n_kf] frame->timeStamp */
+    const int32_t* conn_start;              /* [n_kf + 1] */
+    const struct snk_covis_conn* conn_list; /* [n_list] every keyframe's connections ascending by (weight, kf): the arguments of
+                                               snk_scene_window / snk_lmap_select, as snk_covis_update leaves them */
+} snk_simp_graph;
+
+typedef struct snk_simp_params
+{
+    int32_t min_matches_in_graph; /* simpl_min_matches_in_graph: 20 */
+    float border_angle;           /* simpl_border_angle: 1.0 */
+    float border_redundancy;      /* simpl_border_redundancy: 0.8 */
+    int32_t border_matches;       /* simpl_border_matches: 80 */
+    int32_t th_map;               /* settings.th_map: 140 */
+    int32_t with_imu;             /* WITH_IMU (Simplification.cpp:158) */
+    double gyro_weight;           /* current_gyro_weight */
+    double acc_weight;            /* current_acc_weight */
+    float max_time_between_kf;    /* max_time_between_kf_map: 0.5 */
+} snk_simp_params;
+
+/* One query of stage 2.  status != SNK_SIMP_OK: reason = SNK_SIMP_NONE, everything else 0. */
+typedef struct snk_simp_verdict
+{
+    int32_t reason;       /* SNK_SIMP_FACTOR .. SNK_SIMP_KEEP_LINK */
+    int32_t cull;         /* 1 exactly for FACTOR, NO_CONN, ANGLE, MATCHES, REDUNDANCY, LINK */
+    double value;         /* the third element of the reference's tuple: the angle, the match count, the redundancy, the weakest link; else 0 */
+    int32_t n_nodes;      /* nodes of the first graph, q included; 0 where a verdict fell before the graph */
+    int32_t n_root_edges; /* tree edges at q */
+    int32_t weakest_link; /* of the second tree, where it is connected; else 0 */
+    int32_t status;
+} snk_simp_verdict;
+
+/* Stage 2 for the keyframes q[0 .. n_q) — Simplification::KeyFrameCullingGraph, Simplification.cpp:148-358 — in the reference's order.
+ * stats [n_q] are the same queries' records of stage 1 with min_obs = 3; a status there other than OK is passed through.
+ * q bad (:217): SNK_SIMP_SKIPPED.  cull_factor > 3 (:150): FACTOR.  with_imu (:158-179): a weight == 0 keeps (KEEP_IMU_WEIGHTS); with the
+ * time tables, prev >= 0, next >= 0 and time[next] - time[prev] > max_time_between_kf keeps (KEEP_TIME_GAP).  Nodes (:222-239): id 0 is
+ * q, then q's connections with weight >= min_matches_in_graph in list order, bad targets kept; a keyframe listed twice answers to its
+ * last id, as the reference's id_map does; more than node_cap nodes: SNK_SIMP_NODES_OVERFLOW.  Edges (:242-246): q's filtered list, then
+ * every node's full list, each entry whose target is a node; [DEFINED] undirected, a pair listed more than once has the maximum of its
+ * weights, self edges are dropped.  BuildMST [DEFINED]: the MAXIMUM spanning tree by Prim from id 0 (:351 accepts culling where the
+ * weakest link is large); an outside node keeps its best (weight, parent), the smaller parent among equal weights; the node with the
+ * largest weight joins, the smallest id among equals; unreachable nodes stay outside.  No tree edge at id 0 (:256): NO_CONN.  One, to o
+ * (:287-310): angle = atan2(0.5 |C_q - C_o|, (median[q] + median[o]) * 0.5) * 2 * (180 / pi); angle < border_angle * cull_factor: ANGLE;
+ * else match_count < border_matches * cull_factor: MATCHES; else redundancy > border_redundancy: REDUNDANCY; else KEEP_BRANCH.  Two or
+ * more (:316-357): the maximum tree of the graph on q's tree neighbours alone; a neighbour left outside (:342): KEEP_DISCONNECTED; its
+ * smallest edge * cull_factor > th_map: LINK; else KEEP_LINK.  node_cap (1 .. SNK_SIMP_MAX_NODES) sizes the kernel's LDS: small
+ * graphs pack many workgroups per compute unit.  Everything is checked before anything is launched: a NULL array with a non-zero count,
+ * conn_start not beginning at 0 or decreasing, a query, a connection, kf_prev or kf_next outside its range, n_kf > SNK_COVIS_MAX_KF,
+ * node_cap outside its range, time tables only partly present: SNK_ERR_INVALID_ARG.  n_q == 0 is valid. */
+SNK_API int snk_simp_decide(snk_matcher* m, const snk_simp_graph* graph, const snk_simp_params* params, int node_cap, int n_q,
+                            const int32_t* q, const snk_simp_stats_result* stats, snk_simp_verdict* out);
+
+/* The same (Simplification.cpp:148-358) with every table, q_dev, stats_dev and out_dev on the device.  Asynchronous, no host round trip.
+ * The kernel checks: a query outside [0, n_kf), kf_prev / kf_next outside [-1, n_kf), a conn_start range outside [0, n_list] or
+ * decreasing, a connection's keyframe outside [0, n_kf) give that query SNK_SIMP_BAD_INDEX; only the ranges a query reaches are checked. */
+SNK_API int snk_simp_decide_batch_dev(snk_matcher* m, const snk_simp_graph* graph_dev, const snk_simp_params* params, int node_cap, int n_q,
+                                      const int32_t* q_dev, const snk_simp_stats_result* stats_dev, snk_simp_verdict* out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU result gather (BASELINE config 5: one sequence per GPU)
  * ------------------------------------------------------------------------------------------
  * The path shards over independent units -- one Snake-SLAM process and one sequence per GPU -- and exchanges nothing while it

@@ -90,6 +90,10 @@ SIGNATURES = {
     "snk_scene_window_batch_dev": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
     "snk_scene_gather": (i32, [vp, i32, vp, vp, vp, vp, vp]),
     "snk_scene_gather_batch_dev": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+    "snk_simp_stats": (i32, [vp, vp, vp, i32, vp, vp]),
+    "snk_simp_stats_batch_dev": (i32, [vp, vp, vp, i32, vp, vp]),
+    "snk_simp_decide": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "snk_simp_decide_batch_dev": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "snk_p3p_ransac": (i32, [vp, vp, vp, i32]),
     "snk_p3p_debug_hypotheses": (i32, [vp, vp, vp, vp, vp, vp, vp]),
     "snk_p3p_ransac_frame_batch_dev": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp]),

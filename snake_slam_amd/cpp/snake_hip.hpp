@@ -1208,6 +1208,159 @@ class LocalSceneBuilder
     int win_cap_;
 };
 
+// Simplification::KeyFrameCullingGraph and Redundancy, semantics "snk-simp v1" (reference Snake/Optimizer/Simplification.cpp:148-358,
+// :75-146; Keyframe::MatchCount and ComputeDepthRange, Snake/Map/Keyframe.cpp:68-77, :175-206) for a list of keyframes per call, with
+// the reference's method names.  Map holds the tables; Map::FromObjects flattens reference-shaped Keyframe / MapPoint objects into them.
+// KeyFrameCullingGraph does what the reference does around the decision: the statistics of the queries and of every live keyframe whose
+// cached median is <= 0 (Keyframe.cpp:177), the fill of that cache in the Map, then the verdicts.  UpdateConnections of :207 (the
+// CovisibilityGraph above), EraseKeyframe and the re-queue of the three best covisible keyframes (:50-63) stay with the caller.
+class KeyframeCuller
+{
+   public:
+    struct Map  // the tables of snk_simp_map and snk_simp_graph; times: kf_prev / kf_next / kf_time all or none
+    {
+        std::vector<uint8_t> kf_bad;
+        std::vector<double> kf_pose;  // [n_kf][7]
+        std::vector<float> kf_cull_factor;
+        std::vector<double> kf_median_depth;  // the cache: KeyFrameCullingGraph fills the entries <= 0
+        bool times = false;
+        std::vector<int32_t> kf_prev, kf_next;
+        std::vector<double> kf_time;
+        std::vector<int32_t> conn_start{0};
+        std::vector<snk_covis_conn> conn_list;
+        std::vector<int32_t> feat_start{0}, feat_point, feat_octave;
+        std::vector<float> feat_depth;
+        std::vector<int32_t> obs_start{0}, obs;  // obs [n_obs][2]
+        std::vector<uint8_t> pt_flags;
+        std::vector<double> pt_pos;  // [n_points][3]
+        snk_simp_map map() const
+        {
+            snk_simp_map m{};
+            m.n_kf = (int32_t)kf_bad.size(), m.n_points = (int32_t)pt_flags.size(), m.n_obs = (int32_t)obs.size() / 2, m.n_feat = (int32_t)feat_point.size();
+            m.kf_bad = kf_bad.data(), m.kf_pose = kf_pose.data(), m.feat_start = feat_start.data(), m.feat_point = feat_point.data();
+            m.feat_depth = feat_depth.data(), m.feat_octave = feat_octave.data(), m.obs_start = obs_start.data();
+            m.obs = reinterpret_cast<const int32_t(*)[2]>(obs.data()), m.pt_flags = pt_flags.data(), m.pt_pos = pt_pos.data();
+            return m;
+        }
+        snk_simp_graph graph() const
+        {
+            snk_simp_graph g{};
+            g.n_kf = (int32_t)kf_bad.size(), g.n_list = (int32_t)conn_list.size();
+            g.kf_bad = kf_bad.data(), g.kf_pose = kf_pose.data(), g.kf_cull_factor = kf_cull_factor.data(), g.kf_median_depth = kf_median_depth.data();
+            if (times) g.kf_prev = kf_prev.data(), g.kf_next = kf_next.data(), g.kf_time = kf_time.data();
+            g.conn_start = conn_start.data(), g.conn_list = conn_list.data();
+            return g;
+        }
+        // From objects shaped like the reference's.  KF: bool bad; double pose[7]; float cull_factor; double median_depth;
+        // std::vector<MP*> observations (nullptr: none); std::vector<float> depth; std::vector<int> octave;
+        // std::vector<std::pair<int, KF*>> connections (ascending, as GetConnections returns them); KF *previousKF, *nextKF;
+        // double timeStamp; int slot.  MP: bool bad; double position[3]; std::vector<std::pair<KF*, int>> observations (GetObservationList);
+        // int slot.  The slots are the positions in the two vectors.
+        template <class KF, class MP>
+        static Map FromObjects(const std::vector<KF*>& keyframes, const std::vector<MP*>& points, bool with_times)
+        {
+            Map m;
+            m.times = with_times;
+            for (const KF* kf : keyframes)
+            {
+                m.kf_bad.push_back(kf->bad ? 1 : 0);
+                m.kf_pose.insert(m.kf_pose.end(), kf->pose, kf->pose + 7);
+                m.kf_cull_factor.push_back(kf->cull_factor);
+                m.kf_median_depth.push_back(kf->median_depth);
+                if (with_times)
+                {
+                    m.kf_prev.push_back(kf->previousKF ? kf->previousKF->slot : -1);
+                    m.kf_next.push_back(kf->nextKF ? kf->nextKF->slot : -1);
+                    m.kf_time.push_back(kf->timeStamp);
+                }
+                for (const auto& c : kf->connections) m.conn_list.push_back(snk_covis_conn{c.first, c.second->slot});
+                m.conn_start.push_back((int32_t)m.conn_list.size());
+                for (size_t i = 0; i < kf->observations.size(); ++i)
+                {
+                    m.feat_point.push_back(kf->observations[i] ? kf->observations[i]->slot : -1);
+                    m.feat_depth.push_back(kf->depth[i]);
+                    m.feat_octave.push_back(kf->octave[i]);
+                }
+                m.feat_start.push_back((int32_t)m.feat_point.size());
+            }
+            for (const MP* mp : points)
+            {
+                m.pt_flags.push_back(mp->bad ? SNK_COVIS_PT_BAD : 0);
+                m.pt_pos.insert(m.pt_pos.end(), mp->position, mp->position + 3);
+                for (const auto& o : mp->observations) m.obs.push_back(o.first->slot), m.obs.push_back(o.second);
+                m.obs_start.push_back((int32_t)m.obs.size() / 2);
+            }
+            return m;
+        }
+    };
+
+    explicit KeyframeCuller(const snk_simp_params& params, const snk_simp_stats_params& stats_params, int node_cap = SNK_SIMP_MAX_NODES, int device = 0)
+        : par_(params), spar_(stats_params), node_cap_(node_cap)
+    {
+        check(snk_matcher_create(device, nullptr, &h_), "snk_matcher_create");
+    }
+    ~KeyframeCuller() { snk_matcher_destroy(h_); }
+    KeyframeCuller(const KeyframeCuller&)            = delete;
+    KeyframeCuller& operator=(const KeyframeCuller&) = delete;
+
+    // stage 1 for the keyframes q (min_obs: MatchCount's argument, 3 at Simplification.cpp:282)
+    std::vector<snk_simp_stats_result> Stats(const Map& map, const std::vector<int32_t>& q, int min_obs = 3)
+    {
+        std::vector<snk_simp_stats_result> out(q.size());
+        const snk_simp_map m      = map.map();
+        snk_simp_stats_params par = spar_;
+        par.min_obs               = min_obs;
+        check(snk_simp_stats(h_, &m, &par, (int)q.size(), q.data(), out.data()), "snk_simp_stats");
+        return out;
+    }
+
+    // Simplification::Redundancy (:75-146) of every q; a bad keyframe answers 0 as the reference's `return false` does
+    std::vector<float> Redundancy(const Map& map, const std::vector<int32_t>& q)
+    {
+        std::vector<float> out;
+        for (const snk_simp_stats_result& s : Stats(map, q)) out.push_back(s.redundancy);
+        return out;
+    }
+
+    // Simplification::KeyFrameCullingGraph (:148-358) of every q: {cull, reason, value} and the graph's counts.  Fills map.kf_median_depth.
+    std::vector<snk_simp_verdict> KeyFrameCullingGraph(Map& map, const std::vector<int32_t>& q, std::vector<snk_simp_stats_result>* stats_out = nullptr)
+    {
+        std::vector<int32_t> todo = q;
+        for (size_t k = 0; k < map.kf_bad.size(); ++k)
+            if (map.kf_median_depth[k] <= 0 && !map.kf_bad[k]) todo.push_back((int32_t)k);
+        const std::vector<snk_simp_stats_result> st = Stats(map, todo);
+        for (size_t i = 0; i < todo.size(); ++i)  // Keyframe.cpp:177, :199-202
+        {
+            const size_t k = (size_t)todo[i];
+            if (map.kf_median_depth[k] <= 0 && !map.kf_bad[k] && st[i].status == SNK_SIMP_OK && st[i].n_depth > 0) map.kf_median_depth[k] = (double)st[i].median_depth;
+        }
+        std::vector<snk_simp_verdict> out(q.size());
+        const snk_simp_graph g = map.graph();
+        check(snk_simp_decide(h_, &g, &par_, node_cap_, (int)q.size(), q.data(), st.data(), out.data()), "snk_simp_decide");
+        if (stats_out) stats_out->assign(st.begin(), st.begin() + (std::ptrdiff_t)q.size());
+        return out;
+    }
+
+    // the device forms: every pointer is device memory, nothing is copied, the call returns before the kernel has run
+    void StatsDev(const snk_simp_map& map_dev, int n_q, const int32_t* q_dev, snk_simp_stats_result* out_dev, int min_obs = 3)
+    {
+        snk_simp_stats_params par = spar_;
+        par.min_obs               = min_obs;
+        check(snk_simp_stats_batch_dev(h_, &map_dev, &par, n_q, q_dev, out_dev), "snk_simp_stats_batch_dev");
+    }
+    void DecideDev(const snk_simp_graph& graph_dev, int n_q, const int32_t* q_dev, const snk_simp_stats_result* stats_dev, snk_simp_verdict* out_dev)
+    {
+        check(snk_simp_decide_batch_dev(h_, &graph_dev, &par_, node_cap_, n_q, q_dev, stats_dev, out_dev), "snk_simp_decide_batch_dev");
+    }
+    void Sync() { check(snk_matcher_sync(h_), "snk_matcher_sync"); }
+
+   private:
+    snk_matcher* h_ = nullptr;
+    snk_simp_params par_;
+    snk_simp_stats_params spar_;
+    int node_cap_;
+};
+
 // Saiga::P3PRansac as Tracking::TrackBruteForce uses it -- Snake/Tracking/TrackingCoarse.cpp:403-440, semantics "snk-p3p v1":
 //   RansacParameters params; params.maxIterations = 250; params.residualThreshold = chi1 * chi1;
 //   P3PRansac pnp2(params);  inliers = pnp2.solve(wps, ips, pose, inlierMatches, inlierMask);

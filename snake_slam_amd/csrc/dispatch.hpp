@@ -1,4 +1,4 @@
-// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, localmap.hip, scene.hip, ba.hip,
+// Which kernel form a launch shape selects: the ONE place where the thresholds of matcher.hip, pose.hip, mappoint.hip, covis.hip, localmap.hip, scene.hip, simp.hip, ba.hip,
 // orb.hip (the extractor's whole launch plan, over the geometry of orb_layout.hpp) and track.hip (the projection matchers) live.
 // Host-only and free of HIP includes, so that tests/cpp/dispatch_driver.cpp builds it with plain g++ and tests/forms.py can pin every
 // shape of the GPU tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
@@ -237,6 +237,23 @@ constexpr size_t scene_gather_carve(int pt_cap, int img_cap)
 {
     const size_t a = scene_points_carve(pt_cap), b = scene_obs_carve(img_cap);
     return (size_t)(SCENE_WIN_SLOTS + SCENE_MISC) * 4 + (a > b ? a : b);
+}
+
+// ---- keyframe culling (simp.hip: snk_simp_stats, snk_simp_decide and their _batch_dev forms) ------------------------------------------
+// One form each, a workgroup of four wavefronts per query.  simp_stats_kernel: a lane per feature, a list of at most simp_long_min
+// observations is walked by its lane, a longer one by a wavefront (covis_kernel's scheme); the depths stay in LDS for the radix select.
+// simp_decide_kernel: a lane per node, the strict upper triangle of the weight matrix in LDS.
+constexpr int SIMP_THREADS  = 256;
+constexpr int SIMP_LONG_MIN = 32;  // observations above which a list is walked by a wavefront
+constexpr int SIMP_MISC     = 32;  // u32 words of flags, counts and the partial results of the reductions (two banks of four u64)
+// long_env: SNK_SIMP_LONG_MIN (< 0 = unset; n >= 0: lists longer than n observations are queued -- 0 queues every walked list)
+constexpr int simp_long_min(int long_env) { return long_env >= 0 ? long_env : SIMP_LONG_MIN; }
+// LDS carve of simp_stats_kernel: a key per feature, the queue of long lists (a feature per lane and round), the words above
+constexpr size_t simp_stats_carve(int feat_cap) { return (size_t)((feat_cap + 3) & ~3) * 4 + (size_t)SIMP_THREADS * 4 + (size_t)SIMP_MISC * 4; }
+// LDS carve of simp_decide_kernel: the triangle (an even number of words), the sorted node keys, the nodes' keyframes, the words above
+constexpr size_t simp_decide_carve(int max_nodes)
+{
+    return (size_t)((max_nodes * (max_nodes - 1) / 2 + 1) & ~1) * 4 + (size_t)max_nodes * 8 + (size_t)((max_nodes + 1) & ~1) * 4 + (size_t)SIMP_MISC * 4;
 }
 
 // ---- bundle adjustment (ba.hip: ba_plan_pcg, enqueue_lm, snk_ba_solve_async, snk_ba_pcg_form; the hand-over asks ba_sets_will_run) --
