@@ -10,7 +10,7 @@
 //                        the first child wins a tie.  The children of a node are contiguous in memory (repacked at create): k = 10 is
 //                        one 320-byte run per step.  The loop runs exactly L times for every row (rows at a leaf idle), so the DPP
 //                        moves never sit under divergent control flow.
-//   bow_finish_kernel    one workgroup per frame: (word, feature) and (node, feature) keys sorted in LDS by a bitonic network, run
+//   bow_finish_kernel    one workgroup per frame: (word, feature) and (node, feature) keys sorted in LDS by block_sort (wg.hpp), run
 //                        lengths by a workgroup scan, the L1 norm by a fixed-order reduction, the division.
 //   bow_db_store_kernel  copies rows of a batched transform into the slots of the database.
 //   bow_db_score_kernel  brute force instead of an inverted file: one wavefront per stored keyframe looks its words up by binary search
@@ -28,6 +28,7 @@
 
 #include "matcher_handle.hpp"
 #include "bow_core.hpp"
+#include "wg.hpp"
 
 struct snk_bow_vocab : snk::HandleBase
 {
@@ -136,29 +137,6 @@ __global__ __launch_bounds__(256) void bow_descent_kernel(BowTree T, const u64* 
 }
 
 // ---- workgroup helpers of the finish and match kernels (256 threads) ----
-// bitonic sort, ascending, of s[0 .. N), N a power of two
-__device__ __forceinline__ void block_sort(u64* s, int N)
-{
-    for (int k = 2; k <= N; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1)
-        {
-            for (int i = threadIdx.x; i < N; i += 256)
-            {
-                const int o = i ^ j;
-                if (o > i)
-                {
-                    const u64 a = s[i], c = s[o];
-                    if ((a > c) == ((i & k) == 0))
-                    {
-                        s[i] = c;
-                        s[o] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // exclusive prefix of one int per thread over the workgroup, and the total
 __device__ __forceinline__ int block_scan_excl(int v, int* s_wave, int& total)
 {
@@ -239,7 +217,7 @@ __global__ __launch_bounds__(256) void bow_finish_kernel(const int* __restrict__
         s_key[i]    = (w >= 0 && w < n_vocab_words) ? (((u64)w << FEAT_BITS) | (u64)i) : KEY_NONE;
     }
     __syncthreads();
-    block_sort(s_key, N);
+    block_sort<256>(s_key, N);
     int runs = block_runs(s_key, n, s_hpos, s_wave, O.words + base);
     double part = 0.0;
     for (int r = tid; r < runs; r += 256) part += (double)(s_hpos[r + 1] - s_hpos[r]) * word_weight[(int)(s_key[s_hpos[r]] >> FEAT_BITS)];
@@ -262,7 +240,7 @@ __global__ __launch_bounds__(256) void bow_finish_kernel(const int* __restrict__
     }
     int m;
     (void)block_scan_excl(mine, s_wave, m);  // m = features with a node; also the barrier behind the key writes
-    block_sort(s_key, N);
+    block_sort<256>(s_key, N);
     runs = block_runs(s_key, m, s_hpos, s_wave, O.node_id + base);
     for (int r = tid; r <= runs; r += 256) O.node_start[(size_t)b * (cap + 1) + r] = s_hpos[r];
     for (int i = tid; i < m; i += 256) O.features[base + i] = (int)(s_key[i] & (u64)(BOW_MAX_FEATURES - 1));

@@ -5,22 +5,21 @@
 //
 // Mapping to the hardware.  covis_kernel: a workgroup of four wavefronts per set (a query keyframe or a frame); the two forms are the
 // template's four switches.  The counters are u32 [n_kf] in LDS.  Count: a lane takes a feature, applies the gate and reads its point's
-// list bounds; a list of at most long_min observations it walks itself with LDS atomic adds, a longer one it appends to a queue in LDS
-// (at most one entry per lane and round), and after a barrier each wavefront takes queued lists in turn, a lane per observation, so
-// that a 4096-entry list costs 64 steps of one wavefront instead of 4096 of a lane.  Integer adds commute: the counters do not depend
-// on the order in which atomics land.  Emit: one pass over the counters applies the bad flags, the threshold and the arg-max (an LDS
-// atomic max of count << 32 | ~id) and zeroes every counter that is not listed, so the later passes test count > 0 only.  More than
-// cap listed: covis_cut builds the cap-th largest key bit by bit, one counting pass per bit (partial sums per wavefront, one barrier a
-// pass).  The ids kept (a power of two of them, padded) are sorted in LDS by a bitonic network on the key count << 32 | id, which has
-// no ties, so the compaction order (an atomic slot counter) does not show in the result.  No step is quadratic.  No scratch; every
-// byte of LDS is in the dynamic carve (covis_carve).  The host entries check every table and upload it; the device entries launch
-// the same kernel, which checks what the host could not see and answers SNK_COVIS_BAD_INDEX per set.
+// list bounds; the lists are walked by walk_lists (wg.hpp: a short one by its lane, a long one by a wavefront) with LDS atomic adds.
+// Integer adds commute: the counters do not depend on the order in which atomics land.  Emit: one pass over the counters applies the
+// bad flags, the threshold and the arg-max (an LDS atomic max of count << 32 | ~id) and zeroes every counter that is not listed, so the
+// later passes test count > 0 only.  More than cap listed: covis_cut builds the cap-th largest key bit by bit, one counting pass per
+// bit (block_reduce, one barrier a pass).  The ids kept (a power of two of them, padded) are sorted in LDS by block_sort on the key
+// count << 32 | id, which has no ties, so the compaction order (an atomic slot counter) does not show in the result.  No step is
+// quadratic.  No scratch; every byte of LDS is in the dynamic carve (covis_carve).  The host entries check every table and upload it;
+// the device entries launch the same kernel, which checks what the host could not see and answers SNK_COVIS_BAD_INDEX per set.
 #include <cstddef>
 
 #include "matcher_handle.hpp"
 
 #include "covis_core.hpp"
 #include "dispatch.hpp"
+#include "wg.hpp"
 
 namespace snk
 {
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
     u32* s_ids   = s_cnt + ((c.n_kf + 3) & ~3);                     // [sort_len]
     int* s_queue = reinterpret_cast<int*>(s_ids + sort_len);        // [COVIS_THREADS] points whose lists a wavefront walks
     u32* s_misc  = reinterpret_cast<u32*>(s_queue + COVIS_THREADS);  // [COVIS_MISC]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int set = blockIdx.x;
 
     for (int k = tid; k < c.n_kf; k += COVIS_THREADS) s_cnt[k] = 0;
@@ -102,38 +101,23 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
         a = c.obs_start[p], b = c.obs_start[p + 1];
         return a >= 0 && b >= a && b <= c.n_obs;
     };
-    u32 queued_before = 0;
-    for (int base = first; base < last; base += COVIS_THREADS)  // uniform
-    {
-        const int i = base + tid;
-        int p = -1, a = 0, b = 0;
-        if (i < last)
-        {
+    walk_lists<COVIS_THREADS>(
+        first, last, c.long_min, s_queue, &s_misc[W_QUEUED],
+        [&](int i, int& p, int& a, int& b) {
             p = c.item_point[i];
-            if (p < -1 || p >= c.n_points) s_misc[W_BAD] = 1, p = -1;
-            else if (p >= 0)
-            {
-                if (!covis_gate<GATE>(c.pt_flags[p], GATE ? c.item_depth[i] : 0.0f, c.th_depth)) p = -1;
-                else if (!list_of(p, a, b)) s_misc[W_BAD] = 1, p = -1;
-            }
-        }
-        if (p >= 0)
-        {
-            if (b - a > c.long_min) s_queue[atomicAdd(&s_misc[W_QUEUED], 1u) - queued_before] = p;  // at most one per lane and round
-            else
-                for (int o = a; o < b; ++o) add(o);
-        }
-        __syncthreads();
-        const u32 queued = s_misc[W_QUEUED];  // a running total: nobody resets it between rounds
-        for (int e = wave; e < (int)(queued - queued_before); e += COVIS_THREADS / 64)
-        {
+            if (p < -1 || p >= c.n_points) return s_misc[W_BAD] = 1, false;
+            if (p < 0 || !covis_gate<GATE>(c.pt_flags[p], GATE ? c.item_depth[i] : 0.0f, c.th_depth)) return false;
+            if (!list_of(p, a, b)) return s_misc[W_BAD] = 1, false;
+            return true;
+        },
+        [&](int, int a, int b) {
+            for (int o = a; o < b; ++o) add(o);
+        },
+        [&](int p, int lane) {
             int la, lb;
-            list_of(s_queue[e], la, lb);  // checked when it was queued
+            list_of(p, la, lb);  // checked when it was queued
             for (int o = la + lane; o < lb; o += 64) add(o);
-        }
-        queued_before = queued;
-        __syncthreads();  // the queue is the next round's
-    }
+        });
     __syncthreads();
     if (s_misc[W_BAD])  // uniform
     {
@@ -202,19 +186,13 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
         int pass = 0;
         cut      = covis_cut(
             [&](u64 T) {
-                int n = 0;
+                u32 n = 0;
                 for (int k = tid; k < c.n_kf; k += COVIS_THREADS)
                 {
                     const u32 w = s_cnt[k];
-                    n += w > 0 && covis_key(w, (u32)k) >= T ? 1 : 0;
+                    n += w > 0 && covis_key(w, (u32)k) >= T ? 1u : 0u;
                 }
-                n = wave_sum_xor(n);
-                // two banks of partial sums: a bank is written again two passes later, behind the barrier of the pass between
-                u32* part = s_misc + W_PART + (pass & 1) * (COVIS_THREADS / 64);
-                if (lane == 0) part[wave] = (u32)n;
-                __syncthreads();
-                pass += 1;
-                return (int)(part[0] + part[1] + part[2] + part[3]);
+                return (int)block_reduce<COVIS_THREADS>(n, [](u32 x, u32 y) { return x + y; }, s_misc + W_PART, pass);
             },
             c.cap, (u32)(max_key >> 32), c.n_kf);
     }
@@ -235,21 +213,7 @@ __global__ __launch_bounds__(COVIS_THREADS) void covis_kernel(CovisCall c)
     }
     __syncthreads();
     auto key_of = [&](u32 id) { return id == 0xFFFFFFFFu ? ~0ull : covis_key(s_cnt[id], id); };
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1)
-        {
-            for (int i = tid; i < P; i += COVIS_THREADS)
-            {
-                const int l = i ^ j;
-                if (l > i)
-                {
-                    const u32 x = s_ids[i], y = s_ids[l];
-                    const bool up = (i & k2) == 0;
-                    if ((key_of(x) > key_of(y)) == up) s_ids[i] = y, s_ids[l] = x;
-                }
-            }
-            __syncthreads();
-        }
+    block_sort<COVIS_THREADS>(s_ids, P, [&](u32 x, u32 y) { return key_of(x) < key_of(y); });
     for (int i = tid; i < n_conn; i += COVIS_THREADS)
     {
         const u32 id = s_ids[i];

@@ -4,6 +4,7 @@
 // shape of the GPU tests to the form it was written for.  launch_knn2, snk_stereo_match, stereo_match_batch_dev_impl, snk_pose_refine,
 // refine_batch_impl, the BA solver (ba_plan_pcg, enqueue_lm), the extractor (snk_orb_configure, run_part, run_pipeline) and the batched
 // projection matchers call these functions and keep no copy of the conditions; the environment switches are read there and passed in.
+// The workgroup-level blocks that the map-side kernels share (sort, long scan, first-appearance table, list walk, reduction): wg.hpp.
 #pragma once
 #include <cstddef>
 
@@ -213,7 +214,7 @@ constexpr size_t lmap_gather_carve(int kf_cap, int pts_cap)
 
 // ---- local BA windows (scene.hip: snk_scene_window, snk_scene_gather and their _batch_dev forms) -------------------------------------
 // One form each, a workgroup per query.  scene_window_kernel: one wavefront, a lane per candidate.  scene_gather_kernel: four wavefronts;
-// its carve is used twice: first the point table of lmap_gather_kernel (four-byte slots), then, the point list being in the pt_id row,
+// its carve is used twice: first the first-appearance table of wg.hpp (four-byte slots, as lmap_gather_kernel), then, the point list being in the pt_id row,
 // the fixed-camera table (a key and a value per slot), the sort keys of the fixed cameras, a base per image and the words of a chunk.
 constexpr int SCENE_WIN_THREADS = 64;   // one wavefront: a lane per candidate (SCENE_MAX_WINDOW)
 constexpr int SCENE_THREADS     = 256;  // four wavefronts; a chunk is one point or one observation per lane
@@ -241,7 +242,7 @@ constexpr size_t scene_gather_carve(int pt_cap, int img_cap)
 
 // ---- keyframe culling (simp.hip: snk_simp_stats, snk_simp_decide and their _batch_dev forms) ------------------------------------------
 // One form each, a workgroup of four wavefronts per query.  simp_stats_kernel: a lane per feature, a list of at most simp_long_min
-// observations is walked by its lane, a longer one by a wavefront (covis_kernel's scheme); the depths stay in LDS for the radix select.
+// observations is walked by its lane, a longer one by a wavefront (walk_lists of wg.hpp, as covis_kernel); the depths stay in LDS for the radix select.
 // simp_decide_kernel: a lane per node, the strict upper triangle of the weight matrix in LDS.
 constexpr int SIMP_THREADS  = 256;
 constexpr int SIMP_LONG_MIN = 32;  // observations above which a list is walked by a wavefront

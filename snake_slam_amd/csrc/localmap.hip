@@ -10,22 +10,18 @@
 // lmap_select_kernel.  The marks of TrackingFine.cpp:246-250 are a bit per keyframe (atomic OR).  The direct keyframes are copied from
 // the back of the vote's list.  Walk 1: a lane per remaining entry evaluates its own draw; accepted entries are ranked into the local
 // list, the rejected ones are only counted (walk 2 recomputes their draws instead of storing up to n_kf of them).  Neighbours: a slot
-// per (local keyframe, neighbour rank) in list order; a listable candidate becomes the key kf << bits | slot, the keys are sorted by a
-// bitonic network and an entry whose predecessor has another keyframe is that keyframe's first appearance; the firsts go back to
+// per (local keyframe, neighbour rank) in list order; a listable candidate becomes the key kf << bits | slot, the keys are sorted by
+// block_sort (wg.hpp) and an entry whose predecessor has another keyframe is that keyframe's first appearance; the firsts go back to
 // their slots, so that a scan over the slots restores the reference's order.  Walk 2 runs over the rejected entries and then over the
 // slots, two scans per chunk (the position in `indirect`, the position in the local list).
 //
 // lmap_gather_kernel.  Every candidate has an order number: its position in the concatenated feature ranges of the local keyframes
-// (a prefix sum over at most 256 ranges), the own points behind them.  The table has four-byte slots holding order + 1 (0 = free); the
-// id of a slot is recovered through feat_point / set_point by a binary search of the prefix sums, so 32 768 slots are 128 KiB.
-// Build: linear probing from lmap_hash(id); a free slot is claimed by one compare-and-swap, a slot of the same id takes an atomic
-// minimum, any other slot is passed.  A slot's id never changes, so equal ids meet in one slot whatever the order of the lanes.  The
-// own points come after a barrier: on a slot that a keyframe placed they set bit 31 ("valid is cleared"), otherwise they claim or take
-// the minimum among themselves.  Every probe loop ends after `slots` steps at the latest and no step waits for another lane; the count
-// of claims sets a flag once it passes pts_cap and candidates then stop claiming (the table keeps room for the claims in flight).
-// Emit: chunk by chunk in order, a candidate finds its slot again and wins iff the slot holds its order; winners are ranked by the
-// scan and write their 96-byte record (twelve 8-byte words) and their id.  No result depends on the order in which atomics land: the
-// table's contents as a set (id -> minimum order, flag) do not, and nothing else is read from it.
+// (block_scan_long over at most 256 ranges), the own points behind them.  The points are the first-appearance table of wg.hpp: four-byte
+// slots holding order + 1, the id of a slot recovered through feat_point / set_point by a search of the prefix sums, so 32 768 slots
+// are 128 KiB.  A slot of the same id takes an atomic minimum.  The own points come after a barrier: on a slot that a keyframe placed
+// they set bit 31 ("valid is cleared"), otherwise they claim or take the minimum among themselves.  Emit (table_emit): winners write
+// their 96-byte record (twelve 8-byte words) and their id.  No result depends on the order in which atomics land: the table's contents
+// as a set (id -> minimum order, flag) do not, and nothing else is read from it.
 //
 // The host entries lay the arrays of a call out as one block, inputs and outputs alike: stage.hpp, and matcher_handle.hpp for the copies.
 #include <cstddef>
@@ -34,6 +30,7 @@
 
 #include "lmap_core.hpp"
 #include "dispatch.hpp"
+#include "wg.hpp"
 
 namespace snk
 {
@@ -222,21 +219,7 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_select_kernel(SelectCall c)
         finish(LMAP_BAD_INDEX);
         return;
     }
-    for (int k2 = 2; k2 <= Pn; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1)
-        {
-            for (int i = tid; i < Pn; i += LMAP_THREADS)
-            {
-                const int l = i ^ j;
-                if (l > i)
-                {
-                    const u32 x = s_keys[i], y = s_keys[l];
-                    const bool up = (i & k2) == 0;
-                    if ((x > y) == up) s_keys[i] = y, s_keys[l] = x;
-                }
-            }
-            __syncthreads();
-        }
+    block_sort<LMAP_THREADS>(s_keys, Pn);
     for (int i = tid; i < Pn; i += LMAP_THREADS)
     {
         const u32 k32 = s_keys[i];
@@ -289,7 +272,6 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int n_slots = lmap_table_slots(c.pts_cap);
-    const u32 mask    = (u32)n_slots - 1u;
     u32* s_tab    = reinterpret_cast<u32*>(smem);                      // [n_slots] order + 1 | own bit; 0 = free
     int* s_prefix = reinterpret_cast<int*>(s_tab + n_slots);           // [kf_cap + 1] first order of a local keyframe's features
     int* s_fstart = s_prefix + c.kf_cap + 1;                           // [kf_cap] its feat_start
@@ -333,11 +315,8 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
             else len = b - a, s_fstart[tid] = a;
         }
     }
-    // 256 lengths of up to 2^30 do not fit an int: the halves are summed apart
-    int tot_lo, tot_hi;
-    const int ex_lo     = block_scan<LMAP_THREADS>(len & 0xFFFF, tot_lo, s_misc + W_PART, pass);
-    const int ex_hi     = block_scan<LMAP_THREADS>(len >> 16, tot_hi, s_misc + W_PART, pass);
-    const long long T64 = ((long long)tot_hi << 16) + tot_lo;
+    long long T64;
+    const long long ex = block_scan_long<LMAP_THREADS>(len, T64, s_misc + W_PART, pass);
     const int own_a = c.set_start[set], own_b = c.set_start[set + 1];
     const bool own_ok = own_a >= 0 && own_b >= own_a && own_b <= c.n_set_points;
     const int n_own   = own_ok ? own_b - own_a : 0;
@@ -347,50 +326,24 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
         return;
     }
     const int T = (int)T64;
-    if (tid < n_local) s_prefix[tid] = (int)(((long long)ex_hi << 16) + ex_lo);
+    if (tid < n_local) s_prefix[tid] = (int)ex;
     if (tid == 0) s_prefix[n_local] = T;
     __syncthreads();
     const int fid = c.frame_id[set];
 
-    // the feature index of keyframe candidate ord: the last local keyframe whose first order is <= ord
-    auto feature_of = [&](int ord) {
-        int lo = 0, hi = n_local;
-        while (hi - lo > 1)
-        {
-            const int mid = (lo + hi) >> 1;
-            if (s_prefix[mid] <= ord) lo = mid;
-            else hi = mid;
-        }
-        return s_fstart[lo] + (ord - s_prefix[lo]);
+    // the id of candidate ord: an own point, or the feature ord - first order of the last local keyframe whose first order is <= ord
+    auto id_of = [&](int ord) {
+        if (ord >= T) return c.set_point[own_a + (ord - T)];
+        const int li = last_at_most(s_prefix, n_local, ord);
+        return c.feat_point[s_fstart[li] + (ord - s_prefix[li])];
     };
-    auto id_of = [&](int ord) { return ord >= T ? c.set_point[own_a + (ord - T)] : c.feat_point[feature_of(ord)]; };
-    auto load  = [&](int slot) { return __atomic_load_n(&s_tab[slot], __ATOMIC_RELAXED); };
-
-    // addPoint (LocalMap.h:139-154) for candidate (p, ord): at most n_slots steps, none of which waits for another lane
+    // addPoint (LocalMap.h:139-154) for candidate (p, ord)
     auto insert = [&](int p, int ord, bool own) {
-        if (__atomic_load_n(&s_misc[W_FULL], __ATOMIC_RELAXED)) return;
-        u32 slot = lmap_hash(p) & mask;
-        for (int probe = 0; probe < n_slots; ++probe, slot = (slot + 1) & mask)
-        {
-            u32 w = load(slot);
-            if (w == 0)
-            {
-                w = atomicCAS(&s_tab[slot], 0u, (u32)ord + 1u);
-                if (w == 0)
-                {
-                    if ((int)atomicAdd(&s_misc[W_COUNT], 1u) + 1 > c.pts_cap) s_misc[W_FULL] = 1;
-                    return;
-                }
-            }
-            const int there = (int)(w & 0x7FFFFFFFu) - 1;
-            if (id_of(there) == p)
-            {
-                if (own && there < T) atomicOr(&s_tab[slot], 0x80000000u);  // :353 on a point that a keyframe placed
-                else atomicMin(&s_tab[slot], (u32)ord + 1u);                // no own bit on this slot, now or later
-                return;
-            }
-        }
-        s_misc[W_FULL] = 1;
+        u32 seen;
+        const int slot = table_place(s_tab, n_slots, p, ord, c.pts_cap, &s_misc[W_COUNT], &s_misc[W_FULL], seen, id_of);
+        if (slot < 0 || seen == 0) return;
+        if (own && (int)(seen & 0x7FFFFFFFu) - 1 < T) atomicOr(&s_tab[slot], 0x80000000u);  // :353 on a point that a keyframe placed
+        else atomicMin(&s_tab[slot], (u32)ord + 1u);                                        // no own bit on this slot, now or later
     };
 
     // ---- build: the local keyframes' features (:334-342) ----
@@ -405,7 +358,7 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
         }
     }
     __syncthreads();
-    // ---- build: the frame's own points (:344-354) ----
+    // ---- build: the frame's own points (:344-354), behind the barrier: bit 31 goes on slots that a keyframe placed ----
     for (int i = tid; i < n_own; i += LMAP_THREADS)
     {
         const int p = c.set_point[own_a + i];
@@ -419,44 +372,21 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
         return;
     }
 
-    // ---- emit: chunk by chunk in order; a candidate wins iff its slot holds its order ----
+    // ---- emit: the winners write their 96-byte record (twelve 8-byte words) and their id ----
     u64* recs = c.lm_pts + (size_t)set * (size_t)c.pts_cap * 12;
-    int n_out = 0, searchable = 0, own_new = 0;
-    const int total_cand = T + n_own;
-    for (int base = 0; base < total_cand; base += LMAP_THREADS)  // uniform
-    {
-        const int ord = base + tid;
-        int p         = -1;
-        bool win = false, valid = false;
-        if (ord < total_cand)
-        {
-            p = id_of(ord);
-            const bool live = ord < T ? !lmap_kf_point_skipped(p, p >= 0 ? c.pt_flags[p] : 0, p >= 0 ? c.pt_last_seen[p] : 0, fid)
-                                      : !lmap_own_point_skipped(p, p >= 0 ? c.pt_flags[p] : 0);
-            if (live)
-            {
-                u32 slot = lmap_hash(p) & mask;
-                for (int probe = 0; probe < n_slots; ++probe, slot = (slot + 1) & mask)
-                {
-                    const u32 w = load(slot);
-                    if (w == 0) break;  // cannot happen: every live candidate was inserted
-                    if (id_of((int)(w & 0x7FFFFFFFu) - 1) == p)
-                    {
-                        win   = (w & 0x7FFFFFFFu) == (u32)ord + 1u;
-                        valid = ord < T && (w >> 31) == 0;
-                        break;
-                    }
-                }
-            }
-        }
-        int total;
-        const int rank = n_out + block_scan<LMAP_THREADS>(win ? 1 : 0, total, s_misc + W_PART, pass);
-        if (win && rank < c.pts_cap)
-        {
-            u64* r        = recs + (size_t)rank * 12;
-            const u64* sp = c.pos + (size_t)p * 3;
-            const u64* sn = c.normal + (size_t)p * 3;
-            const u64* sd = c.desc + (size_t)p * 4;
+    int searchable = 0, own_new = 0;
+    const int n_out = table_emit<LMAP_THREADS>(
+        s_tab, n_slots, T + n_own, c.pts_cap, s_misc + W_PART, pass, id_of,
+        [&](int ord, int p) {
+            return ord < T ? !lmap_kf_point_skipped(p, p >= 0 ? c.pt_flags[p] : 0, p >= 0 ? c.pt_last_seen[p] : 0, fid)
+                           : !lmap_own_point_skipped(p, p >= 0 ? c.pt_flags[p] : 0);
+        },
+        [&](int ord, int p, int rank, u32 w) {
+            const bool valid = ord < T && (w >> 31) == 0;
+            u64* r           = recs + (size_t)rank * 12;
+            const u64* sp    = c.pos + (size_t)p * 3;
+            const u64* sn    = c.normal + (size_t)p * 3;
+            const u64* sd    = c.desc + (size_t)p * 4;
             r[0] = sp[0], r[1] = sp[1], r[2] = sp[2];
             r[3] = sn[0], r[4] = sn[1], r[5] = sn[2];
             r[6] = sd[0], r[7] = sd[1], r[8] = sd[2], r[9] = sd[3];
@@ -465,9 +395,7 @@ __global__ __launch_bounds__(LMAP_THREADS) void lmap_gather_kernel(GatherCall c)
             ids[rank] = p;
             searchable += valid ? 1 : 0;
             own_new += ord >= T ? 1 : 0;
-        }
-        n_out += total;
-    }
+        });
     searchable = wave_sum_xor(searchable);
     own_new    = wave_sum_xor(own_new);
     if ((tid & 63) == 0)

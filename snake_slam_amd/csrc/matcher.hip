@@ -10,6 +10,7 @@
 // exactly (the two lexicographically smallest (dist, idx) pairs).
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "wg.hpp"
 
 namespace snk
 {
@@ -389,23 +390,7 @@ __device__ __forceinline__ void stereo_sort_network(const snk_kp64* __restrict__
         keys[i] = k;
     }
     __syncthreads();
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1)
-        {
-            for (int t = tid; t < (n_pow2 >> 1); t += 256)
-            {
-                const int i   = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int ixj = i | j;
-                const bool up = (i & k) == 0;
-                const u32 x = keys[i], y = keys[ixj];
-                if ((x > y) == up)
-                {
-                    keys[i]   = y;
-                    keys[ixj] = x;
-                }
-            }
-            __syncthreads();
-        }
+    block_sort<256>(keys, n_pow2);
     for (int i = tid; i < nr; i += 256) out[i] = keys[i];
 }
 __global__ __launch_bounds__(256) void stereo_sort_kernel(const snk_kp64* __restrict__ right, const int* __restrict__ nr_dev,

@@ -10,11 +10,11 @@
 // earlier ones (:142) and ranks the survivors by counting the smaller ones (:151).
 //
 // scene_gather_kernel.  Four wavefronts, one carve used twice.
-//   Points: lmap_gather_kernel's table -- four-byte slots holding the candidate's order + 1 in the concatenated feature ranges of the
-//   window, the id recovered through feat_point -- and its emit: winners ranked chunk by chunk by block_scan.  The point list goes to the
-//   pt_id row, which is this kernel's work list from here on (and is -1 again if the query fails later).
-//   The walk: the observation stream of the points in order.  256 points per chunk, a prefix sum of their list lengths; 256 stream items
-//   per sub-chunk, a lane finds its point by a binary search of the prefix sums.  Its ordinal is the position in the stream.
+//   Points: the first-appearance table of wg.hpp over the concatenated feature ranges of the window, the id recovered through
+//   feat_point, a slot of the same id taking a plain atomic minimum.  The point list goes to the pt_id row, which is this kernel's work
+//   list from here on (and is -1 again if the query fails later).
+//   The walk: the observation stream of the points in order.  256 points per chunk, block_scan_long over their list lengths; 256 stream
+//   items per sub-chunk, a lane finds its point by last_at_most.  Its ordinal is the position in the stream.
 //   Walk 1, fixed cameras: a keyframe that is neither bad nor in the window (binary search of the 64 window keyframes) goes into an
 //   open-addressing table of (kf + 1, minimum ordinal): claim by compare-and-swap, atomic minimum.  The minima are distinct, so sorting
 //   them (bitonic, LDS) and looking one up again is the order of first appearance; the slot's value becomes the image index.
@@ -31,6 +31,7 @@
 
 #include "scene_core.hpp"
 #include "dispatch.hpp"
+#include "wg.hpp"
 
 namespace snk
 {
@@ -182,7 +183,6 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
     u32* region = s_misc + SCENE_MISC;
     // phase 1
     const int n_slots = lmap_table_slots(O.pt_cap);
-    const u32 mask    = (u32)n_slots - 1u;
     u32* s_tab    = region;                                            // [n_slots] order + 1; 0 = free
     int* s_prefix = reinterpret_cast<int*>(s_tab + n_slots);           // [SCENE_WIN_SLOTS + 1] first order of a window keyframe's features
     int* s_fstart = s_prefix + SCENE_WIN_SLOTS + 1;                    // [SCENE_WIN_SLOTS] its feat_start
@@ -235,32 +235,23 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
             else len = b - a, s_fstart[tid] = a;
         }
     }
-    int tot_lo, tot_hi;
-    const int ex_lo     = block_scan<SCENE_THREADS>(len & 0xFFFF, tot_lo, s_misc + W_PART, pass);
-    const int ex_hi     = block_scan<SCENE_THREADS>(len >> 16, tot_hi, s_misc + W_PART, pass);
-    const long long T64 = ((long long)tot_hi << 16) + tot_lo;
+    long long T64;
+    const long long ex = block_scan_long<SCENE_THREADS>(len, T64, s_misc + W_PART, pass);
     if (T64 > LMAP_MAX_ORDER || s_misc[W_BAD])  // uniform: the scans' barriers are behind the writes of W_BAD
     {
         finish(SCENE_BAD_INDEX);
         return;
     }
     const int T = (int)T64;
-    if (tid < nw) s_prefix[tid] = (int)(((long long)ex_hi << 16) + ex_lo);
+    if (tid < nw) s_prefix[tid] = (int)ex;
     if (tid == 0) s_prefix[nw] = T;
     __syncthreads();
 
-    auto feature_of = [&](int ord) {
-        int lo = 0, hi = nw;
-        while (hi - lo > 1)
-        {
-            const int mid = (lo + hi) >> 1;
-            if (s_prefix[mid] <= ord) lo = mid;
-            else hi = mid;
-        }
-        return s_fstart[lo] + (ord - s_prefix[lo]);
+    auto id_of = [&](int ord) {
+        const int li = last_at_most(s_prefix, nw, ord);
+        return M.feat_point[s_fstart[li] + (ord - s_prefix[li])];
     };
-    auto id_of = [&](int ord) { return M.feat_point[feature_of(ord)]; };
-    auto load  = [&](const u32* w) { return __atomic_load_n(w, __ATOMIC_RELAXED); };
+    auto load = [&](const u32* w) { return __atomic_load_n(w, __ATOMIC_RELAXED); };
 
     // ---- points (:154-167): build ----
     for (int li = 0; li < nw; ++li)  // uniform
@@ -270,31 +261,11 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
         {
             const int p = M.feat_point[a + f];
             if (p < -1 || p >= M.n_points) s_misc[W_BAD] = 1;
-            else if (!scene_point_skipped(p, p >= 0 ? M.pt_flags[p] : 0) && !load(&s_misc[W_FULL]))
+            else if (!scene_point_skipped(p, p >= 0 ? M.pt_flags[p] : 0))
             {
-                const int ord = first + f;
-                u32 slot      = lmap_hash(p) & mask;
-                bool placed   = false;
-                for (int probe = 0; probe < n_slots && !placed; ++probe, slot = (slot + 1) & mask)
-                {
-                    u32 w = load(&s_tab[slot]);
-                    if (w == 0)
-                    {
-                        w = atomicCAS(&s_tab[slot], 0u, (u32)ord + 1u);
-                        if (w == 0)
-                        {
-                            if ((int)atomicAdd(&s_misc[W_COUNT], 1u) + 1 > O.pt_cap) s_misc[W_FULL] = 1;
-                            placed = true;
-                            continue;
-                        }
-                    }
-                    if (id_of((int)w - 1) == p)
-                    {
-                        atomicMin(&s_tab[slot], (u32)ord + 1u);
-                        placed = true;
-                    }
-                }
-                if (!placed) s_misc[W_FULL] = 1;
+                u32 seen;
+                const int slot = table_place(s_tab, n_slots, p, first + f, O.pt_cap, &s_misc[W_COUNT], &s_misc[W_FULL], seen, id_of);
+                if (slot >= 0 && seen != 0) atomicMin(&s_tab[slot], (u32)(first + f) + 1u);
             }
         }
     }
@@ -304,36 +275,10 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
         finish(s_misc[W_BAD] ? SCENE_BAD_INDEX : SCENE_PTS_OVERFLOW);
         return;
     }
-    // ---- points: emit; a candidate wins iff its slot holds its order ----
-    int n_pt = 0;
-    for (int base = 0; base < T; base += SCENE_THREADS)  // uniform
-    {
-        const int ord = base + tid;
-        int p         = -1;
-        bool win      = false;
-        if (ord < T)
-        {
-            p = id_of(ord);
-            if (!scene_point_skipped(p, p >= 0 ? M.pt_flags[p] : 0))
-            {
-                u32 slot = lmap_hash(p) & mask;
-                for (int probe = 0; probe < n_slots; ++probe, slot = (slot + 1) & mask)
-                {
-                    const u32 w = load(&s_tab[slot]);
-                    if (w == 0) break;  // cannot happen: every live candidate was inserted
-                    if (id_of((int)w - 1) == p)
-                    {
-                        win = w == (u32)ord + 1u;
-                        break;
-                    }
-                }
-            }
-        }
-        int total;
-        const int rank = n_pt + block_scan<SCENE_THREADS>(win ? 1 : 0, total, s_misc + W_PART, pass);
-        if (win && rank < O.pt_cap) ids[rank] = p;
-        n_pt += total;
-    }
+    // ---- points: emit ----
+    const int n_pt = table_emit<SCENE_THREADS>(
+        s_tab, n_slots, T, O.pt_cap, s_misc + W_PART, pass, id_of, [&](int, int p) { return !scene_point_skipped(p, p >= 0 ? M.pt_flags[p] : 0); },
+        [&](int, int p, int rank, u32) { ids[rank] = p; });
     __syncthreads();  // the table is read no more; the point list is in ids
 
     // ---- the carve again: the fixed-camera table, the bases ----
@@ -383,29 +328,17 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
             }
             s_pinfo[tid] = p;
             if (bad) s_misc[W_BAD] = 1;
-            int lo_t, hi_t;
-            const int lo_e    = block_scan<SCENE_THREADS>(plen & 0xFFFF, lo_t, s_misc + W_PART, pass);
-            const int hi_e    = block_scan<SCENE_THREADS>(plen >> 16, hi_t, s_misc + W_PART, pass);
-            const long long L = ((long long)hi_t << 16) + lo_t;
+            long long L;
+            const long long ex = block_scan_long<SCENE_THREADS>(plen, L, s_misc + W_PART, pass);
             if (s_misc[W_BAD] || walk_base + L > SCENE_MAX_WALK) return false;  // uniform
-            s_pstart[tid] = (int)(((long long)hi_e << 16) + lo_e);
+            s_pstart[tid] = (int)ex;
             if (tid == 0) s_pstart[SCENE_THREADS] = (int)L;
             __syncthreads();
             for (int sbase = 0; sbase < (int)L; sbase += SCENE_THREADS)  // uniform
             {
                 const int i       = sbase + tid;
                 const bool active = i < (int)L;
-                int lo            = 0;
-                if (active)
-                {
-                    int hi = SCENE_THREADS;
-                    while (hi - lo > 1)
-                    {
-                        const int mid = (lo + hi) >> 1;
-                        if (s_pstart[mid] <= i) lo = mid;
-                        else hi = mid;
-                    }
-                }
+                const int lo      = active ? last_at_most(s_pstart, SCENE_THREADS, i) : 0;
                 f(active, pbase + lo, active ? s_pinfo[lo] : -1, active ? s_ostart[lo] + (i - s_pstart[lo]) : 0, (int)walk_base + i);
             }
             walk_base += L;
@@ -478,6 +411,8 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_gather_kernel(GatherCall 
     const int Pn      = lmap_pow2_at_least(n_fixed, 4);  // <= scene_sort_len(img_cap)
     for (int i = n_fixed + tid; i < Pn; i += SCENE_THREADS) s_sort[i] = 0xFFFFFFFFu;
     __syncthreads();
+    // The network of wg.hpp's block_sort in its `i ^ j` shape, kept inline: with every block of this kernel shared, the gather call of
+    // tools/probes/scene_timing.py measured 0.9 % slower than before (profiles/NOTES.md); with this one inline it does not.
     for (int k2 = 2; k2 <= Pn; k2 <<= 1)
         for (int j = k2 >> 1; j > 0; j >>= 1)
         {

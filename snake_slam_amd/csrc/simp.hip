@@ -4,10 +4,9 @@
 // The per-query statements are simp_core.hpp's; the long-list threshold and the carves are dispatch.hpp's.
 //
 // Mapping to the hardware.  Both kernels: a workgroup of four wavefronts per query, every byte of LDS in the dynamic carve, no scratch.
-// simp_stats_kernel: a lane takes a feature, computes its depth key into LDS and reads its point's list bounds; a list of at most
-// long_min observations it walks itself, a longer one it appends to a queue in LDS (at most one entry per lane and round), and after a
-// barrier each wavefront takes queued lists in turn, a lane per observation (covis_kernel's scheme).  The early stop at three qualifying
-// observations is a count >= 3.  The counts are integer sums, the median is a radix select on the ordered key (a counting pass per
+// simp_stats_kernel: a lane takes a feature, computes its depth key into LDS and reads its point's list bounds; the lists are walked by
+// walk_lists (wg.hpp: a short one by its lane, a long one by a wavefront).  The early stop at three qualifying observations is a
+// count >= 3.  The counts are integer sums, the median is a radix select on the ordered key (a counting pass per
 // bit): nothing depends on the order in which lanes finish.
 // simp_decide_kernel: the nodes are compacted in list order by a prefix sum, the node table is rank-sorted by keyframe so that a target's
 // local id is a binary search, and every node's list is walked by a wavefront, a lane per entry, the weight going into the strict upper
@@ -21,6 +20,7 @@
 
 #include "dispatch.hpp"
 #include "simp_core.hpp"
+#include "wg.hpp"
 
 namespace snk
 {
@@ -63,23 +63,8 @@ struct SimpDecideCall
     SimpVerdict* out;
 };
 
-// words of s_misc: flags and sums, then two banks of four u64 (the reductions), then two banks of four u32 (block_scan)
+// words of s_misc: flags and sums, then two banks of four u64 (block_reduce), then two banks of four u32 (block_scan)
 enum { W_BAD = 0, W_QUEUED = 1, W_NDEPTH = 2, W_MATCH = 3, W_NMPS = 4, W_NRED = 5, W_PART64 = 8, W_PART32 = 24 };
-
-// op over the workgroup, returned to every lane.  part: two banks of four; a bank is written again two passes later, behind the
-// barrier of the pass between.  Called by all lanes together.
-template <class Op>
-__device__ __forceinline__ u64 block_reduce(u64 v, Op op, u64* part, int& pass)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = op(v, __shfl_xor(v, s));
-    u64* bank = part + (pass & 1) * (SIMP_THREADS / 64);
-    pass += 1;
-    if (lane == 0) bank[wave] = v;
-    __syncthreads();
-    return op(op(bank[0], bank[1]), op(bank[2], bank[3]));
-}
 
 __global__ __launch_bounds__(SIMP_THREADS) void simp_stats_kernel(SimpStatsCall c)
 {
@@ -89,7 +74,7 @@ __global__ __launch_bounds__(SIMP_THREADS) void simp_stats_kernel(SimpStatsCall 
     u32* s_misc  = reinterpret_cast<u32*>(s_queue + SIMP_THREADS);       // [SIMP_MISC]
     u64* s_part  = reinterpret_cast<u64*>(s_misc + W_PART64);
     const SimpMapView& M = c.M;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int set = blockIdx.x;
 
     if (tid < SIMP_MISC) s_misc[tid] = 0;
@@ -130,21 +115,18 @@ __global__ __launch_bounds__(SIMP_THREADS) void simp_stats_kernel(SimpStatsCall 
     };
 
     int n_depth = 0, match = 0, n_mps = 0, n_red = 0;
-    u32 queued_before = 0;
-    for (int base = first; base < last; base += SIMP_THREADS)  // uniform
-    {
-        const int i = base + tid;
-        if (i < last)
-        {
+    walk_lists<SIMP_THREADS>(
+        first, last, c.long_min, s_queue, &s_misc[W_QUEUED],
+        [&](int i, int& fi, int& a, int& b) {  // every feature: its depth key and counts; true: its list is walked
             const int p = M.feat_point[i];
             u32 key     = SIMP_KEY_PAD;
+            bool walked = false;
             if (p < -1 || p >= M.n_points) s_misc[W_BAD] = 1;
             else if (p >= 0)
             {
                 key = simp_key(simp_depth(pose, M.pt_pos + (size_t)p * 3));
                 n_depth += 1;
                 const unsigned flags = M.pt_flags[p];
-                int a = 0, b = 0;
                 if (flags & SIMP_PT_BAD) {}
                 else if (!list_of(p, a, b)) s_misc[W_BAD] = 1;
                 else
@@ -153,27 +135,21 @@ __global__ __launch_bounds__(SIMP_THREADS) void simp_stats_kernel(SimpStatsCall 
                     if (simp_point_counts(flags, c.stereo, M.feat_depth[i], c.th_depth))
                     {
                         n_mps += 1;
-                        if (simp_list_walked(b - a))
-                        {
-                            if (b - a > c.long_min) s_queue[atomicAdd(&s_misc[W_QUEUED], 1u) - queued_before] = i;  // at most one per lane and round
-                            else
-                            {
-                                const int octave_i = M.feat_octave[i];
-                                int n              = 0;
-                                for (int o = a; o < b; ++o) n += qualifies(o, octave_i);
-                                n_red += simp_redundant(n) ? 1 : 0;
-                            }
-                        }
+                        walked = simp_list_walked(b - a);
                     }
                 }
             }
             s_key[i - first] = key;
-        }
-        __syncthreads();
-        const u32 queued = s_misc[W_QUEUED];  // a running total: nobody resets it between rounds
-        for (int e = wave; e < (int)(queued - queued_before); e += SIMP_THREADS / 64)
-        {
-            const int fi = s_queue[e];
+            fi               = i;
+            return walked;
+        },
+        [&](int fi, int a, int b) {
+            const int octave_i = M.feat_octave[fi];
+            int n              = 0;
+            for (int o = a; o < b; ++o) n += qualifies(o, octave_i);
+            n_red += simp_redundant(n) ? 1 : 0;
+        },
+        [&](int fi, int lane) {
             int la, lb;
             list_of(M.feat_point[fi], la, lb);  // checked when it was queued
             const int octave_i = M.feat_octave[fi];
@@ -181,10 +157,7 @@ __global__ __launch_bounds__(SIMP_THREADS) void simp_stats_kernel(SimpStatsCall 
             for (int o = la + lane; o < lb; o += 64) n += qualifies(o, octave_i);
             n = wave_sum_xor(n);
             if (lane == 0) n_red += simp_redundant(n) ? 1 : 0;
-        }
-        queued_before = queued;
-        __syncthreads();  // the queue is the next round's
-    }
+        });
     n_depth = wave_sum_xor(n_depth);
     match   = wave_sum_xor(match);
     n_mps   = wave_sum_xor(n_mps);
@@ -216,7 +189,7 @@ __global__ __launch_bounds__(SIMP_THREADS) void simp_stats_kernel(SimpStatsCall 
             [&](u32 T) {
                 int k = 0;
                 for (int i = tid; i < n; i += SIMP_THREADS) k += s_key[i] < T ? 1 : 0;  // the pads are above every T the select can reach
-                return (int)block_reduce((u64)k, [](u64 a, u64 b) { return a + b; }, s_part, pass);
+                return (int)block_reduce<SIMP_THREADS>((u64)k, [](u64 a, u64 b) { return a + b; }, s_part, pass);
             },
             simp_median_rank(r.n_depth)));
     }
@@ -235,7 +208,7 @@ __device__ __forceinline__ int simp_prim_lanes(int n, bool member, int root, con
     int joined = 0, weak = 0;
     for (int step = 1; step < n; ++step)  // uniform: at most n - 1 joins
     {
-        const u64 key = block_reduce(outside ? simp_prim_key(best, v) : 0ull, [](u64 a, u64 b) { return a > b ? a : b; }, s_part, pass);
+        const u64 key = block_reduce<SIMP_THREADS>(outside ? simp_prim_key(best, v) : 0ull, [](u64 a, u64 b) { return a > b ? a : b; }, s_part, pass);
         if (key == 0) break;
         const int j     = simp_prim_key_id(key);
         const int32_t w = simp_prim_key_weight(key);
@@ -376,14 +349,14 @@ __global__ __launch_bounds__(SIMP_THREADS) void simp_decide_kernel(SimpDecideCal
     int parent, weakest;
     simp_prim_lanes(n, tid < n, 0, s_tri, s_part, pass, parent, weakest);
     const bool at_root = tid < n && tid != 0 && parent == 0;
-    const int n_root   = (int)block_reduce((u64)(at_root ? 1 : 0), [](u64 a, u64 b) { return a + b; }, s_part, pass);
+    const int n_root   = (int)block_reduce<SIMP_THREADS>((u64)(at_root ? 1 : 0), [](u64 a, u64 b) { return a + b; }, s_part, pass);
     if (n_root == 0)  // uniform
     {
         if (tid == 0) c.out[set] = simp_verdict(SIMP_NO_CONN, 0.0, n, 0, 0);
         return;
     }
     // the smallest neighbour id: ~id is largest
-    const int first = (int)~(u32)block_reduce(at_root ? (u64)(u32)~(u32)tid : 0ull, [](u64 a, u64 b) { return a > b ? a : b; }, s_part, pass);
+    const int first = (int)~(u32)block_reduce<SIMP_THREADS>(at_root ? (u64)(u32)~(u32)tid : 0ull, [](u64 a, u64 b) { return a > b ? a : b; }, s_part, pass);
     double value = 0.0;
     if (n_root == 1)  // uniform
     {

@@ -17,6 +17,7 @@
 // point i+1), so one wavefront walks the points in order with the taken mask in LDS.
 #include "dispatch.hpp"
 #include "matcher_handle.hpp"
+#include "wg.hpp"
 
 namespace snk
 {
@@ -851,23 +852,7 @@ __global__ __launch_bounds__(256) void grid_kernel(const snk_kp64* __restrict__ 
         keys[i] = k;
     }
     __syncthreads();
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1)
-        {
-            for (int t = tid; t < (n_pow2 >> 1); t += 256)
-            {
-                const int i   = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int ixj = i | j;
-                const bool up = (i & k) == 0;
-                const u32 x = keys[i], y = keys[ixj];
-                if ((x > y) == up)
-                {
-                    keys[i]   = y;
-                    keys[ixj] = x;
-                }
-            }
-            __syncthreads();
-        }
+    block_sort<256>(keys, n_pow2);
     for (int p = tid; p < n; p += 256)
     {
         const u32 k       = keys[p];

@@ -415,6 +415,34 @@ def gather_case(pts_cap=64):
     return c
 
 
+LONG_RANGE = 65540  # features of one keyframe: the smallest count at the tests' scale whose length and prefix have a high 16-bit half
+
+
+def long_range_case(pts_cap=64):
+    """Keyframe 2 has LONG_RANGE features, all -1 except three at either end; two ordinary keyframes stand in front of it and two behind,
+    so that the keyframes behind it start at orders above 65 535 and its own last features win at such orders.  Asserts its coverage."""
+    n_points = 64
+    long_kf = [15, 20, 21] + [-1] * (LONG_RANGE - 6) + [22, 10, 23]
+    lists = [[10, 11, 12, -1, 13], [12, 14, 15], long_kf, [23, 24, 11], [25, 20, -1, 26]]
+    m = dict(feat_start=csr(lists), feat_point=np.array([p for lst in lists for p in lst], np.int32), pt_flags=np.zeros(n_points, np.uint8),
+             pt_last_seen=np.full(n_points, -1, np.int32), **point_tables(n_points))
+    sets = [([0, 1, 2, 3, 4], [21, 30, 24]), ([4, 3, 2, 1, 0], []), ([2], [22, 31]), ([2, 0], [])]
+    kf_cap = 16
+    local_kf = np.full((len(sets), kf_cap), -1, np.int32)
+    sel = np.zeros(len(sets), SELECT)
+    for s, (local, _) in enumerate(sets):
+        local_kf[s, :len(local)] = local
+        sel[s] = (len(local), len(local), 0, local[0], OK)
+    c = dict(m=m, frame_id=np.ones(len(sets), np.int32), local_kf=local_kf, sel=sel, set_start=csr([x[1] for x in sets]),
+             set_point=np.array([p for x in sets for p in x[1]], np.int32), pts_cap=pts_cap)
+    lm, ids, n_pts, res = gather(m, c["frame_id"], local_kf, sel, c["set_start"], c["set_point"], pts_cap)
+    assert len(long_kf) == LONG_RANGE and LONG_RANGE >> 16 == 1 and (res["status"] == OK).all()
+    assert ids[0, :n_pts[0]].tolist() == [10, 11, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 30] and tuple(res[0]) == (14, 11, 1, OK)
+    assert ids[1, :n_pts[1]].tolist() == [25, 20, 26, 23, 24, 11, 15, 21, 22, 10, 12, 14, 13]
+    assert ids[2, :n_pts[2]].tolist() == [15, 20, 21, 22, 10, 23, 31] and ids[3, :n_pts[3]].tolist() == [15, 20, 21, 22, 10, 23, 11, 12, 13]
+    return c
+
+
 GATHER_KEYS = ("feat_start", "feat_point", "pt_flags", "pt_last_seen")
 
 

@@ -237,6 +237,44 @@ def build_map(seed=3, n_kf=120, feats=64, stride=24, band=200, n_levels=8, imu=T
 
 QUERIES = [100, 45, 41, 5, 50, 60, 7, 110, 20]
 
+LONG_RANGE = 65540  # features of one keyframe: the smallest count at the tests' scale whose length and prefix have a high 16-bit half
+LONG_QUERIES = [4, 2]
+
+
+def long_range_map(seed=5, n_levels=8):
+    """Keyframe 2 has LONG_RANGE features, all -1 except three at either end.  The window of query 4 is its chain 0 .. 4: two ordinary
+    keyframes in front of the long one and two behind, which start at orders above 65 535; the window of query 2 ends with the long one.
+    Keyframe 5 is outside both windows and sees two of the points: a fixed camera.  No connections, no IMU tables."""
+    rng = np.random.RandomState(seed)
+    lists = [[10, 11, 12, -1, 13], [12, 14, 15], [15, 20, 21] + [-1] * (LONG_RANGE - 6) + [22, 10, 23], [23, 24, 11], [25, 20, -1, 26], [22, 13]]
+    n_kf, n_points = len(lists), 32
+    feat_start = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
+    feat_point = np.array([p for x in lists for p in x], np.int32)
+    n_feat = len(feat_point)
+    seen = [[] for _ in range(n_points)]
+    for k, x in enumerate(lists):
+        for f, p in enumerate(x):
+            if p >= 0:
+                seen[p].append((k, f))
+    pt_flags = np.zeros(n_points, np.uint8)
+    pt_flags[[14, 22]] = PT_CONST
+    quat = rng.randn(n_kf, 4)
+    depth = rng.uniform(0.5, 30.0, n_feat).astype(np.float32)
+    depth[::3] = -1.0
+    t = dict(kf_bad=np.zeros(n_kf, np.uint8), kf_prev=np.array([-1, 0, 1, 2, 3, -1], np.int32),
+             kf_pose=np.concatenate([quat / np.linalg.norm(quat, axis=1, keepdims=True), rng.randn(n_kf, 3)], axis=1),
+             feat_start=feat_start, feat_point=feat_point, feat_depth=depth, feat_uv=rng.uniform(0, 640, (n_feat, 2)).astype(np.float32),
+             feat_octave=rng.randint(0, n_levels, n_feat).astype(np.int32),
+             obs_start=np.concatenate([[0], np.cumsum([len(x) for x in seen])]).astype(np.int32),
+             obs=np.array([o for x in seen for o in x], np.int32).reshape(-1, 2), pt_flags=pt_flags, pt_pos=rng.randn(n_points, 3) * 5,
+             level_inv_sq_scale=(1.0 / (np.float32(1.2) ** np.arange(n_levels, dtype=np.float32)) ** 2).astype(np.float32),
+             conn_start=np.zeros(n_kf + 1, np.int32), conn_list=np.zeros(0, np.dtype([("weight", "<i4"), ("kf", "<i4")])))
+    (w4, s4), (w2, s2) = (local_scene(t, q, pt_cap=64, img_cap=16, obs_cap=256) for q in LONG_QUERIES)
+    assert w4 == [0, 1, 2, 3, 4] and w2 == [0, 1, 2] and s4["status"] == OK and s2["status"] == OK and LONG_RANGE >> 16 == 1
+    assert s4["pt_id"].tolist() == [10, 11, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26] and s4["img_kf"].tolist() == [0, 1, 2, 3, 4, 5]
+    assert s2["pt_id"].tolist() == [10, 11, 12, 13, 14, 15, 20, 21, 22, 23] and s2["img_kf"].tolist() == [0, 1, 2, 3, 5, 4]
+    return t
+
 
 def stream_chunks(t, scene):
     """(chunk of the walk, image or -1) of every observation of the scene's points: 256 points per chunk, 256 observations per sub-chunk."""

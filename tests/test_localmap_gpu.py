@@ -5,7 +5,8 @@ each output array: the results are integers and copied bytes, so there is nothin
 The shapes are localmap_numpy.select_case (votes of 0 / 1 / 14 / 15 / 16 / 20 / 21 / 80 / 272 entries, one cut by its cap, twins under two
 frame ids, connection lists of 0 / 3 / 5 / 9 entries, bad and repeated neighbours, kf_cap around n_local, three seeds) and gather_case
 (candidate totals at the scan-chunk edges, duplicates, skips, own points of every kind, pts_cap 64 and SNK_LMAP_MAX_PTS met from both
-sides, 40 ids on one slot, a probe chain that wraps, stage-1 statuses passed through); then the device forms' BAD_INDEX answers, the host
+sides, 40 ids on one slot, a probe chain that wraps, stage-1 statuses passed through) and long_range_case (a keyframe of 65 540
+features between ordinary ones); then the device forms' BAD_INDEX answers, the host
 forms' argument errors, a large call followed by a small one on one handle and the edge case in a child under SNK_DEBUG_POISON=1."""
 import ctypes as C
 import functools
@@ -168,6 +169,22 @@ def test_gather_host_and_device_forms_equal_the_restatement(pts_cap):
     want = gather_want(pts_cap, 0)
     assert same(host, want), differing(host, want)
     assert want[3]["status"][c["what"]["cap+1"]] == M.PTS_OVERFLOW and want[2][c["what"]["cap"]] == pts_cap
+
+
+def test_gather_with_a_feature_range_longer_than_65535():
+    """localmap_numpy.long_range_case: the high 16-bit halves of the range lengths and of their prefix sums are not 0."""
+    c = M.long_range_case(64)
+    b = builder(kf_cap=16)
+    try:
+        dev = dev_gather(b, c, 64)
+        host = host_gather(b, c, 64)
+    finally:
+        b.close()
+    m = c["m"]
+    want = M.gather(m, c["frame_id"], c["local_kf"], c["sel"], c["set_start"], c["set_point"], 64, FILL)
+    assert same(dev, want), differing(dev, want)
+    want = M.gather(m, c["frame_id"], c["local_kf"], c["sel"], c["set_start"], c["set_point"], 64, 0)
+    assert same(host, want), differing(host, want)
 
 
 def test_select_then_gather_on_the_device_without_a_copy_between():

@@ -4,7 +4,7 @@ pattern behind every count and a guard row on either side of every device array:
 values, so there is nothing to tolerate.
 
 The map is scene_numpy.build_map (120 keyframes, 64 features each, 3 080 points), whose builder raises unless it holds every property
-listed in scene_numpy.PROPERTIES; then every overflow status met at its cap and one above, the device forms' BAD_INDEX answers with the
+listed in scene_numpy.PROPERTIES, and scene_numpy.long_range_map (a window keyframe of 65 540 features); then every overflow status met at its cap and one above, the device forms' BAD_INDEX answers with the
 other sets of the batch unharmed, the table limits (32 768 keyframe slots, pt_cap 16 384, img_cap 4 096), two runs of one batch byte for
 byte, and two batches of different sizes on one handle in a child under SNK_DEBUG_POISON=1."""
 import functools
@@ -161,6 +161,19 @@ def test_device_forms_equal_the_restatement_and_two_runs_give_the_same_bytes():
     check_rows(o, expected)
     _, _, _, bytes_2 = run_dev(t, M.QUERIES, CAPS, b, d)
     assert bytes_1 == bytes_2  # no result depends on the order in which atomics land
+
+
+def test_gather_with_a_feature_range_longer_than_65535():
+    """scene_numpy.long_range_map: the high 16-bit halves of the range lengths and of their prefix sums are not 0."""
+    t = M.long_range_map()
+    expected = want(t, M.LONG_QUERIES, CAPS)
+    assert all(sc["status"] == M.OK for _, sc in expected)
+    win, res, o, _ = run_dev(t, M.LONG_QUERIES, CAPS)
+    check_window(win, res, expected, CAPS["win_cap"])
+    check_rows(o, expected)
+    win, res, o = run_host(t, M.LONG_QUERIES, CAPS)
+    check_window(win, res, expected, CAPS["win_cap"])
+    check_rows(o, expected)
 
 
 def test_without_imu_tables_or_gyro_weight_no_constraints_are_emitted():
